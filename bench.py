@@ -18,9 +18,13 @@ reverse sweep + ONE all-reduce of the flat gradient + fused Adam) and reports th
 time and bandwidth.
 
 Prints ONE JSON line (rank 0).  ``value`` / ``ms_per_step`` time exactly K steps with nothing else in
-the loop; ``roofline`` / ``kernels`` are measured live with HIP events recorded on the launch stream around
-every kernel launch of the same K steps run once more right after the timed region
-(``instrumented_ms_per_step``: what the events cost is then visible instead of sitting in the headline).
+the loop.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the result line.
+``--full`` adds everything else the benchmark measures or checks, after the timed region: ``roofline`` /
+``kernels`` measured live with HIP events recorded on the launch stream around every kernel launch of the
+same K steps run once more (``instrumented_ms_per_step``: what the events cost is then visible instead of
+sitting in the headline), the spot check against the oracle, the secondary lines, the CPU baseline, the
+U(1) block, the collective probes and the train-mode exchange A/B.  ``--dump-outputs DIR`` writes what
+the last timed step returned as ``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 import argparse
 import json
@@ -60,6 +64,10 @@ ALG_BYTES = {
     'l2q_scale_f64': 1152,
 }
 
+# --dump-outputs: elements kept of one output array (a seeded sample beyond that) and the cap on all files
+DUMP_SAMPLE = 1 << 18
+DUMP_MAX_BYTES = 64 << 20
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -74,6 +82,13 @@ def parse():
     ap.add_argument('--mode', choices=['l2hmc', 'hmc', 'train'], default='l2hmc')
     ap.add_argument('--micro-batch', type=int, default=None,
                     help='train mode: chains per tape micro-batch (needed at 16^4)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check everything beyond the headline (kernel '
+                         'table, rooflines, spot check, secondary lines, CPU baseline, U(1) block, probes); the '
+                         '--no-* switches below only apply to it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to DIR/<name>.npy (float32 / float64; outputs '
+                         f'larger than {DUMP_SAMPLE} elements as a fixed, seeded sample of them)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-spot-check', action='store_true')
     ap.add_argument('--no-comm-probe', action='store_true')
@@ -936,6 +951,158 @@ def native_comm_probe(dist, world, n_params, reps=3):
         return {'route': 'l2q_allreduce_grads', 'error': f'{type(e).__name__}: {e}'[:300]}
 
 
+def dump_outputs(outdir, result):
+    """--dump-outputs: what the last timed step returned to its caller -- x_out and every tensor or number of
+    the metrics dict, the init / proposed / out states of ``mc_states`` included (a lazy state is formed here,
+    after the timed region) -- one ``outdir/<name>.npy`` each: complex as a trailing (re, im) axis, 16- and
+    32-bit floats as float32, everything else as float64.  An array of more than DUMP_SAMPLE elements is
+    written as the DUMP_SAMPLE elements of its flattened form at sorted indices drawn with seed 0 from its
+    size alone, so that two builds run with the same arguments write the same sample."""
+    from l2hmc.dynamics.pytorch.dynamics import MonteCarloStates, State
+    arrays = {}
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v
+        elif isinstance(v, (bool, int, float, np.ndarray, np.number)):
+            arrays[name] = torch.as_tensor(np.asarray(v, dtype=np.float64))
+        elif isinstance(v, MonteCarloStates):
+            for k in ('init', 'proposed', 'out'):
+                walk(f'{name}.{k}', getattr(v, k))
+        elif isinstance(v, State):
+            walk(f'{name}.x', v.x)
+            walk(f'{name}.v', v.v)
+        elif isinstance(v, dict):
+            for k, vv in v.items():
+                if not str(k).startswith('_'):
+                    walk(f'{name}.{k}' if name else str(k), vv)
+    xout, metrics = result
+    walk('x', xout)
+    walk('', metrics)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        dt = np.float32 if t.dtype in (torch.float16, torch.bfloat16, torch.float32) else np.float64
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.to(torch.float64).cpu().numpy().astype(dt)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f'--dump-outputs: {len(out)} arrays of {total} bytes exceed {DUMP_MAX_BYTES}')
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
+def kernel_tables(args, ks, train):
+    """--full: the per-kernel table and the rooflines of the instrumented pass (KernelTimer.summary())."""
+    V = int(np.prod(args.lattice))
+    sites = args.nchains * V
+    total_k = sum(v[1] for v in ks.values())
+    kernels = {}
+    for name, (cnt, tt, fl) in sorted(ks.items(), key=lambda kv: -kv[1][1]):
+        ent = {'launches': cnt, 'avg_ms': round(tt / cnt * 1e3, 4),
+               'share': round(tt / total_k, 4)}
+        if name in ALG_BYTES and not (train and args.micro_batch):
+            ent['GB/s'] = round(sites * ALG_BYTES[name] / (tt / cnt) / 1e9, 1)
+        kernels[name] = ent
+    if len(kernels) > 24:                      # train mode: ~60 entry points; keep the top
+        kernels = dict(list(kernels.items())[:24])
+    traffic = load_traffic(args)
+
+    def hbm_roof(name):
+        cnt, tt, _ = ks[name]
+        ach = sites * ALG_BYTES[name] / (tt / cnt) / 1e9
+        tr_, src = traffic(name)
+        return {'kernel': name, 'symbol': native_name(name), 'bound': 'hbm',
+                'achieved': round(ach, 1),
+                'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(ach / HBM_PEAK_GBS, 4),
+                'traffic': tr_, 'traffic_source': src, 'avg_ms': round(tt / cnt * 1e3, 4),
+                'launches': cnt, 'algorithmic_bytes_per_launch': sites * ALG_BYTES[name],
+                'time_s': tt}
+
+    def native_name(name):
+        from l2hmc import native
+        return native.kernel_name(name, [int(i) for i in args.lattice])
+
+    def mfma_roof(names, label, flops, peak=FP64_MFMA_PEAK_TF, unit='TFLOP/s'):
+        cnt = sum(ks[n][0] for n in names)
+        tt = sum(ks[n][1] for n in names)
+        ach = flops / tt / 1e12
+        tr_, src = traffic(names[0])
+        return {'kernel': label, 'bound': 'mfma', 'achieved': round(ach, 2),
+                'peak': peak, 'unit': unit,
+                'frac': round(ach / peak, 4), 'traffic': tr_,
+                'traffic_source': src, 'avg_ms': round(tt / cnt * 1e3, 4), 'launches': cnt,
+                'time_s': tt}
+
+    rooflines = []
+    if not (train and args.micro_batch):
+        for fname in ('l2q_su3_force', 'l2q_su3_force_vec8', 'l2q_su3_force_kick'):
+            if fname in ks:
+                rooflines.append(hbm_roof(fname))
+        if 'l2q_su3_plaq_reduce' in ks:
+            rooflines.append(hbm_roof('l2q_su3_plaq_reduce'))
+        heads = [n for n in ('l2q_vnet_heads_vupdate_pair_f64', 'l2q_vnet_heads_vupdate_f64')
+                 if n in ks]
+        if heads:
+            per = 3 * 2.0 * args.nchains * args.units[-1] * 36 * V       # s, t, q heads
+            rooflines.append(mfma_roof(heads, 'l2q_vnet_heads_vupdate[_pair]_f64 (3 heads + '
+                                       'v-update)', per * sum(ks[n][0] for n in heads)))
+        if 'l2q_vnet_heads_vupdate_sliced_f64' in ks:
+            # the same heads with the fp64 products rebuilt from 28 exact int8 slice products
+            # (csrc/heads_sliced.hip).  `achieved` keeps the contract's meaning -- the ALGORITHMIC
+            # flops of the three fp64 GEMMs / time, against the fp64 MFMA peak (the instruction this
+            # replaces) --; `int8` prices the operations that actually execute (28 x as many) against
+            # the int8 MFMA peak, which is the unit that bounds the kernel
+            nm = 'l2q_vnet_heads_vupdate_sliced_f64'
+            per = 3 * 2.0 * args.nchains * args.units[-1] * 36 * V
+            r = mfma_roof([nm], 'l2q_vnet_heads_vupdate_sliced_f64 (3 heads, fp64 products from 28 int8 '
+                          'slice GEMMs, + v-update)', per * ks[nm][0])
+            tops = 28 * per * ks[nm][0] / ks[nm][1] / 1e12
+            r['int8'] = {'ops_per_launch': 28 * per, 'achieved': round(tops, 1),
+                         'peak': INT8_MFMA_PEAK_TOPS, 'unit': 'TOP/s',
+                         'frac': round(tops / INT8_MFMA_PEAK_TOPS, 4)}
+            rooflines.append(r)
+        if 'l2q_gemm_sliced_f64' in ks:
+            # the vnet's input layer the same way (csrc/gemm_sliced.hip: 28 int8 slice products per
+            # fp64 product, the activations sliced on the fly)
+            nm = 'l2q_gemm_sliced_f64'
+            r = mfma_roof([nm], 'l2q_gemm_sliced_f64 (input layer, fp64 products from 28 int8 slice '
+                          'GEMMs)', ks[nm][2])
+            tops = 28 * ks[nm][2] / ks[nm][1] / 1e12
+            r['int8'] = {'ops_per_launch': 28 * ks[nm][2] / ks[nm][0], 'achieved': round(tops, 1),
+                         'peak': INT8_MFMA_PEAK_TOPS, 'unit': 'TOP/s',
+                         'frac': round(tops / INT8_MFMA_PEAK_TOPS, 4)}
+            rooflines.append(r)
+        if 'l2q_gemm_f64' in ks:
+            rooflines.append(mfma_roof(['l2q_gemm_f64'], 'l2q_gemm_f64 (input + hidden layers)',
+                                       ks['l2q_gemm_f64'][2]))
+    # `roofline` = the dominant kernel (largest share of the timed region) among those
+    roofline = dict(max(rooflines, key=lambda r: r['time_s'])) if rooflines else None
+    for r in rooflines + ([roofline] if roofline else []):
+        r.pop('time_s', None)
+    if roofline is not None:
+        # BASELINE's metric has a second half, "plaquette-kernel HBM GB/s": the lattice kernels' own lines sit
+        # INSIDE `roofline` (the record the driver keeps), next to the int8 pricing of the sliced GEMMs
+        short = {'l2q_su3_plaq_reduce': 'plaq', 'l2q_su3_force': 'force', 'l2q_su3_force_vec8': 'force_vec8',
+                 'l2q_su3_force_kick': 'force_kick'}
+        roofline['hbm_kernels'] = {
+            short[r['kernel']]: {'symbol': r['symbol'], 'GB/s': r['achieved'], 'peak': r['peak'],
+                                 'frac': r['frac'], 'avg_ms': r['avg_ms'], 'launches': r['launches'],
+                                 'traffic': r['traffic'],
+                                 'algorithmic_bytes_per_launch': r['algorithmic_bytes_per_launch']}
+            for r in rooflines if r['bound'] == 'hbm' and r['kernel'] in short}
+        i8 = {('heads' if 'heads' in r['kernel'] else 'input_layer'): dict(r['int8'], avg_ms=r['avg_ms'])
+              for r in rooflines if 'int8' in r}
+        if i8:
+            roofline['int8'] = i8
+    return kernels, roofline, rooflines
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -1016,7 +1183,8 @@ def main():
         setup_steps += args.settle
         torch.cuda.synchronize()
     timer = KernelTimer()
-    timer.install()
+    if args.full:
+        timer.install()
     for _ in range(args.warmup):
         x, m = step(x)
 
@@ -1036,12 +1204,14 @@ def main():
         x, m = step(x)
     barrier()
     dt = time.perf_counter() - t0
-    timer.enabled = os.environ.get('L2Q_BENCH_NO_KTIMER') != '1'     # (experiment switch: no kernel table)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (x, m))
+    timer.enabled = args.full and os.environ.get('L2Q_BENCH_NO_KTIMER') != '1'  # (experiment switch: no kernel table)
     # (HIP events cannot be recorded inside a graph replay -- torch: "External events are disallowed in rocm" --
     # so the instrumented pass launches the SAME kernels eagerly: its per-kernel durations are those of the lower
     # clock state, i.e. an upper bound of what ran in the timed region; the rocprofv3 table of the graph replay
     # itself is profiles/r05*_bench_l2hmc_kernel_stats.txt)
-    skip_instr = os.environ.get('L2Q_BENCH_SKIP_INSTRUMENTED') == '1'
+    skip_instr = not args.full or os.environ.get('L2Q_BENCH_SKIP_INSTRUMENTED') == '1'
     # (L2Q_BENCH_SKIP_INSTRUMENTED=1: no second pass -- the LAST K trajectories of the process are then the timed ones,
     # which is what tools/kstats.sh selects for the rocprofv3 table of the graph replay)
     if graphed and not skip_instr:
@@ -1057,7 +1227,7 @@ def main():
         dyn.auto_graph = True
     per_rank = None
     ranks_check = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the N > 1 run checks itself: N distinct devices, the SAME model on every rank (built from the
         # seed), DIFFERENT chains on every rank -- or it fails loudly instead of reporting a number
         from l2hmc.utils.dist import model_checksum
@@ -1095,7 +1265,7 @@ def main():
     acc = m['acc']
     assert torch.isfinite(acc).all() and torch.isfinite(x).all(), 'non-finite trajectory'
     blocking_ms = None
-    if train and dist is not None:
+    if train and dist is not None and args.full:
         # A/B of the gradient exchange: the same K steps with ONE blocking all-reduce after the reverse sweep
         # instead of the slab-by-slab exchange that overlaps it (Trainer.overlap_grad_exchange); the
         # difference is what the overlap hides of the collective
@@ -1110,10 +1280,10 @@ def main():
         dist.all_reduce(tb, op=dist.ReduceOp.MAX)
         blocking_ms = float(tb.item()) / args.steps * 1e3
         tr.overlap_grad_exchange = True
-    ar = allreduce_probe(tr, dist, world) if train else None
+    ar = allreduce_probe(tr, dist, world) if train and args.full else None
     probe = None
     nprobe = None
-    if not train and args.mode == 'l2hmc' and not args.no_comm_probe:
+    if args.full and not train and args.mode == 'l2hmc' and not args.no_comm_probe:
         nparam = sum(p.numel() for p in dyn.vnet.parameters())
         if dist is not None:
             probe = collective_probe(dist, world, nparam)
@@ -1123,108 +1293,6 @@ def main():
             nprobe = native_comm_probe(dist, world, nparam)
 
     if rank == 0:
-        V = int(np.prod(args.lattice))
-        sites = args.nchains * V
-        ks = timer.summary()
-        total_k = sum(v[1] for v in ks.values())
-        kernels = {}
-        for name, (cnt, tt, fl) in sorted(ks.items(), key=lambda kv: -kv[1][1]):
-            ent = {'launches': cnt, 'avg_ms': round(tt / cnt * 1e3, 4),
-                   'share': round(tt / total_k, 4)}
-            if name in ALG_BYTES and not (train and args.micro_batch):
-                ent['GB/s'] = round(sites * ALG_BYTES[name] / (tt / cnt) / 1e9, 1)
-            kernels[name] = ent
-        if len(kernels) > 24:                      # train mode: ~60 entry points; keep the top
-            kernels = dict(list(kernels.items())[:24])
-        traffic = load_traffic(args)
-
-        def hbm_roof(name):
-            cnt, tt, _ = ks[name]
-            ach = sites * ALG_BYTES[name] / (tt / cnt) / 1e9
-            tr_, src = traffic(name)
-            return {'kernel': name, 'symbol': native_name(name), 'bound': 'hbm',
-                    'achieved': round(ach, 1),
-                    'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(ach / HBM_PEAK_GBS, 4),
-                    'traffic': tr_, 'traffic_source': src, 'avg_ms': round(tt / cnt * 1e3, 4),
-                    'launches': cnt, 'algorithmic_bytes_per_launch': sites * ALG_BYTES[name],
-                    'time_s': tt}
-
-        def native_name(name):
-            from l2hmc import native
-            return native.kernel_name(name, [int(i) for i in args.lattice])
-
-        def mfma_roof(names, label, flops, peak=FP64_MFMA_PEAK_TF, unit='TFLOP/s'):
-            cnt = sum(ks[n][0] for n in names)
-            tt = sum(ks[n][1] for n in names)
-            ach = flops / tt / 1e12
-            tr_, src = traffic(names[0])
-            return {'kernel': label, 'bound': 'mfma', 'achieved': round(ach, 2),
-                    'peak': peak, 'unit': unit,
-                    'frac': round(ach / peak, 4), 'traffic': tr_,
-                    'traffic_source': src, 'avg_ms': round(tt / cnt * 1e3, 4), 'launches': cnt,
-                    'time_s': tt}
-
-        rooflines = []
-        if not (train and args.micro_batch):
-            for fname in ('l2q_su3_force', 'l2q_su3_force_vec8', 'l2q_su3_force_kick'):
-                if fname in ks:
-                    rooflines.append(hbm_roof(fname))
-            if 'l2q_su3_plaq_reduce' in ks:
-                rooflines.append(hbm_roof('l2q_su3_plaq_reduce'))
-            heads = [n for n in ('l2q_vnet_heads_vupdate_pair_f64', 'l2q_vnet_heads_vupdate_f64')
-                     if n in ks]
-            if heads:
-                per = 3 * 2.0 * args.nchains * args.units[-1] * 36 * V       # s, t, q heads
-                rooflines.append(mfma_roof(heads, 'l2q_vnet_heads_vupdate[_pair]_f64 (3 heads + '
-                                           'v-update)', per * sum(ks[n][0] for n in heads)))
-            if 'l2q_vnet_heads_vupdate_sliced_f64' in ks:
-                # the same heads with the fp64 products rebuilt from 28 exact int8 slice products
-                # (csrc/heads_sliced.hip).  `achieved` keeps the contract's meaning -- the ALGORITHMIC
-                # flops of the three fp64 GEMMs / time, against the fp64 MFMA peak (the instruction this
-                # replaces) --; `int8` prices the operations that actually execute (28 x as many) against
-                # the int8 MFMA peak, which is the unit that bounds the kernel
-                nm = 'l2q_vnet_heads_vupdate_sliced_f64'
-                per = 3 * 2.0 * args.nchains * args.units[-1] * 36 * V
-                r = mfma_roof([nm], 'l2q_vnet_heads_vupdate_sliced_f64 (3 heads, fp64 products from 28 int8 '
-                              'slice GEMMs, + v-update)', per * ks[nm][0])
-                tops = 28 * per * ks[nm][0] / ks[nm][1] / 1e12
-                r['int8'] = {'ops_per_launch': 28 * per, 'achieved': round(tops, 1),
-                             'peak': INT8_MFMA_PEAK_TOPS, 'unit': 'TOP/s',
-                             'frac': round(tops / INT8_MFMA_PEAK_TOPS, 4)}
-                rooflines.append(r)
-            if 'l2q_gemm_sliced_f64' in ks:
-                # the vnet's input layer the same way (csrc/gemm_sliced.hip: 28 int8 slice products per
-                # fp64 product, the activations sliced on the fly)
-                nm = 'l2q_gemm_sliced_f64'
-                r = mfma_roof([nm], 'l2q_gemm_sliced_f64 (input layer, fp64 products from 28 int8 slice '
-                              'GEMMs)', ks[nm][2])
-                tops = 28 * ks[nm][2] / ks[nm][1] / 1e12
-                r['int8'] = {'ops_per_launch': 28 * ks[nm][2] / ks[nm][0], 'achieved': round(tops, 1),
-                             'peak': INT8_MFMA_PEAK_TOPS, 'unit': 'TOP/s',
-                             'frac': round(tops / INT8_MFMA_PEAK_TOPS, 4)}
-                rooflines.append(r)
-            if 'l2q_gemm_f64' in ks:
-                rooflines.append(mfma_roof(['l2q_gemm_f64'], 'l2q_gemm_f64 (input + hidden layers)',
-                                           ks['l2q_gemm_f64'][2]))
-        # `roofline` = the dominant kernel (largest share of the timed region) among those
-        roofline = dict(max(rooflines, key=lambda r: r['time_s'])) if rooflines else None
-        for r in rooflines + ([roofline] if roofline else []):
-            r.pop('time_s', None)
-        if roofline is not None:
-            # BASELINE's metric has a second half, "plaquette-kernel HBM GB/s": the lattice kernels' own lines sit
-            # INSIDE `roofline` (the record the driver keeps), next to the int8 pricing of the sliced GEMMs
-            short = {'l2q_su3_plaq_reduce': 'plaq', 'l2q_su3_force': 'force', 'l2q_su3_force_vec8': 'force_vec8',
-                     'l2q_su3_force_kick': 'force_kick'}
-            roofline['hbm_kernels'] = {
-                short[r['kernel']]: {'symbol': r['symbol'], 'GB/s': r['achieved'], 'peak': r['peak'],
-                                     'frac': r['frac'], 'avg_ms': r['avg_ms'], 'launches': r['launches'],
-                                     'traffic': r['traffic'],
-                                     'algorithmic_bytes_per_launch': r['algorithmic_bytes_per_launch']}
-                for r in rooflines if r['bound'] == 'hbm' and r['kernel'] in short}
-            i8 = {('heads' if 'heads' in r['kernel'] else 'input_layer'): dict(r['int8'], avg_ms=r['avg_ms'])
-                  for r in rooflines if 'int8' in r}
-            if i8:
-                roofline['int8'] = i8
         nchain_lf = world * args.nchains * nlf_exec * args.steps
         what = {'l2hmc': 'Dynamics.forward merged L2HMC', 'hmc': 'apply_transition_hmc',
                 'train': 'Trainer.train_step (tape + reverse sweep + all-reduce + Adam)'}[args.mode]
@@ -1244,36 +1312,42 @@ def main():
                                    f'(mc_states.out.v is formed on first access)',
                        'global_chains': world * args.nchains, 'parallelism': f'chains sharded x{world}'},
             # ranks of the RCCL communicator that executed in this run (N = 1: the one-rank
-            # communicator of the native probe, if it ran)
+            # communicator of the native probe, which only --full runs: 0 in a plain N = 1 line)
             'rccl_ranks': (world if (dist is not None and backend == 'nccl')
                            else (f'{world} ({backend})' if dist is not None
                                  else (1 if (nprobe or {}).get('sum_correct') else 0))),
-            'roofline': roofline,
-            'rooflines': rooflines,
-            'instrumented_ms_per_step': round(dt_instr / args.steps * 1e3, 3),
-            'launch_path': ('HIP-graph replay behind Dynamics.forward (Dynamics.auto_graph, default); the kernel '
-                            'table / rooflines below come from the instrumented pass on eager launches of the same '
-                            'kernels (HIP events cannot be recorded inside a replay): an upper bound of the '
-                            'durations in the timed region') if graphed else 'eager launches',
+            'roofline': None,
             'setup_steps': setup_steps,
-            'kernel_time_fraction_of_wall': round(total_k / dt_instr, 4),
-            'kernels': kernels,
             'accept_prob_mean': round(float(acc.mean()), 4),
         }
+        if args.full:
+            ks = timer.summary()
+            kernels, out['roofline'], rooflines = kernel_tables(args, ks, train)
+            out.update({
+                'rooflines': rooflines,
+                'instrumented_ms_per_step': round(dt_instr / args.steps * 1e3, 3),
+                'launch_path': ('HIP-graph replay behind Dynamics.forward (Dynamics.auto_graph, default); the kernel '
+                                'table / rooflines below come from the instrumented pass on eager launches of the '
+                                'same kernels (HIP events cannot be recorded inside a replay): an upper bound of the '
+                                'durations in the timed region') if graphed else 'eager launches',
+                'kernel_time_fraction_of_wall': round(sum(v[1] for v in ks.values()) / dt_instr, 4),
+                'kernels': kernels})
         if args.mode == 'l2hmc' and float(acc.mean()) == 0.0:
             # default-initialised heads from a hot start reject every proposal (dH ~ -50; the reference would
             # too), so the timed loop takes the reject branch of the final select.  The rate does not depend on
             # it: `secondary.l2hmc_scaled_heads` runs the same trajectory with the heads scaled so that about
             # half of the chains accept (and x changes from step to step)
             out['accept_prob_note'] = ('random-init networks from a hot start reject everything; see '
-                                       'secondary.l2hmc_scaled_heads for the same rate at acceptance ~0.5')
+                                       'secondary.l2hmc_scaled_heads (--full) for the same rate at acceptance ~0.5')
         if per_rank is not None:
             unit_per_rank = args.nchains * nlf_exec * args.steps
             rates = sorted(unit_per_rank / t for t in per_rank)
             out['per_rank'] = {'unit': 'chain*leapfrog-steps/s per rank', 'min': round(rates[0], 1),
                                'median': round(rates[len(rates) // 2], 1), 'max': round(rates[-1], 1),
                                'seconds_min': round(per_rank[0], 4), 'seconds_max': round(per_rank[-1], 4),
-                               'rates': [round(r, 1) for r in rates], 'self_check': ranks_check}
+                               'rates': [round(r, 1) for r in rates]}
+            if args.full:
+                out['per_rank']['self_check'] = ranks_check
         if probe is not None:
             out['grad_allreduce_probe'] = probe
         if nprobe is not None:
@@ -1284,7 +1358,7 @@ def main():
                             'blocking_exchange_ms_per_step': None if blocking_ms is None else round(blocking_ms, 3),
                             'micro_batch': args.micro_batch, 'loss': m.get('loss'),
                             'peak_mem_GiB': round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
-        if world == 1 and not train:
+        if args.full and world == 1 and not train:
             if not args.no_spot_check:
                 out['spot_check'] = spot_check(dyn, lat, x, args)
             if not args.no_cpu_baseline:

@@ -5,7 +5,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, 'bench.py', '--no-cpu-baseline', '--no-spot-check'] + sys.argv[1:],
+out = subprocess.run([sys.executable, 'bench.py', '--full', '--no-cpu-baseline', '--no-spot-check'] + sys.argv[1:],
                      capture_output=True, text=True).stdout.strip().splitlines()[-1]
 d = json.loads(out)
 print(f"value {d['value']:.0f} ms/step {d['ms_per_step']:.3f}  " +

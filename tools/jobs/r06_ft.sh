@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 o=gpurun_out/r06ft; mkdir -p $o
 for r in 1 2; do for ft in 5 7; do
-  L2Q_TUNING=force_tile=$ft python bench.py --no-cpu-baseline --no-spot-check --no-u1 --no-comm-probe > $o/b_${ft}_$r.json 2>/dev/null
+  L2Q_TUNING=force_tile=$ft python bench.py --full --no-cpu-baseline --no-spot-check --no-u1 --no-comm-probe > $o/b_${ft}_$r.json 2>/dev/null
   python - $o/b_${ft}_$r.json $ft <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).readline())

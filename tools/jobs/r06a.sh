@@ -7,9 +7,9 @@ tag="${1:-r06a}"
 o="gpurun_out/$tag"; mkdir -p "$o"
 export TMPDIR=/tmp
 python -m pytest tests -q -m gpu -x 2>&1 | tail -4 | tee "$o/pytest_gpu.txt"
-python bench.py > "$o/bench_l2hmc.json" 2> "$o/bench_l2hmc.err"; echo "bench rc=$?"
-L2Q_BENCH_SHARE_GPU=1 L2Q_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 8 --steps 3 --warmup 1 --nchains 32 --no-u1 > "$o/bench_8ranks_gloo_shared_gpu.json" 2> "$o/bench_8ranks.err"; echo "8 ranks sampling rc=$?"
-L2Q_BENCH_SHARE_GPU=1 L2Q_BENCH_BACKEND=gloo timeout 1200 python bench.py --gpus 8 --mode train --steps 3 --warmup 1 --nchains 32 --no-u1 > "$o/bench_train_8ranks_gloo_shared_gpu.json" 2> "$o/bench_train_8ranks.err"; echo "8 ranks train rc=$?"
+python bench.py --full > "$o/bench_l2hmc.json" 2> "$o/bench_l2hmc.err"; echo "bench rc=$?"
+L2Q_BENCH_SHARE_GPU=1 L2Q_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 8 --steps 3 --warmup 1 --nchains 32 --no-u1 > "$o/bench_8ranks_gloo_shared_gpu.json" 2> "$o/bench_8ranks.err"; echo "8 ranks sampling rc=$?"
+L2Q_BENCH_SHARE_GPU=1 L2Q_BENCH_BACKEND=gloo timeout 1200 python bench.py --full --gpus 8 --mode train --steps 3 --warmup 1 --nchains 32 --no-u1 > "$o/bench_train_8ranks_gloo_shared_gpu.json" 2> "$o/bench_train_8ranks.err"; echo "8 ranks train rc=$?"
 tail -3 "$o/bench_8ranks.err" "$o/bench_train_8ranks.err"
 python - "$o" <<'PY'
 import json, sys
