@@ -475,6 +475,12 @@ int l2q_im2col_periodic_f32(const float* in, long sn, long sc, long sh, long sw,
                             void* stream);
 int l2q_maxpool_act_nhwc_f32(const float* in, int nb, int H, int W, int C, int pool, int act,
                              float* out, void* stream);
+/* fp64 twins (the conv stack under precision=float64) */
+int l2q_im2col_periodic_f64(const double* in, long sn, long sc, long sh, long sw, int nb, int C,
+                            int H, int W, int k, int channels_last_cols, double* col,
+                            void* stream);
+int l2q_maxpool_act_nhwc_f64(const double* in, int nb, int H, int W, int C, int pool, int act,
+                             double* out, void* stream);
 /* The conv layer without the col matrix: im2col happens inside the A-tile loader of the f32
  * MFMA GEMM.  out[(b*Ho + ho)*Wo + wo][cout] = act(conv + bias) (NHWC); weight [cout][C k k] in
  * nn.Conv2d's flatten order (ci, i, j), or -- channels_last_cols != 0 -- permuted to (i, j, ci) so
@@ -484,9 +490,15 @@ int l2q_maxpool_act_nhwc_f32(const float* in, int nb, int H, int W, int C, int p
 int l2q_conv_gemm_periodic_f32(const float* in, long sn, long sc, long sh, long sw, int nb, int C,
                                int H, int W, int k, const float* weight, int channels_last_cols,
                                const float* bias, int cout, int act, float* out, void* stream);
+/* fp64: the same implicit GEMM on v_mfma_f64_16x16x4_f64 (16-byte gathers of two channels) */
+int l2q_conv_gemm_periodic_f64(const double* in, long sn, long sc, long sh, long sw, int nb, int C,
+                               int H, int W, int k, const double* weight, int channels_last_cols,
+                               const double* bias, int cout, int act, double* out, void* stream);
 /* out[b][h][w][c] = c < C ? in[b][c][h][w] : 0 for c < cpad (fp32 NCHW -> NHWC, channels padded
  * to a 16-byte group): lets the first conv layer use the vector gathers of the later ones. */
 int l2q_nchw_to_nhwc_pad_f32(const float* in, int nb, int C, int H, int W, int cpad, float* out,
+                             void* stream);
+int l2q_nchw_to_nhwc_pad_f64(const double* in, int nb, int C, int H, int W, int cpad, double* out,
                              void* stream);
 
 /* ---------------------------------------------------------------- fused U(1) sub-updates (fp32)
@@ -571,10 +583,16 @@ int l2q_bn_bwd(const void* dy, const void* x, const void* save_mean, const void*
 int l2q_col2im_periodic_f32(const float* dcol, long sn, long sc, long sh, long sw, int nb, int C,
                             int H, int W, int k, int channels_last_cols, float* dx,
                             void* stream);
+int l2q_col2im_periodic_f64(const double* dcol, long sn, long sc, long sh, long sw, int nb, int C,
+                            int H, int W, int k, int channels_last_cols, double* dx,
+                            void* stream);
 /* adjoint of l2q_maxpool_act_nhwc_f32: din[nb][H][W][C] overwritten (first maximum of each
  * window receives dout * act'(out)) */
 int l2q_maxpool_act_nhwc_bwd_f32(const float* dout, const float* out, const float* in, int nb,
                                  int H, int W, int C, int pool, int act, float* din,
+                                 void* stream);
+int l2q_maxpool_act_nhwc_bwd_f64(const double* dout, const double* out, const double* in, int nb,
+                                 int H, int W, int C, int pool, int act, double* din,
                                  void* stream);
 /* VJP of the U(1) force (the reference differentiates through autograd.grad(create_graph=True),
  * lattice/u1/pytorch/lattice.py:102-117):  dx += D^T [cos(theta) beta (D dF)] */

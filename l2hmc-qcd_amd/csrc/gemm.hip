@@ -308,19 +308,21 @@ struct ConvGeom {
 
 // BN = 32 / 64 / 128 output-channel tile: the conv layers have 8..128 channels, a fixed 128-wide
 // tile would spend most MFMAs on padding.
-// VEC4: NHWC input, (i, j, ci) K order, C % 4 == 0: a thread gathers four consecutive input
-// channels of one tap with one 16-byte load (4x fewer gather instructions than element-wise).
-template <int KS, int BN, bool VEC4>
-__global__ __launch_bounds__(kBlock, 2) void conv_gemm_kernel(const float* __restrict__ in,
+// VECG: NHWC input, (i, j, ci) K order, C % VEC == 0: a thread gathers VEC consecutive input
+// channels of one tap with one 16-byte load (float4 / double2: VEC x fewer gather instructions
+// than element-wise).  T = float: v_mfma_f32_16x16x4_f32, T = double: v_mfma_f64_16x16x4_f64 (twice
+// the accumulator VGPRs and LDS bytes of the f32 tile).
+template <typename T, int KS, int BN, bool VECG>
+__global__ __launch_bounds__(kBlock, 2) void conv_gemm_kernel(const T* __restrict__ in,
                                                               ConvGeom g,
-                                                              const float* __restrict__ Wt, int N,
-                                                              Epilogue<float> epi,
-                                                              float* __restrict__ C) {
-  using T = float;
+                                                              const T* __restrict__ Wt, int N,
+                                                              Epilogue<T> epi,
+                                                              T* __restrict__ C) {
   constexpr int BM = 128;
   constexpr int WN = BN >= 64 ? 2 : 1, WM = 4 / WN;       // wavefront grid over the tile
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 16, NI = TN / 16;
-  using acc_t = Mfma<T>::acc_t;
+  using acc_t = typename Mfma<T>::acc_t;
+  using vec_t = typename Mfma<T>::vec_t;
   __shared__ T As[BM][LDP];
   __shared__ T Ws[BN][LDP];
   __shared__ long rbase[BM];
@@ -354,7 +356,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_gemm_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = (acc_t){0, 0, 0, 0};
 
-  constexpr int AV = VEC4 ? 4 : 1;
+  constexpr int AV = VECG ? Mfma<T>::VEC : 1;
   constexpr int SRPP = kBlock / (BK / AV), SNP = BM / SRPP;       // rows per pass, passes
   const int kq = (tid % (BK / AV)) * AV, rq = tid / (BK / AV);
   T areg[SNP][AV];
@@ -377,10 +379,10 @@ __global__ __launch_bounds__(kBlock, 2) void conv_gemm_kernel(const float* __res
         int r_ = rr0[row_] + i_; if (r_ >= g.H) r_ -= g.H; if (r_ >= g.H) r_ %= g.H;    \
         int c_ = rc0[row_] + j_; if (c_ >= g.W) c_ -= g.W; if (c_ >= g.W) c_ %= g.W;    \
         const T* src_ = in + base_ + coff_ + r_ * g.sh + c_ * g.sw;                     \
-        if (VEC4) {                                                                     \
-          const float4 v_ = *reinterpret_cast<const float4*>(src_);                     \
-          areg[p][0] = v_.x; areg[p][AV > 1 ? 1 : 0] = v_.y;                            \
-          areg[p][AV > 2 ? 2 : 0] = v_.z; areg[p][AV > 3 ? 3 : 0] = v_.w;               \
+        if (VECG) {                                                                     \
+          const vec_t v_ = *reinterpret_cast<const vec_t*>(src_);                       \
+          const T* e_ = reinterpret_cast<const T*>(&v_);                                \
+          _Pragma("unroll") for (int e = 0; e < AV; ++e) areg[p][e] = e_[e];            \
         } else {                                                                        \
           areg[p][0] = src_[0];                                                         \
         }                                                                               \
@@ -1135,6 +1137,62 @@ static int gemm_launch(const T* A, const T* W, int M, int N, long K, const T* A2
   return check_launch("l2q_gemm");
 }
 
+// Periodic implicit-GEMM conv layer, fp32 or fp64 (l2q_conv_gemm_periodic_f32 / _f64)
+template <typename T>
+int conv_gemm_launch(const T* in, long sn, long sc, long sh, long sw, int nb, int C, int H, int W,
+                     int k, const T* weight, int channels_last_cols, const T* bias, int cout, int act,
+                     T* out, hipStream_t st, const char* what) {
+#define L2Q_CONV_REQUIRE(cond, code, msg)                       \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      ::l2q::set_error("%s: %s", what, msg);                    \
+      return code;                                              \
+    }                                                           \
+  } while (0)
+  L2Q_CONV_REQUIRE(in && weight && out, L2Q_EINVAL, "null pointer");
+  L2Q_CONV_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL,
+                   "non-positive size");
+  L2Q_CONV_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  ConvGeom g;
+  g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
+  g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
+  g.clast = channels_last_cols ? 1 : 0;
+  g.M = (long)nb * g.Ho * g.Wo;
+  L2Q_CONV_REQUIRE(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
+  Epilogue<T> epi{bias, nullptr, nullptr, (T)1, act, 0};
+  const int bn = cout <= 32 ? 32 : cout <= 64 ? 64 : 128;
+  const dim3 grid((unsigned)cdiv(cout, bn), (unsigned)cdiv(g.M, 128)), block(kBlock);
+  // 16-byte channel gathers (float4 / double2): NHWC input, (i, j, ci) order, C % VEC == 0, aligned
+  constexpr int V = Mfma<T>::VEC;
+  const bool vecg = g.clast && sc == 1 && C % V == 0 && sw % V == 0 && sh % V == 0 && sn % V == 0 &&
+                    (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+#define L2Q_CGB(KS, BNV)                                                                          \
+  do {                                                                                            \
+    if (vecg) hipLaunchKernelGGL((conv_gemm_kernel<T, KS, BNV, true>), grid, block, 0, st, in, g, \
+                                 weight, cout, epi, out);                                         \
+    else hipLaunchKernelGGL((conv_gemm_kernel<T, KS, BNV, false>), grid, block, 0, st, in, g,     \
+                            weight, cout, epi, out);                                              \
+  } while (0)
+#define L2Q_CG(KS)                                                     \
+  do {                                                                 \
+    if (bn == 32) L2Q_CGB(KS, 32);                                     \
+    else if (bn == 64) L2Q_CGB(KS, 64);                                \
+    else L2Q_CGB(KS, 128);                                             \
+  } while (0)
+  switch (k) {
+    case 1: L2Q_CG(1); break;
+    case 2: L2Q_CG(2); break;
+    case 3: L2Q_CG(3); break;
+    case 4: L2Q_CG(4); break;
+    case 5: L2Q_CG(5); break;
+    default: L2Q_CG(0); break;
+  }
+#undef L2Q_CG
+#undef L2Q_CGB
+#undef L2Q_CONV_REQUIRE
+  return check_launch(what);
+}
+
 }  // namespace l2q
 
 using namespace l2q;
@@ -1189,47 +1247,15 @@ int l2q_gemm_ex(const void* A, int a_trans, const void* W, int w_trans, int M, i
 int l2q_conv_gemm_periodic_f32(const float* in, long sn, long sc, long sh, long sw, int nb, int C,
                                int H, int W, int k, const float* weight, int channels_last_cols,
                                const float* bias, int cout, int act, float* out, void* stream) {
-  L2Q_REQUIRE(in && weight && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL,
-              "non-positive size");
-  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  ConvGeom g;
-  g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
-  g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
-  g.clast = channels_last_cols ? 1 : 0;
-  g.M = (long)nb * g.Ho * g.Wo;
-  L2Q_REQUIRE(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
-  Epilogue<float> epi{bias, nullptr, nullptr, 1.0f, act, 0};
-  const int bn = cout <= 32 ? 32 : cout <= 64 ? 64 : 128;
-  const dim3 grid((unsigned)cdiv(cout, bn), (unsigned)cdiv(g.M, 128)), block(kBlock);
-  hipStream_t st = (hipStream_t)stream;
-  // 16-byte channel gathers: NHWC input, (i, j, ci) order, C % 4 == 0, aligned
-  const bool vec4 = g.clast && sc == 1 && C % 4 == 0 && sw % 4 == 0 && sh % 4 == 0 && sn % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-#define L2Q_CGB(KS, BNV)                                                                          \
-  do {                                                                                            \
-    if (vec4) hipLaunchKernelGGL((conv_gemm_kernel<KS, BNV, true>), grid, block, 0, st, in, g,    \
-                                 weight, cout, epi, out);                                         \
-    else hipLaunchKernelGGL((conv_gemm_kernel<KS, BNV, false>), grid, block, 0, st, in, g,        \
-                            weight, cout, epi, out);                                              \
-  } while (0)
-#define L2Q_CG(KS)                                                     \
-  do {                                                                 \
-    if (bn == 32) L2Q_CGB(KS, 32);                                     \
-    else if (bn == 64) L2Q_CGB(KS, 64);                                \
-    else L2Q_CGB(KS, 128);                                             \
-  } while (0)
-  switch (k) {
-    case 1: L2Q_CG(1); break;
-    case 2: L2Q_CG(2); break;
-    case 3: L2Q_CG(3); break;
-    case 4: L2Q_CG(4); break;
-    case 5: L2Q_CG(5); break;
-    default: L2Q_CG(0); break;
-  }
-#undef L2Q_CG
-#undef L2Q_CGB
-  return check_launch("l2q_conv_gemm_periodic_f32");
+  return conv_gemm_launch<float>(in, sn, sc, sh, sw, nb, C, H, W, k, weight, channels_last_cols, bias,
+                                 cout, act, out, (hipStream_t)stream, "l2q_conv_gemm_periodic_f32");
+}
+
+int l2q_conv_gemm_periodic_f64(const double* in, long sn, long sc, long sh, long sw, int nb, int C,
+                               int H, int W, int k, const double* weight, int channels_last_cols,
+                               const double* bias, int cout, int act, double* out, void* stream) {
+  return conv_gemm_launch<double>(in, sn, sc, sh, sw, nb, C, H, W, k, weight, channels_last_cols,
+                                  bias, cout, act, out, (hipStream_t)stream, "l2q_conv_gemm_periodic_f64");
 }
 
 size_t l2q_vnet_heads_ws_bytes(int M, long N) {

@@ -8,6 +8,7 @@
 // training.py).  Per-chain reductions (d eps) finish inside one workgroup in a fixed order.
 #include "l2q_common.hpp"
 #include "u1_math.hpp"
+#include <limits>
 
 namespace l2q {
 
@@ -244,9 +245,10 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_kernel(
 // Adjoint of im2col_periodic: dx[b][ci][r][c] = sum over (ho, i), (wo, j) whose source pixel
 // is (r, c) of dcol[(b, ho, wo)][(ci, i, j)].  Gather form (no atomics): one thread per input
 // element enumerates its (ho, i) x (wo, j) pre-images in a fixed order.
+template <typename T>
 __global__ __launch_bounds__(kBlock) void col2im_periodic_kernel(
-    const float* __restrict__ dcol, long sn, long sc, long sh, long sw, int C, int H, int W, int k,
-    int Ho, int Wo, int Kc, long total, int clast, float* __restrict__ dx) {
+    const T* __restrict__ dcol, long sn, long sc, long sh, long sw, int C, int H, int W, int k,
+    int Ho, int Wo, int Kc, long total, int clast, T* __restrict__ dx) {
   const long idx = (long)blockIdx.x * kBlock + threadIdx.x;
   if (idx >= total) return;
   // thread order follows the fastest index of dcol's columns: (b, ci, r, c) for the (ci, i, j)
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void col2im_periodic_kernel(
     ci = (int)((idx / ((long)W * H)) % C);
     b = idx / ((long)W * H * C);
   }
-  float acc = 0.0f;
+  T acc = (T)0;
   for (int i = 0; i < k; ++i) {
     int h0 = (r + (k - 1) - i) % H; if (h0 < 0) h0 += H;
     for (int ho = h0; ho < Ho; ho += H)
@@ -281,9 +283,10 @@ __global__ __launch_bounds__(kBlock) void col2im_periodic_kernel(
 // out = act(maxpool(in)) (NHWC, floor mode).  din[window argmax] = dout * act'(out); every
 // other input element (and the rows / columns the floor drops) gets 0.  First maximum in
 // row-major window order wins, like nn.MaxPool2d.
+template <typename T>
 __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_bwd_kernel(
-    const float* __restrict__ dout, const float* __restrict__ out, const float* __restrict__ in,
-    int H, int W, int C, int pool, int act, int Ho, int Wo, long total, float* __restrict__ din) {
+    const T* __restrict__ dout, const T* __restrict__ out, const T* __restrict__ in,
+    int H, int W, int C, int pool, int act, int Ho, int Wo, long total, T* __restrict__ din) {
   const long idx = (long)blockIdx.x * kBlock + threadIdx.x;
   if (idx >= total) return;
   const int c = (int)(idx % C);
@@ -291,25 +294,25 @@ __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_bwd_kernel(
   const int h = (int)((idx / ((long)C * W)) % H);
   const long b = idx / ((long)C * W * H);
   const int ho = h / pool, wo = w / pool;
-  float g = 0.0f;
+  T g = (T)0;
   if (ho < Ho && wo < Wo) {
-    float best = -3.402823466e38f;
+    T best = std::numeric_limits<T>::lowest();
     int bh = 0, bw = 0;
     for (int ph = 0; ph < pool; ++ph)
       for (int pw = 0; pw < pool; ++pw) {
-        const float val = in[((b * H + ho * pool + ph) * W + wo * pool + pw) * C + c];
+        const T val = in[((b * H + ho * pool + ph) * W + wo * pool + pw) * C + c];
         if (val > best) { best = val; bh = ph; bw = pw; }
       }
     if (ho * pool + bh == h && wo * pool + bw == w) {
       const long o = ((b * Ho + ho) * (long)Wo + wo) * C + c;
-      const float y = out[o];
-      float d;
+      const T y = out[o];
+      T d;
       switch (act) {
-        case L2Q_ACT_TANH: d = 1.0f - y * y; break;
-        case L2Q_ACT_RELU: d = y > 0.0f ? 1.0f : 0.0f; break;
-        case L2Q_ACT_LEAKY_RELU: d = y > 0.0f ? 1.0f : 0.01f; break;
-        case L2Q_ACT_ELU: d = y > 0.0f ? 1.0f : y + 1.0f; break;
-        default: d = 1.0f; break;
+        case L2Q_ACT_TANH: d = (T)1 - y * y; break;
+        case L2Q_ACT_RELU: d = y > (T)0 ? (T)1 : (T)0; break;
+        case L2Q_ACT_LEAKY_RELU: d = y > (T)0 ? (T)1 : (T)0.01; break;
+        case L2Q_ACT_ELU: d = y > (T)0 ? (T)1 : y + (T)1; break;
+        default: d = (T)1; break;
       }
       g = dout[o] * d;
     }
@@ -503,6 +506,43 @@ using namespace l2q;
 
 static inline unsigned grid1(long n, int block = kBlock) { return (unsigned)cdiv(n, block); }
 
+// ---- host side of the conv-stack backward kernels, fp32 / fp64 (entry point name `what` in errors)
+#define L2Q_REQUIRE_W(cond, code, msg)                          \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      ::l2q::set_error("%s: %s", what, msg);                    \
+      return code;                                              \
+    }                                                           \
+  } while (0)
+
+template <typename T>
+int col2im_periodic_launch(const T* dcol, long sn, long sc, long sh, long sw, int nb, int C, int H, int W,
+                           int k, int channels_last_cols, T* dx, hipStream_t st, const char* what) {
+  L2Q_REQUIRE_W(dcol && dx, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0, L2Q_EINVAL, "non-positive size");
+  const int Ho = H + k - 1, Wo = W + k - 1, Kc = C * k * k;
+  const long total = (long)nb * C * H * W;
+  L2Q_REQUIRE_W(cdiv(total, kBlock) < 0x7fffffffL, L2Q_ESHAPE, "grid too large");
+  hipLaunchKernelGGL(col2im_periodic_kernel<T>, dim3(grid1(total)), dim3(kBlock), 0, st, dcol, sn, sc, sh,
+                     sw, C, H, W, k, Ho, Wo, Kc, total, channels_last_cols ? 1 : 0, dx);
+  return check_launch(what);
+}
+
+template <typename T>
+int maxpool_act_nhwc_bwd_launch(const T* dout, const T* out, const T* in, int nb, int H, int W, int C,
+                                int pool, int act, T* din, hipStream_t st, const char* what) {
+  L2Q_REQUIRE_W(dout && out && in && din, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE_W(act != L2Q_ACT_SWISH, L2Q_EINVAL, "swish is not supported by the training path");
+  const int Ho = H / pool, Wo = W / pool;
+  L2Q_REQUIRE_W(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
+  const long total = (long)nb * H * W * C;
+  hipLaunchKernelGGL(maxpool_act_nhwc_bwd_kernel<T>, dim3(grid1(total)), dim3(kBlock), 0, st, dout, out,
+                     in, H, W, C, pool, act, Ho, Wo, total, din);
+  return check_launch(what);
+}
+#undef L2Q_REQUIRE_W
+
 extern "C" {
 
 int l2q_act_bwd(const void* dy, const void* y, int act, long n, int elem_bytes, void* dx,
@@ -648,29 +688,29 @@ int l2q_bn_bwd(const void* dy, const void* x, const void* save_mean, const void*
 int l2q_col2im_periodic_f32(const float* dcol, long sn, long sc, long sh, long sw, int nb, int C,
                             int H, int W, int k, int channels_last_cols, float* dx,
                             void* stream) {
-  L2Q_REQUIRE(dcol && dx, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0, L2Q_EINVAL, "non-positive size");
-  const int Ho = H + k - 1, Wo = W + k - 1, Kc = C * k * k;
-  const long total = (long)nb * C * H * W;
-  L2Q_REQUIRE(cdiv(total, kBlock) < 0x7fffffffL, L2Q_ESHAPE, "grid too large");
-  hipLaunchKernelGGL(col2im_periodic_kernel, dim3(grid1(total)), dim3(kBlock), 0,
-                     (hipStream_t)stream, dcol, sn, sc, sh, sw, C, H, W, k, Ho, Wo, Kc, total,
-                     channels_last_cols ? 1 : 0, dx);
-  return check_launch("l2q_col2im_periodic_f32");
+  return col2im_periodic_launch<float>(dcol, sn, sc, sh, sw, nb, C, H, W, k, channels_last_cols, dx,
+                                       (hipStream_t)stream, "l2q_col2im_periodic_f32");
+}
+
+int l2q_col2im_periodic_f64(const double* dcol, long sn, long sc, long sh, long sw, int nb, int C,
+                            int H, int W, int k, int channels_last_cols, double* dx,
+                            void* stream) {
+  return col2im_periodic_launch<double>(dcol, sn, sc, sh, sw, nb, C, H, W, k, channels_last_cols, dx,
+                                        (hipStream_t)stream, "l2q_col2im_periodic_f64");
 }
 
 int l2q_maxpool_act_nhwc_bwd_f32(const float* dout, const float* out, const float* in, int nb,
                                  int H, int W, int C, int pool, int act, float* din,
                                  void* stream) {
-  L2Q_REQUIRE(dout && out && in && din, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
-  L2Q_REQUIRE(act != L2Q_ACT_SWISH, L2Q_EINVAL, "swish is not supported by the training path");
-  const int Ho = H / pool, Wo = W / pool;
-  L2Q_REQUIRE(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
-  const long total = (long)nb * H * W * C;
-  hipLaunchKernelGGL(maxpool_act_nhwc_bwd_kernel, dim3(grid1(total)), dim3(kBlock), 0,
-                     (hipStream_t)stream, dout, out, in, H, W, C, pool, act, Ho, Wo, total, din);
-  return check_launch("l2q_maxpool_act_nhwc_bwd_f32");
+  return maxpool_act_nhwc_bwd_launch<float>(dout, out, in, nb, H, W, C, pool, act, din,
+                                            (hipStream_t)stream, "l2q_maxpool_act_nhwc_bwd_f32");
+}
+
+int l2q_maxpool_act_nhwc_bwd_f64(const double* dout, const double* out, const double* in, int nb,
+                                 int H, int W, int C, int pool, int act, double* din,
+                                 void* stream) {
+  return maxpool_act_nhwc_bwd_launch<double>(dout, out, in, nb, H, W, C, pool, act, din,
+                                             (hipStream_t)stream, "l2q_maxpool_act_nhwc_bwd_f64");
 }
 
 int l2q_u1_force_bwd(const void* x, const void* dF, double beta, int nb, int T_, int X_,

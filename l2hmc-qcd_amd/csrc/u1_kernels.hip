@@ -6,6 +6,7 @@
 // no second pass) and 2048-8192 chains fill the 256 CUs.
 #include "l2q_common.hpp"
 #include "u1_math.hpp"
+#include <limits>
 
 namespace l2q {
 
@@ -255,10 +256,10 @@ __global__ __launch_bounds__(kBlock) void conv2d_periodic_kernel(
 // (ci, i, j) decomposition divides by the compile-time kernel size only.  (The first version
 // decomposed every element separately: ~10 runtime divisions per 4-byte store made this kernel
 // 62 % of the conv stack's time.)
-template <int KS>
+template <typename T, int KS>
 __global__ __launch_bounds__(kBlock) void im2col_periodic_kernel(
-    const float* __restrict__ in, long sn, long sc, long sh, long sw, int C, int H, int W, int kr,
-    int Ho, int Wo, int Kc, long Mrows, int clast, float* __restrict__ col) {
+    const T* __restrict__ in, long sn, long sc, long sh, long sw, int C, int H, int W, int kr,
+    int Ho, int Wo, int Kc, long Mrows, int clast, T* __restrict__ col) {
   const int k = KS > 0 ? KS : kr;
   const long m = (long)blockIdx.x * 4 + threadIdx.y;
   if (m >= Mrows) return;
@@ -266,8 +267,8 @@ __global__ __launch_bounds__(kBlock) void im2col_periodic_kernel(
   const long t = m / Wo;
   const int ho = (int)(t % Ho);
   const long b = t / Ho;
-  const float* inb = in + b * sn;
-  float* out = col + m * Kc;
+  const T* inb = in + b * sn;
+  T* out = col + m * Kc;
   // first source row / column of the window, reduced once into [0, H) / [0, W)
   int r0 = (ho - (k - 1)) % H; if (r0 < 0) r0 += H;
   int c0 = (wo - (k - 1)) % W; if (c0 < 0) c0 += W;
@@ -282,27 +283,28 @@ __global__ __launch_bounds__(kBlock) void im2col_periodic_kernel(
 }
 
 // NHWC max-pool (floor mode, stride = window) followed by the activation
-__global__ __launch_bounds__(kBlock) void nchw_to_nhwc_pad_kernel(const float* __restrict__ in, int C,
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nchw_to_nhwc_pad_kernel(const T* __restrict__ in, int C,
                                                                   long HW, int CP, long total,
-                                                                  float* __restrict__ out) {
+                                                                  T* __restrict__ out) {
   // out[b][hw][c] = c < C ? in[b][c][hw] : 0: the first conv layer's 2 / 4 lattice channels as
   // NHWC padded to a 16-byte group, so that it uses the vector gathers of the later layers
   const long idx = (long)blockIdx.x * kBlock + threadIdx.x;
   if (idx >= total) return;
   const long b = idx / HW, p = idx % HW;
-  const float* src = in + b * C * HW + p;
-  float* dst = out + idx * CP;
-  for (int c = 0; c < CP; ++c) dst[c] = c < C ? src[c * HW] : 0.f;
+  const T* src = in + b * C * HW + p;
+  T* dst = out + idx * CP;
+  for (int c = 0; c < CP; ++c) dst[c] = c < C ? src[c * HW] : (T)0;
 }
 
-// VEC channels per thread: 4 = one 16-byte access (C % 4 == 0), else 1
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_kernel(const float* __restrict__ in,
+// VEC channels per thread: one 16-byte access (4 floats / 2 doubles, C % VEC == 0), else 1
+template <typename T, int VEC>
+__global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_kernel(const T* __restrict__ in,
                                                                   int H, int W, int C, int pool,
                                                                   int act, int Ho, int Wo,
                                                                   long total,
-                                                                  float* __restrict__ out) {
-  typedef float fv __attribute__((ext_vector_type(VEC)));
+                                                                  T* __restrict__ out) {
+  typedef T fv __attribute__((ext_vector_type(VEC)));
   const long idx = (long)blockIdx.x * kBlock + threadIdx.x;      // over [b, ho, wo, C / VEC]
   if (idx >= total) return;
   const int cv = C / VEC;
@@ -312,17 +314,80 @@ __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_kernel(const float* _
   const long b = idx / ((long)cv * Wo * Ho);
   fv best;
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) best[e] = -3.402823466e38f;
+  for (int e = 0; e < VEC; ++e) best[e] = std::numeric_limits<T>::lowest();
   for (int ph = 0; ph < pool; ++ph)
     for (int pw = 0; pw < pool; ++pw) {
       const fv v = *reinterpret_cast<const fv*>(in + ((b * H + ho * pool + ph) * W + wo * pool + pw) * C + c);
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) best[e] = fmaxf(best[e], v[e]);
+      for (int e = 0; e < VEC; ++e) best[e] = fmax(best[e], v[e]);
     }
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) best[e] = act_f32(best[e], act);
+  for (int e = 0; e < VEC; ++e) best[e] = act_t(best[e], act);
   *reinterpret_cast<fv*>(out + ((b * Ho + ho) * Wo + wo) * (long)C + c) = best;
 }
+
+// ---- host side of the conv-stack helpers, fp32 / fp64 (entry point name `what` in errors)
+#define L2Q_REQUIRE_W(cond, code, msg)                          \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      ::l2q::set_error("%s: %s", what, msg);                    \
+      return code;                                              \
+    }                                                           \
+  } while (0)
+
+template <typename T>
+int nchw_to_nhwc_pad_launch(const T* in, int nb, int C, int H, int W, int cpad, T* out, hipStream_t st,
+                            const char* what) {
+  L2Q_REQUIRE_W(in && out, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, L2Q_EINVAL, "bad size");
+  const long HW = (long)H * W, total = (long)nb * HW;
+  hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<T>, dim3((unsigned)cdiv(total, kBlock)), dim3(kBlock), 0,
+                     st, in, C, HW, cpad, total, out);
+  return check_launch(what);
+}
+
+template <typename T>
+int im2col_periodic_launch(const T* in, long sn, long sc, long sh, long sw, int nb, int C, int H, int W,
+                           int k, int channels_last_cols, T* col, hipStream_t st, const char* what) {
+  L2Q_REQUIRE_W(in && col, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0, L2Q_EINVAL, "non-positive size");
+  const int Ho = H + k - 1, Wo = W + k - 1, Kc = C * k * k;
+  const long Mrows = (long)nb * Ho * Wo;
+  L2Q_REQUIRE_W(cdiv(Mrows, 4) < 0x7fffffffL, L2Q_ESHAPE, "grid too large");
+  const dim3 grid((unsigned)cdiv(Mrows, 4)), block(64, 4);
+#define L2Q_I2C(KS)                                                                                 \
+  hipLaunchKernelGGL((im2col_periodic_kernel<T, KS>), grid, block, 0, st, in, sn, sc, sh, sw, C, H, W, \
+                     k, Ho, Wo, Kc, Mrows, channels_last_cols ? 1 : 0, col)
+  switch (k) {
+    case 1: L2Q_I2C(1); break;
+    case 2: L2Q_I2C(2); break;
+    case 3: L2Q_I2C(3); break;
+    case 4: L2Q_I2C(4); break;
+    case 5: L2Q_I2C(5); break;
+    default: L2Q_I2C(0); break;
+  }
+#undef L2Q_I2C
+  return check_launch(what);
+}
+
+template <typename T>
+int maxpool_act_nhwc_launch(const T* in, int nb, int H, int W, int C, int pool, int act, T* out,
+                            hipStream_t st, const char* what) {
+  L2Q_REQUIRE_W(in && out, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
+  const int Ho = H / pool, Wo = W / pool;
+  L2Q_REQUIRE_W(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
+  constexpr int V = 16 / sizeof(T);
+  const bool vec = C % V == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const long total = (long)nb * Ho * Wo * (vec ? C / V : C);
+  const dim3 grid((unsigned)cdiv(total, kBlock)), block(kBlock);
+  if (vec) hipLaunchKernelGGL((maxpool_act_nhwc_kernel<T, V>), grid, block, 0, st, in, H, W, C, pool, act,
+                              Ho, Wo, total, out);
+  else hipLaunchKernelGGL((maxpool_act_nhwc_kernel<T, 1>), grid, block, 0, st, in, H, W, C, pool, act, Ho,
+                          Wo, total, out);
+  return check_launch(what);
+}
+#undef L2Q_REQUIRE_W
 
 }  // namespace l2q
 
@@ -447,53 +512,40 @@ int l2q_conv2d_periodic_f32(const float* in, const float* w, const float* bias, 
 
 int l2q_nchw_to_nhwc_pad_f32(const float* in, int nb, int C, int H, int W, int cpad, float* out,
                              void* stream) {
-  L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, L2Q_EINVAL, "bad size");
-  const long HW = (long)H * W, total = (long)nb * HW;
-  hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel, dim3((unsigned)cdiv(total, kBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, in, C, HW, cpad, total, out);
-  return check_launch("l2q_nchw_to_nhwc_pad_f32");
+  return nchw_to_nhwc_pad_launch<float>(in, nb, C, H, W, cpad, out, (hipStream_t)stream,
+                                        "l2q_nchw_to_nhwc_pad_f32");
+}
+
+int l2q_nchw_to_nhwc_pad_f64(const double* in, int nb, int C, int H, int W, int cpad, double* out,
+                             void* stream) {
+  return nchw_to_nhwc_pad_launch<double>(in, nb, C, H, W, cpad, out, (hipStream_t)stream,
+                                         "l2q_nchw_to_nhwc_pad_f64");
 }
 
 int l2q_im2col_periodic_f32(const float* in, long sn, long sc, long sh, long sw, int nb, int C,
                             int H, int W, int k, int channels_last_cols, float* col,
                             void* stream) {
-  L2Q_REQUIRE(in && col, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0, L2Q_EINVAL, "non-positive size");
-  const int Ho = H + k - 1, Wo = W + k - 1, Kc = C * k * k;
-  const long Mrows = (long)nb * Ho * Wo;
-  L2Q_REQUIRE(cdiv(Mrows, 4) < 0x7fffffffL, L2Q_ESHAPE, "grid too large");
-  const dim3 grid((unsigned)cdiv(Mrows, 4)), block(64, 4);
-  hipStream_t st = (hipStream_t)stream;
-#define L2Q_I2C(KS)                                                                              \
-  hipLaunchKernelGGL(im2col_periodic_kernel<KS>, grid, block, 0, st, in, sn, sc, sh, sw, C, H, W, \
-                     k, Ho, Wo, Kc, Mrows, channels_last_cols ? 1 : 0, col)
-  switch (k) {
-    case 1: L2Q_I2C(1); break;
-    case 2: L2Q_I2C(2); break;
-    case 3: L2Q_I2C(3); break;
-    case 4: L2Q_I2C(4); break;
-    case 5: L2Q_I2C(5); break;
-    default: L2Q_I2C(0); break;
-  }
-#undef L2Q_I2C
-  return check_launch("l2q_im2col_periodic_f32");
+  return im2col_periodic_launch<float>(in, sn, sc, sh, sw, nb, C, H, W, k, channels_last_cols, col,
+                                       (hipStream_t)stream, "l2q_im2col_periodic_f32");
+}
+
+int l2q_im2col_periodic_f64(const double* in, long sn, long sc, long sh, long sw, int nb, int C,
+                            int H, int W, int k, int channels_last_cols, double* col,
+                            void* stream) {
+  return im2col_periodic_launch<double>(in, sn, sc, sh, sw, nb, C, H, W, k, channels_last_cols, col,
+                                        (hipStream_t)stream, "l2q_im2col_periodic_f64");
 }
 
 int l2q_maxpool_act_nhwc_f32(const float* in, int nb, int H, int W, int C, int pool, int act,
                              float* out, void* stream) {
-  L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
-  const int Ho = H / pool, Wo = W / pool;
-  L2Q_REQUIRE(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
-  const bool vec = C % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-  const long total = (long)nb * Ho * Wo * (vec ? C / 4 : C);
-  const dim3 grid((unsigned)cdiv(total, kBlock)), block(kBlock);
-  if (vec) hipLaunchKernelGGL(maxpool_act_nhwc_kernel<4>, grid, block, 0, (hipStream_t)stream, in, H,
-                              W, C, pool, act, Ho, Wo, total, out);
-  else hipLaunchKernelGGL(maxpool_act_nhwc_kernel<1>, grid, block, 0, (hipStream_t)stream, in, H, W,
-                          C, pool, act, Ho, Wo, total, out);
-  return check_launch("l2q_maxpool_act_nhwc_f32");
+  return maxpool_act_nhwc_launch<float>(in, nb, H, W, C, pool, act, out, (hipStream_t)stream,
+                                        "l2q_maxpool_act_nhwc_f32");
+}
+
+int l2q_maxpool_act_nhwc_f64(const double* in, int nb, int H, int W, int C, int pool, int act,
+                             double* out, void* stream) {
+  return maxpool_act_nhwc_launch<double>(in, nb, H, W, C, pool, act, out, (hipStream_t)stream,
+                                         "l2q_maxpool_act_nhwc_f64");
 }
 
 }  // extern "C"

@@ -55,6 +55,21 @@ __device__ __forceinline__ float act_f32(float z, int act) {
   }
 }
 
+__device__ __forceinline__ double act_f64(double z, int act) {
+  switch (act) {
+    case L2Q_ACT_TANH: return ::tanh(z);
+    case L2Q_ACT_RELU: return ::fmax(z, 0.0);
+    case L2Q_ACT_LEAKY_RELU: return z > 0.0 ? z : 0.01 * z;
+    case L2Q_ACT_ELU: return z > 0.0 ? z : ::expm1(z);
+    case L2Q_ACT_SWISH: return z / (1.0 + ::exp(-z));
+    default: return z;
+  }
+}
+
+// act_f32 / act_f64 by element type (kernels templated on float / double)
+__device__ __forceinline__ float act_t(float z, int act) { return act_f32(z, act); }
+__device__ __forceinline__ double act_t(double z, int act) { return act_f64(z, act); }
+
 #define L2Q_DISPATCH_T(elem_bytes, CALL)                                  \
   if ((elem_bytes) == 4) { using T = float; CALL; }                       \
   else if ((elem_bytes) == 8) { using T = double; CALL; }                 \

@@ -843,13 +843,30 @@ def conv2d_periodic(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, pool: int
     return out
 
 
+_CONV_SUFFIX = {torch.float32: 'f32', torch.float64: 'f64'}
+
+
+def _conv_suffix(where: str, x: torch.Tensor, *others: Optional[torch.Tensor]) -> str:
+    """'f32' / 'f64': the conv kernels' entry point for x.dtype.  Every other operand must have
+    x's dtype (no silent casts); any other dtype is refused."""
+    sfx = _CONV_SUFFIX.get(x.dtype)
+    if sfx is None:
+        raise N.L2QError(f'{where}: the conv kernels take float32 or float64, got {x.dtype}')
+    for t in others:
+        if t is not None and t.dtype != x.dtype:
+            raise N.L2QError(f'{where}: dtype mismatch {t.dtype} vs input {x.dtype}')
+    return sfx
+
+
 def conv2d_periodic_gemm(x: torch.Tensor, layout: str, w: torch.Tensor, b: torch.Tensor,
                          pool: int = 1, act: Optional[str] = None,
                          w_clast: Optional[torch.Tensor] = None) -> torch.Tensor:
     """PeriodicPadding(k-1) -> Conv2d(k) -> [MaxPool2d(pool)] -> [act] as implicit GEMM on
-    the f32 MFMA kernel.  x: [nb, C, H, W] if layout == 'nchw' else [nb, H, W, C];
-    returns NHWC [nb, Ho, Wo, cout].  w_clast: the weight as [cout, k, k, C] (used for NHWC
-    inputs: contiguous gathers); made on the fly when not supplied."""
+    the f32 or f64 MFMA kernel (x.dtype; w, b, w_clast alike).  x: [nb, C, H, W] if
+    layout == 'nchw' else [nb, H, W, C]; returns NHWC [nb, Ho, Wo, cout].  w_clast: the weight
+    as [cout, k, k, C] (used for NHWC inputs: contiguous gathers); made on the fly when not
+    supplied."""
+    sfx = _conv_suffix('conv2d_periodic_gemm', x, w, b, w_clast)
     x = x.contiguous()
     if layout == 'nchw':
         nb, C, H, W = x.shape
@@ -861,27 +878,28 @@ def conv2d_periodic_gemm(x: torch.Tensor, layout: str, w: torch.Tensor, b: torch
     assert cin == C
     Ho, Wo, Kc = H + k - 1, W + k - 1, C * k * k
     pool = max(int(pool), 1)
-    y = torch.empty((nb * Ho * Wo, cout), dtype=torch.float32, device=x.device)
+    y = torch.empty((nb * Ho * Wo, cout), dtype=x.dtype, device=x.device)
     # im2col inside the GEMM's A-tile loader: no col matrix in HBM
     clast = layout != 'nchw'
     if clast:
         wk = (w.permute(0, 2, 3, 1) if w_clast is None else w_clast).reshape(cout, Kc).contiguous()
     else:
         wk = w.reshape(cout, Kc).contiguous()
-    N.call('l2q_conv_gemm_periodic_f32', x, sn, sc, sh, sw, nb, C, H, W, k, wk, int(clast),
+    N.call('l2q_conv_gemm_periodic_' + sfx, x, sn, sc, sh, sw, nb, C, H, W, k, wk, int(clast),
            b.contiguous(), cout, N.ACT[None if pool > 1 else act], y)
     if pool == 1:
         return y.reshape(nb, Ho, Wo, cout)
-    out = torch.empty((nb, Ho // pool, Wo // pool, cout), dtype=torch.float32, device=x.device)
-    N.call('l2q_maxpool_act_nhwc_f32', y, nb, Ho, Wo, cout, pool, N.ACT[act], out)
+    out = torch.empty((nb, Ho // pool, Wo // pool, cout), dtype=x.dtype, device=x.device)
+    N.call('l2q_maxpool_act_nhwc_' + sfx, y, nb, Ho, Wo, cout, pool, N.ACT[act], out)
     return out
 
 
 def nchw_to_nhwc_pad(x: torch.Tensor, cpad: int) -> torch.Tensor:
-    """fp32 [nb, C, H, W] -> fp32 [nb, H, W, cpad], channels zero-padded."""
+    """fp32 / fp64 [nb, C, H, W] -> [nb, H, W, cpad] of the same dtype, channels zero-padded."""
+    sfx = _conv_suffix('nchw_to_nhwc_pad', x)
     nb, C, H, W = x.shape
-    out = torch.empty((nb, H, W, cpad), dtype=torch.float32, device=x.device)
-    N.call('l2q_nchw_to_nhwc_pad_f32', x.contiguous(), nb, C, H, W, cpad, out)
+    out = torch.empty((nb, H, W, cpad), dtype=x.dtype, device=x.device)
+    N.call('l2q_nchw_to_nhwc_pad_' + sfx, x.contiguous(), nb, C, H, W, cpad, out)
     return out
 
 
@@ -1131,7 +1149,11 @@ def conv2d_periodic_gemm_train(x: torch.Tensor, layout: str, w: torch.Tensor, b:
     half = float16 | bfloat16: the layer as torch.autocast runs it in the reference's train step -- input,
     weight and bias rounded to that type, fp32 accumulation (products of 16-bit values are exact in fp32:
     the fp32 MFMA GEMM gives what the 16-bit one gives, to summation order), the convolution's output rounded,
-    the activation's output rounded; everything stays in fp32 containers for the backward pass."""
+    the activation's output rounded; everything stays in fp32 containers for the backward pass.
+    half = None: fp32 or fp64 by x.dtype (w, b alike)."""
+    sfx = _conv_suffix('conv2d_periodic_gemm_train', x, w, b)
+    if half is not None and x.dtype != torch.float32:
+        raise N.L2QError(f'conv2d_periodic_gemm_train: half={half} expects fp32 containers, got {x.dtype}')
     x = x.contiguous()
     if half is not None:
         r16 = lambda t: t.to(half).float()
@@ -1147,8 +1169,8 @@ def conv2d_periodic_gemm_train(x: torch.Tensor, layout: str, w: torch.Tensor, b:
     # NHWC input: K columns in (i, j, ci) order, so that im2col, the GEMM and col2im all move
     # contiguous runs of channels (col2im was 35 % of the conv training step in (ci, i, j) order)
     clast = layout != 'nchw'
-    col = torch.empty((nb * Ho * Wo, Kc), dtype=torch.float32, device=x.device)
-    N.call('l2q_im2col_periodic_f32', x, *strides, nb, C, H, W, k, int(clast), col)
+    col = torch.empty((nb * Ho * Wo, Kc), dtype=x.dtype, device=x.device)
+    N.call('l2q_im2col_periodic_' + sfx, x, *strides, nb, C, H, W, k, int(clast), col)
     pool = max(int(pool), 1)
     wk = (w.permute(0, 2, 3, 1) if clast else w).reshape(cout, Kc).contiguous()
     if half is not None and pool == 1 and act is not None:
@@ -1163,8 +1185,8 @@ def conv2d_periodic_gemm_train(x: torch.Tensor, layout: str, w: torch.Tensor, b:
     if pool == 1:
         out = y.reshape(nb, Ho, Wo, cout)
     else:
-        out = torch.empty((nb, Ho // pool, Wo // pool, cout), dtype=torch.float32, device=x.device)
-        N.call('l2q_maxpool_act_nhwc_f32', y, nb, Ho, Wo, cout, pool, N.ACT[act], out)
+        out = torch.empty((nb, Ho // pool, Wo // pool, cout), dtype=x.dtype, device=x.device)
+        N.call('l2q_maxpool_act_nhwc_' + sfx, y, nb, Ho, Wo, cout, pool, N.ACT[act], out)
         if half is not None:
             out = out.to(half).float()
     ctx['out'] = out
@@ -1180,10 +1202,11 @@ def conv2d_periodic_gemm_bwd(ctx: dict, dout: torch.Tensor, w: torch.Tensor, dw:
     if act == 'swish':
         # the fused conv kernels keep the activation OUTPUT only; swish' needs the pre-activation
         raise NotImplementedError('conv backward with swish: the conv tape holds post-activations')
+    sfx = _conv_suffix('conv2d_periodic_gemm_bwd', dout, ctx['y'], w, dw, db)
     dout = dout.contiguous()
     if pool > 1:
         dy = torch.empty_like(ctx['y'])
-        N.call('l2q_maxpool_act_nhwc_bwd_f32', dout, ctx['out'], ctx['y'], nb, Ho, Wo, cout, pool,
+        N.call('l2q_maxpool_act_nhwc_bwd_' + sfx, dout, ctx['out'], ctx['y'], nb, Ho, Wo, cout, pool,
                N.ACT[act], dy)
     else:
         dy = act_bwd(dout.reshape(nb * Ho * Wo, cout).clone(), ctx['y'], act)
@@ -1200,8 +1223,8 @@ def conv2d_periodic_gemm_bwd(ctx: dict, dout: torch.Tensor, w: torch.Tensor, dw:
     dcol = gemm(dy, t2d(ctx['wk'] if 'wk' in ctx else w.reshape(cout, Kc)))    # [M, Kc]
     sn, sc, sh, sw = ctx['strides']
     shape = (nb, C, H, W) if sw == 1 else (nb, H, W, C)
-    dx = torch.empty(shape, dtype=torch.float32, device=dout.device)
-    N.call('l2q_col2im_periodic_f32', dcol, sn, sc, sh, sw, nb, C, H, W, k, int(clast), dx)
+    dx = torch.empty(shape, dtype=dout.dtype, device=dout.device)
+    N.call('l2q_col2im_periodic_' + sfx, dcol, sn, sc, sh, sw, nb, C, H, W, k, int(clast), dx)
     return dx
 
 

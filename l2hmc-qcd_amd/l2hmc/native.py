@@ -106,6 +106,10 @@ SIGNATURES = {
     'l2q_maxpool_act_nhwc_f32': (I, [P, I, I, I, I, I, I, P, P]),
     'l2q_conv_gemm_periodic_f32': (I, [P, L, L, L, L, I, I, I, I, I, P, I, P, I, I, P, P]),
     'l2q_nchw_to_nhwc_pad_f32': (I, [P, I, I, I, I, I, P, P]),
+    'l2q_im2col_periodic_f64': (I, [P, L, L, L, L, I, I, I, I, I, I, P, P]),
+    'l2q_maxpool_act_nhwc_f64': (I, [P, I, I, I, I, I, I, P, P]),
+    'l2q_conv_gemm_periodic_f64': (I, [P, L, L, L, L, I, I, I, I, I, P, I, P, I, I, P, P]),
+    'l2q_nchw_to_nhwc_pad_f64': (I, [P, I, I, I, I, I, P, P]),
     'l2q_u1_fused_max_n': (I, []),
     'l2q_u1_vstep_f32': (I, [P, P, D, D, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, D, P, P, P, I, I, P, P]),
     'l2q_u1_xstep_f32': (I, [P, P, P, I, D, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, D, P, P, P, I, I, P, P]),
@@ -121,6 +125,8 @@ SIGNATURES = {
     'l2q_bn_bwd': (I, [P, P, P, P, P, I, I, I, P, P, P, P]),
     'l2q_col2im_periodic_f32': (I, [P, L, L, L, L, I, I, I, I, I, I, P, P]),
     'l2q_maxpool_act_nhwc_bwd_f32': (I, [P, P, P, I, I, I, I, I, I, P, P]),
+    'l2q_col2im_periodic_f64': (I, [P, L, L, L, L, I, I, I, I, I, I, P, P]),
+    'l2q_maxpool_act_nhwc_bwd_f64': (I, [P, P, P, I, I, I, I, I, I, P, P]),
     'l2q_u1_force_bwd': (I, [P, P, D, I, I, I, I, P, P]),
     'l2q_u1_plaq_bwd': (I, [P, P, P, I, I, I, I, P, P]),
     'l2q_u1_x_update_bwd': (I, [P, P, P, P, P, P, I, D, I, I, P, P, I, I, L, P, P, P, P, P, P, P]),

@@ -277,13 +277,14 @@ class ConvStack(nn.Module):
         """conv weight as [cout, k, k, cin] (K columns of the implicit GEMM in the order in which
         an NHWC activation is contiguous), cached per weight version."""
         conv = self.layers[ci]
-        ver = (conv.weight._version, ops.PARAM_GENERATION[0])
+        ver = (conv.weight._version, ops.PARAM_GENERATION[0], conv.weight.dtype)
         hit = self._wcache.get(ci)
         if hit is None or hit[0] != ver:
             w = conv.weight.detach().permute(0, 2, 3, 1)
-            if ci == self.plan[0][0] and w.shape[-1] % 4:     # first layer: lattice channels
+            vec = 16 // w.element_size()                       # channels per 16-byte group: 4 fp32, 2 fp64
+            if ci == self.plan[0][0] and w.shape[-1] % vec:   # first layer: lattice channels
                 # padded to a 16-byte group (its input is padded alike in forward)
-                w = torch.nn.functional.pad(w, (0, 4 - w.shape[-1] % 4))
+                w = torch.nn.functional.pad(w, (0, vec - w.shape[-1] % vec))
             hit = (ver, w.contiguous())
             self._wcache[ci] = hit
         return hit[1]
@@ -336,13 +337,15 @@ class ConvStack(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         x = x.to(DEVICE)
         x = x.reshape(x.shape[0], self.in_channels, self.nt, self.nx).contiguous()
-        if x.dtype != torch.float32:
-            raise NotImplementedError('the conv kernels are fp32 (the U(1) configs)')
         if getattr(self, 'half_dtype', None) is not None:
+            if x.dtype != torch.float32:
+                raise NotImplementedError('the half-precision conv stack takes fp32 input')
             return self._forward_half(x, self.half_dtype)
-        # implicit GEMM: periodic im2col -> f32 MFMA GEMM (NHWC activations) -> pool + act
+        if x.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError(f'the conv kernels are fp32 / fp64, got {x.dtype}')
+        # implicit GEMM: periodic im2col -> f32 / f64 MFMA GEMM (NHWC activations) -> pool + act
         layout = 'nchw'
-        if self.plan:                 # NHWC from the start (channels padded to 4): vector gathers
+        if self.plan:                 # NHWC from the start (channels padded to a 16-byte group): vector gathers
             x = ops.nchw_to_nhwc_pad(x, self._clast_weight(self.plan[0][0]).shape[-1])
             layout = 'nhwc'
         for ci, k, pool, act in self.plan:
@@ -365,8 +368,9 @@ class ConvStack(nn.Module):
         x = x.to(DEVICE)
         nb = x.shape[0]
         x = x.reshape(nb, self.in_channels, self.nt, self.nx).contiguous()
-        if x.dtype != torch.float32:
-            raise NotImplementedError('the conv kernels are fp32 (the U(1) configs)')
+        if x.dtype not in ((torch.float32,) if half is not None else (torch.float32, torch.float64)):
+            raise NotImplementedError(f'the conv training kernels are fp32 / fp64 (fp32 containers '
+                                      f'under half precision), got {x.dtype}')
         layout, ctxs = 'nchw', []
         for ci, k, pool, act in self.plan:
             conv = self.layers[ci]

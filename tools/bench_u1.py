@@ -19,12 +19,16 @@ ap.add_argument('--conv', action='store_true')
 ap.add_argument('--steps', type=int, default=5)
 ap.add_argument('--ch', type=int, default=0, help='chains per workgroup of the fused U(1) kernels (0: auto)')
 ap.add_argument('--unfused', action='store_true', help='multi-kernel sub-updates instead of the fused U(1) kernels')
-ap.add_argument('--precision', default=None, help="'fp16' | 'bf16': half-precision Linear layers (cfg-3)")
+ap.add_argument('--precision', default=None, help="'fp16' | 'bf16': half-precision Linear layers (cfg-3); "
+                "'float64': float64 default dtype for the lattice and the networks (precision=float64)")
 ap.add_argument('--units', type=int, nargs='+', default=[16, 16, 16, 16])
 ap.add_argument('--no-hmc', action='store_true')
 ap.add_argument('--no-graph', action='store_true')
 ap.add_argument('--tune', nargs=2, action='append', default=[], metavar=('KEY', 'VALUE'))
 a = ap.parse_args()
+f64 = a.precision in ('float64', 'fp64')
+if f64:                     # before the lattice and the networks are built (the reference's entry order)
+    torch.set_default_dtype(torch.float64)
 torch.manual_seed(9992); np.random.seed(9992)
 dc = cfgs.DynamicsConfig(nchains=a.nb, group='U1', latvolume=a.L, nleapfrog=a.nlf, eps=0.1,
                          eps_hmc=0.1, verbose=False)
@@ -37,7 +41,7 @@ spec = cfgs.InputSpec(xshape=tuple(dc.xshape), xnet={'x': [dc.xdim, 2], 'v': [dc
 lat = LatticeU1(a.nb, a.L)
 dyn = Dynamics(lat.action, dc, NetworkFactory(spec, nc, cc)).eval()
 dyn.fuse_u1_steps = not a.unfused
-dyn.set_net_precision(a.precision)
+dyn.set_net_precision(None if f64 else a.precision)
 from l2hmc import native  # noqa: E402
 native.set_tuning('u1_fused_ch', a.ch)
 for k_, v_ in a.tune:
