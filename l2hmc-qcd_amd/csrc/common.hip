@@ -223,21 +223,15 @@ int l2q_set_tuning(const char* key, int value) {
   Tuning& t = tuning();
   int* slot = nullptr;
   bool ok = false;
-  if (!strcmp(key, "plaq_occ")) { slot = &t.plaq_occ; ok = value >= 2 && value <= 4; }
-  else if (!strcmp(key, "force_occ")) { slot = &t.force_occ; ok = value >= 2 && value <= 4; }
-  else if (!strcmp(key, "xcd_swizzle")) { slot = &t.xcd_swizzle; ok = value == 0 || value == 1; }
-  else if (!strcmp(key, "plaq_sweep")) { slot = &t.plaq_sweep; ok = value >= 0 && value <= 3; }
-  else if (!strcmp(key, "force_tile")) { slot = &t.force_tile; ok = value >= 0 && value <= 7; }
-  else if (!strcmp(key, "gemm_h_wide_fused")) { slot = &t.gemm_h_wide_fused; ok = value == 0 || value == 1; }
-  else if (!strcmp(key, "conv_stream")) { slot = &t.conv_stream; ok = value == 0 || value == 1; }
+  if (!strcmp(key, "xcd_swizzle")) { slot = &t.xcd_swizzle; ok = value == 0 || value == 1; }
+  else if (!strcmp(key, "force_tile")) { slot = &t.force_tile; ok = value == 2 || value == 5 || value == 7; }
   else if (!strcmp(key, "conv_patch")) { slot = &t.conv_patch; ok = value >= 0 && value <= 2; }
   else if (!strcmp(key, "gemm_h_dma")) { slot = &t.gemm_h_dma; ok = value == 0 || value == 1; }
   else if (!strcmp(key, "gemm_h_lt")) { slot = &t.gemm_h_lt; ok = value == 0 || value == 1; }
   else if (!strcmp(key, "gemm_h_skinny")) { slot = &t.gemm_h_skinny; ok = value == 0 || value == 1 || value == 2 || value == 4 || value == 8; }
   else if (!strcmp(key, "gemm_h_small")) { slot = &t.gemm_h_small; ok = value == 0 || value == 1; }
   else if (!strcmp(key, "gemm_h_patch")) { slot = &t.gemm_h_patch; ok = value == 0 || value == 1; }
-  else if (!strcmp(key, "heads_h_bm")) { slot = &t.heads_h_bm; ok = value == 64 || value == 128; }
-  else if (!strcmp(key, "heads_h_stream")) { slot = &t.heads_h_stream; ok = value >= 0 && value <= 3; }
+  else if (!strcmp(key, "heads_h_stream")) { slot = &t.heads_h_stream; ok = value == 0 || value == 2 || value == 3; }
   else if (!strcmp(key, "heads_h_order")) { slot = &t.heads_h_order; ok = value == 0 || value == 1; }
   else if (!strcmp(key, "u1_fused_ch")) { slot = &t.u1_fused_ch; ok = value == 0 || value == 1 || value == 2 || value == 4 || value == 8; }
   else if (!strcmp(key, "heads_dma")) { slot = &t.heads_dma; ok = value == 0 || value == 1; }

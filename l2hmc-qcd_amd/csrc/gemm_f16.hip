@@ -334,10 +334,6 @@ static int pick_splits_h(int M, int N, long Kt) {
 // wide: the 128 x 256 tile (512 threads, one workgroup per CU), always through split-K partials.
 static int pick_config_h(int M, int N, long Kt, bool* wide) {
   *wide = N > 128 && Kt >= 32 * HBK && cdiv(M, 128) * cdiv(N, 128) < 256;
-  if (!*wide && tuning().gemm_h_wide_fused && N >= 1024 && M >= 1024 && Kt >= 16 * HBK) {
-    *wide = true;                  // large square-ish layer: 128 x 256 tiles, epilogue in-kernel
-    return 1;
-  }
   if (!*wide) return pick_splits_h(M, N, Kt);
   const long tiles = cdiv(M, 128) * cdiv(N, 256);
   long s = cdiv(256, tiles);
@@ -383,9 +379,8 @@ static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, c
   const int veca = K % VA == 0 && K2 % VA == 0 && al16(A) && al16(A2);
   const int vecw = K % 8 == 0 && K2 % 8 == 0 && al16(W) && al16(W2);
   const int patch = tuning().gemm_h_patch;
-  const bool wide_fused = wide && splits == 1 && (long)M * N >= 1024L * 1024L;
   float* part = nullptr;
-  if (splits > 1 || (wide && !wide_fused)) {
+  if (splits > 1 || wide) {
     const size_t need = (size_t)splits * M * N * sizeof(float);
     if (!ws || ws_bytes < need) {
       set_error("l2q_gemm_h: split-K workspace too small (%zu < %zu)", ws_bytes, need);
@@ -393,11 +388,7 @@ static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, c
     }
     part = (float*)ws;
   }
-  if (wide_fused) {
-    const dim3 grid((unsigned)(cdiv(N, 256) * cdiv(M, 128)));
-    hipLaunchKernelGGL((gemm_nt_h_kernel<HT, AS, CT, true, 512>), grid, dim3(512), 0, st, A, W, A2,
-                       W2, M, N, K, K2, kchunk, splits, epi, veca, vecw, C, part, patch, cs_mask, cs_compl);
-  } else if (wide) {
+  if (wide) {
     const dim3 grid((unsigned)(cdiv(N, 256) * cdiv(M, 128) * splits));
     hipLaunchKernelGGL((gemm_nt_h_kernel<HT, AS, CT, false, 512>), grid, dim3(512), 0, st, A, W, A2,
                        W2, M, N, K, K2, kchunk, splits, epi, veca, vecw, C, part, patch, cs_mask, cs_compl);
@@ -410,7 +401,7 @@ static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, c
     hipLaunchKernelGGL((gemm_nt_h_kernel<HT, AS, CT, false, 256>), grid, dim3(kBlock), 0, st, A, W,
                        A2, W2, M, N, K, K2, kchunk, splits, epi, veca, vecw, C, part, patch, cs_mask, cs_compl);
   }
-  if (splits > 1 || (wide && !wide_fused)) {
+  if (splits > 1 || wide) {
     launch_splitk_reduce_h<HT, CT>((const float*)part, splits, (long)M * N, N, epi, C, st);
   }
   return check_launch("l2q_gemm_h");
@@ -667,237 +658,6 @@ __global__ __launch_bounds__(kBlock, BM == 128 ? 2 : 3) void u1_heads_update_h_k
     if (lane < 16 && m < a.M) {
       const long col = (n0 / BN) * 2 + (wave & 1);
       a.logdet_part[m * a.ncols_part + col] = x;
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------
-// The same operation as u1_heads_update_h_kernel, organised as a STREAM over the chains with the
-// weights stationary (round 3).  Same-box decomposition of the tile kernel at cfg-3 (8192 chains x
-// 8192 entries, K = 256; tools/probe_heads_h3.py on -DL2Q_HH_SKIP builds): whole kernel 0.41 ms =
-// staging + MFMA 0.20 ms (every 128 x 64 tile stages 160 KB of Z and W through registers into LDS in
-// four dependent round trips) + field traffic 0.16-0.25 ms (805 MB) + epilogue arithmetic 0.06-0.09 ms,
-// and the first two do not overlap.  Here
-//  * a workgroup owns 64 entries (columns) and a range of chains; each of its four wavefronts keeps the
-//    three heads' weights of ITS 16 columns in registers for the whole sweep (3 x K / 32 MFMA operand
-//    fragments = 96 VGPRs at K = 256; W is read once per workgroup) together with the per-column
-//    biases / scales / mask;
-//  * the chains stream by in steps of 32 rows: their Z rows (32 x K 16-bit = 16 KB, four 16-byte chunks
-//    per thread) and the fp32 field operands (a, b) of the NEXT step are requested while the current
-//    step's epilogue runs; Z goes registers -> LDS (two stages, one barrier per step, chunk-swizzled so
-//    that the ds_read_b128 fragments are conflict-free).  (An LDS-DMA version was written first: hipcc
-//    cannot tell its vmcnt traffic from the operand prefetches and drains vmcnt to 0 around every
-//    global_load_lds, which serialises the step; plain loads keep its scoreboard exact.)
-//  * per step a wavefront issues 6 K / 32 MFMAs (32 rows x its 16 columns x 3 heads), runs the shared
-//    hh_element arithmetic on 2 x 4 entries per lane and stores two float4.
-// Same MFMA instruction, operand roles and k order as the tile kernel: identical accumulators; the fp32
-// epilogue is contracted differently by hipcc in the two kernels (rare 1-ulp16 flips of a head); the
-// per-chain log-det is summed in a different (fixed) order.
-// Needs K in {32, 64, 128, 256}, N % 4 == 0 and 16-byte aligned operands (heads_h_launch falls back).
-// MEASURED (cfg-3, same box, four rotating operand sets): 0.475 ms (v) / 0.56 ms (x) against the tile
-// kernel's 0.420 / 0.48 ms -- with one step of prefetch the operand latency of every 32-row step is still
-// exposed (hipcc waits vmcnt(0) at the top of a step; a second prefetch stage does not fit the 256
-// registers next to the 96 of the stationary weights).  Kept as tuning `heads_h_stream = 1`, off by default.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <typename HT, bool XUPD, bool FWD, bool NCP>
-__global__ __launch_bounds__(kBlock, 2) void u1_heads_stream_h_kernel(HeadsHArgs a, int swz, int rows_per_wg) {
-  constexpr int KS_MAX = 8;                       // K <= 256
-  constexpr int ROWS = 32;                        // chains per step
-  constexpr int STAGE = ROWS * 512;               // bytes (K = 256); smaller K uses a prefix
-  using vec_t = typename MfmaH<HT>::vec_t;
-  __shared__ __attribute__((aligned(1024))) char zs[2 * STAGE];
-  __shared__ float red[2][4][ROWS];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int K = a.K;
-  const int ksteps = K >> 5;                      // MFMA k-steps of 32
-  const int cpr = K >> 3;                         // 16-byte chunks per Z row
-  const int rowb = K * 2;                         // bytes per Z row
-  const int swm = (cpr < 16 ? cpr : 16) - 1;      // chunk swizzle mask
-  const long ntiles = (a.N + 63) / 64;
-  const long w = xcd_swizzle(blockIdx.x, gridDim.x, swz);
-  const long n0 = (w % ntiles) * 64;              // n-tiles fastest: neighbours walk the same rows
-  const long mbeg = (w / ntiles) * rows_per_wg;
-  long mend = mbeg + rows_per_wg;
-  if (mend > a.M) mend = a.M;
-  if (mbeg >= a.M) return;
-  const int nstep = (int)((mend - mbeg + ROWS - 1) / ROWS);
-
-  // ---- stationary operands of this wavefront: columns nw0 .. nw0 + 15
-  const long nw0 = n0 + 16 * wave;
-  const long ncol = nw0 + (lane & 15);            // W row this lane's fragments come from
-  const long nrow = ncol < a.N ? ncol : a.N - 1;
-  vec_t wf[3][KS_MAX];
-#pragma unroll
-  for (int h = 0; h < 3; ++h) {
-    const HT* W = (const HT*)a.W[h] + nrow * (long)K + 8 * (lane >> 4);
-#pragma unroll
-    for (int kk = 0; kk < KS_MAX; ++kk) {
-      // unconditional (k-steps past K re-read the last one and are never used): a load behind a branch
-      // makes hipcc guard every later use with s_waitcnt vmcnt(0), which would drain the prefetches
-      const int ko = kk < ksteps ? 32 * kk : K - 32;
-      wf[h][kk] = *reinterpret_cast<const vec_t*>(W + ko);
-    }
-  }
-  const long nb4 = nw0 + 4 * (lane >> 4);         // this lane's four consecutive entries
-  const bool ncok = nb4 < a.N;                    // (N % 4 == 0: all four or none)
-  const long nq = ncok ? nb4 : 0;
-  float bs[4], bt[4], bq[4], cs[4], cq[4], keep[4];
-  {
-    const float4 v0 = *reinterpret_cast<const float4*>(a.b[0] + nq);
-    const float4 v1 = *reinterpret_cast<const float4*>(a.b[1] + nq);
-    const float4 v2 = *reinterpret_cast<const float4*>(a.b[2] + nq);
-    const float4 v3 = *reinterpret_cast<const float4*>(a.cs + nq);
-    const float4 v4 = *reinterpret_cast<const float4*>(a.cq + nq);
-    bs[0] = v0.x; bs[1] = v0.y; bs[2] = v0.z; bs[3] = v0.w;
-    bt[0] = v1.x; bt[1] = v1.y; bt[2] = v1.z; bt[3] = v1.w;
-    bq[0] = v2.x; bq[1] = v2.y; bq[2] = v2.z; bq[3] = v2.w;
-    cs[0] = v3.x; cs[1] = v3.y; cs[2] = v3.z; cs[3] = v3.w;
-    cq[0] = v4.x; cq[1] = v4.y; cq[2] = v4.z; cq[3] = v4.w;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) keep[r] = 0.f;
-    if (XUPD) {
-      const float4 v5 = *reinterpret_cast<const float4*>(a.mask + nq);
-      keep[0] = v5.x; keep[1] = v5.y; keep[2] = v5.z; keep[3] = v5.w;
-      if (a.complement) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) keep[r] = 1.f - keep[r];
-      }
-    }
-  }
-
-  // ---- Z stream: a step's 32 rows are 32 * cpr 16-byte chunks; thread t carries chunks t, t + 256, ...
-  // (at most four) in registers for one step and writes them to the stage when their turn comes.
-  // Chunk c of row r sits at slot c ^ (r & swm) of its row: the ds_read_b128 fragments below (16 rows, one
-  // chunk index) then touch 16 different bank groups.
-  const int nchunk = ROWS * cpr;                  // 1024 (K = 256) .. 128 (K = 32)
-  const char* zbase = reinterpret_cast<const char*>(a.Z);
-  uint4 zr[4];
-  auto zfetch = [&](long r0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      int p = tid + 256 * q;
-      if (p >= nchunk) p = nchunk - 1;            // unconditional loads (a load behind a branch is waited for
-                                                  // on the spot); the surplus copies are never stored
-      const int row = p / cpr, c = p - row * cpr;
-      long m = r0 + row;
-      if (m >= a.M) m = a.M - 1;                  // rows past the end re-read a valid one (masked later)
-      zr[q] = *reinterpret_cast<const uint4*>(zbase + m * (long)rowb + (c << 4));
-    }
-  };
-  auto zstore = [&](int st) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p = tid + 256 * q;
-      if (p < nchunk) {
-        const int row = p / cpr, c = p - row * cpr;
-        *reinterpret_cast<uint4*>(zs + st * STAGE + row * rowb + ((c ^ (row & swm)) << 4)) = zr[q];
-      }
-    }
-  };
-  // fragment read offsets of this lane: row (lane & 15) [+ 16 i], chunk 4 kk + (lane >> 4)
-  const int frow = lane & 15;
-  const int fsw = frow & swm;                     // (row + 16 i) & swm == row & swm (swm <= 15)
-
-  // ---- field operands: lane holds chain 16 i + (lane & 15) of the step and entries nb4 .. nb4 + 3
-  float* __restrict__ pa = a.a;
-  const float* __restrict__ pb = a.bsrc;
-  float4 av[2][2], bv[2][2];                      // [slot][i]
-  auto fetch = [&](int slot, long r0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long m = r0 + 16 * i + (lane & 15);
-      const bool ok = ncok && m < mend;
-      const long o = ok ? m * (long)a.N + nb4 : 0;
-      av[slot][i] = *reinterpret_cast<const float4*>(pa + o);
-      bv[slot][i] = *reinterpret_cast<const float4*>(pb + o);
-    }
-  };
-  const float eps = a.eps;
-  zfetch(mbeg);
-  fetch(0, mbeg);
-  auto step = [&](auto CUR, int s) {
-    constexpr int cur = decltype(CUR)::value;      // stage / operand slot of this step (compile time)
-    const long r0 = mbeg + (long)s * ROWS;
-    zstore(cur);                                   // stage `cur` was last read two steps ago
-    __syncthreads();
-    // previous step's row sums of the log-det: the four wavefronts' partials meet here
-    if (s > 0 && tid < ROWS) {
-      const long m = r0 - ROWS + tid;
-      if (m < mend) {
-        const int pr = (s - 1) & 1;
-        const double x = ((double)red[pr][0][tid] + (double)red[pr][1][tid]) +
-                         ((double)red[pr][2][tid] + (double)red[pr][3][tid]);
-        a.logdet_part[m * a.ncols_part + (n0 >> 6)] = x;
-      }
-    }
-    v4f32 acc[3][2];
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[h][i] = (v4f32){0, 0, 0, 0};
-    const char* sb = zs + cur * STAGE;
-#pragma unroll
-    for (int kk = 0; kk < KS_MAX; ++kk) {
-      if (kk < ksteps) {
-        vec_t fa[2];
-        const int chunk = (4 * kk + (lane >> 4)) ^ fsw;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          fa[i] = *reinterpret_cast<const vec_t*>(sb + (frow + 16 * i) * rowb + (chunk << 4));
-#pragma unroll
-        for (int h = 0; h < 3; ++h)
-#pragma unroll
-          for (int i = 0; i < 2; ++i) acc[h][i] = MfmaH<HT>::run(wf[h][kk], fa[i], acc[h][i]);
-      }
-    }
-    // next step's operands (Z rows into registers, field values into the other slot): in flight during
-    // this step's epilogue, consumed one step later
-    if (s + 1 < nstep) {
-      zfetch(r0 + ROWS);
-      fetch(cur ^ 1, r0 + ROWS);
-    }
-    float ld[2] = {0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long m = r0 + 16 * i + (lane & 15);
-      const bool ok = ncok && m < mend;
-      const float4 ta = av[cur][i];
-      const float4 tb = bv[cur][i];
-      const float a4[4] = {ta.x, ta.y, ta.z, ta.w}, b4[4] = {tb.x, tb.y, tb.z, tb.w};
-      float out[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float ldt;
-        out[r] = hh_element<HT, XUPD, FWD, NCP>(acc[0][i][r], acc[1][i][r], acc[2][i][r], bs[r], bt[r], bq[r],
-                                                cs[r], cq[r], a.st, eps, a4[r], b4[r], keep[r], ldt);
-        if (ok) ld[i] += ldt;
-      }
-      if (ok) *reinterpret_cast<float4*>(pa + m * (long)a.N + nb4) = make_float4(out[0], out[1], out[2], out[3]);
-    }
-    // row sums over this wavefront's 16 columns (four lane groups of 4 entries)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float x = ld[i];
-      x += __shfl_xor(x, 16, 64);
-      x += __shfl_xor(x, 32, 64);
-      if (lane < 16) red[cur][wave][16 * i + lane] = x;
-    }
-  };
-  for (int s = 0; s < nstep; s += 2) {
-    step(std::integral_constant<int, 0>{}, s);
-    if (s + 1 < nstep) step(std::integral_constant<int, 1>{}, s + 1);
-  }
-  __syncthreads();
-  if (tid < ROWS) {
-    const long m = mbeg + (long)(nstep - 1) * ROWS + tid;
-    if (m < mend) {
-      const int pr = (nstep - 1) & 1;
-      const double x = ((double)red[pr][0][tid] + (double)red[pr][1][tid]) +
-                       ((double)red[pr][2][tid] + (double)red[pr][3][tid]);
-      a.logdet_part[m * a.ncols_part + (n0 >> 6)] = x;
     }
   }
 }
@@ -1179,11 +939,6 @@ template <typename HT>
 bool conv_patch_launch(const void* in, const ConvGeomH& g, const void* w, const float* bias,
                        int cout, int act, void* out, hipStream_t st);
 
-// conv_stream_f16.hip: persistent whole-K kernel when the layer fits it; false -> the gather kernel here
-template <typename HT>
-bool conv_stream_launch(const void* in, const ConvGeomH& g, const void* w, const float* bias, int cout,
-                        int act, void* out, hipStream_t st);
-
 template <typename HT, typename IT>
 static int conv_h_launch(const void* in_, ConvGeomH g, const void* w_, const float* bias, int cout,
                          int act, void* out_, hipStream_t st) {
@@ -1197,9 +952,6 @@ static int conv_h_launch(const void* in_, ConvGeomH g, const void* w_, const flo
                     g.sh % 8 == 0 && g.sn % 8 == 0 && al16(in);
   if (g.pool != 2 && vec8 && tuning().conv_patch &&
       conv_patch_launch<HT>(in_, g, w_, bias, cout, act, out_, st))
-    return check_launch("l2q_conv_gemm_periodic_h");
-  if (vec8 && tuning().conv_stream && cout > (g.pool == 2 ? 0 : 16) &&
-      conv_stream_launch<HT>(in_, g, w_, bias, cout, act, out_, st))
     return check_launch("l2q_conv_gemm_periodic_h");
 #define L2Q_CHB(KS, BNV)                                                                         \
   do {                                                                                           \
@@ -1247,8 +999,7 @@ bool heads_h_kstream_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, in
 template <typename HT>
 static int heads_h_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, float* logdet,
                           int accumulate, void* ws, hipStream_t st) {
-  const int bm = tuning().heads_h_bm;
-  const long ntile = cdiv(a.N, 64), mtile = cdiv(a.M, bm);
+  const long ntile = cdiv(a.N, 64), mtile = cdiv(a.M, 128);
   const dim3 grid((unsigned)(ntile * mtile)), block(kBlock);
   const int swz = tuning().xcd_swizzle;
   const int nfast = tuning().heads_h_order;
@@ -1261,40 +1012,9 @@ static int heads_h_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, floa
       heads_h_kstream_launch<HT>(a, xupd, forward, use_ncp, swz, logdet, accumulate, st, tuning().heads_h_stream == 3))
     return check_launch("l2q_u1_heads_update_h");
   launch_zero(part, (size_t)a.M * a.ncols_part * sizeof(double), st);
-  // weights-stationary stream kernel wherever its shape conditions hold (tuning heads_h_stream = 0: tile kernel)
-  const bool stream = tuning().heads_h_stream == 1 && (a.K == 32 || a.K == 64 || a.K == 128 || a.K == 256) &&
-                      (a.N & 3) == 0 && al16(a.a) && al16(a.bsrc) && al16(a.b[0]) && al16(a.b[1]) &&
-                      al16(a.b[2]) && al16(a.cs) && al16(a.cq) && (!xupd || al16(a.mask)) && al16(a.Z) &&
-                      al16(a.W[0]) && al16(a.W[1]) && al16(a.W[2]);
-  if (stream) {
-    const long nt = cdiv(a.N, 64);
-    long msplit = cdiv(768, nt);
-    const long maxsplit = cdiv(a.M, 32);
-    if (msplit > maxsplit) msplit = maxsplit;
-    if (msplit < 1) msplit = 1;
-    const int rows_per_wg = (int)(cdiv(cdiv(a.M, msplit), 32) * 32);
-    msplit = cdiv(a.M, rows_per_wg);
-    const dim3 sgrid((unsigned)(nt * msplit));
-#define L2Q_HS(X, F, C) \
-  hipLaunchKernelGGL((u1_heads_stream_h_kernel<HT, X, F, C>), sgrid, block, 0, st, a, swz, rows_per_wg)
-    if (!xupd) { if (forward) L2Q_HS(false, true, false); else L2Q_HS(false, false, false); }
-    else if (use_ncp) { if (forward) L2Q_HS(true, true, true); else L2Q_HS(true, false, true); }
-    else { if (forward) L2Q_HS(true, true, false); else L2Q_HS(true, false, false); }
-#undef L2Q_HS
-    launch_finalize(part, tmp, a.M, a.ncols_part, 1, 1.0, 0.0, st);
-    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3((unsigned)cdiv(a.M, 64)), dim3(64), 0, st, tmp, logdet,
-                       a.M, accumulate);
-    return check_launch("l2q_u1_heads_update_h");
-  }
-#define L2Q_HH(X, F, C)                                                                          \
-  do {                                                                                           \
-    if (bm == 128)                                                                               \
-      hipLaunchKernelGGL((u1_heads_update_h_kernel<HT, X, F, C, 128>), grid, block, 0, st, a,    \
-                         swz, nfast, stg);                                                  \
-    else                                                                                         \
-      hipLaunchKernelGGL((u1_heads_update_h_kernel<HT, X, F, C, 64>), grid, block, 0, st, a,     \
-                         swz, nfast, stg);                                                  \
-  } while (0)
+  // tile kernel (tuning heads_h_stream = 0, or a shape the K-split stream kernel does not take)
+#define L2Q_HH(X, F, C) \
+  hipLaunchKernelGGL((u1_heads_update_h_kernel<HT, X, F, C, 128>), grid, block, 0, st, a, swz, nfast, stg)
   if (!xupd) { if (forward) L2Q_HH(false, true, false); else L2Q_HH(false, false, false); }
   else if (use_ncp) { if (forward) L2Q_HH(true, true, true); else L2Q_HH(true, false, true); }
   else { if (forward) L2Q_HH(true, true, false); else L2Q_HH(true, false, false); }
@@ -1316,7 +1036,6 @@ size_t l2q_gemm_h_ws_bytes(int M, int N, long K, long K2) {
   bool wide = false;
   const int splits = pick_config_h(M, N, K + K2, &wide);
   size_t need = (splits == 1 && !wide) ? 0 : (size_t)(splits + 1) * M * N * sizeof(float);
-  if (wide && splits == 1 && (long)M * N >= 1024L * 1024L) need = 0;     // fused wide tile
   // the streaming input-layer kernel (fp32 operands, N <= 256): up to 8 K-splits of partial sums.  The
   // element type and the U1X form are not known here: sized for any of them.
   if (tuning().gemm_h_skinny != 0 && N <= 256 && K + K2 >= 4096 && M >= 1024) {

@@ -4,8 +4,8 @@
 //
 // Why: the tile kernel stages 160 KB of Z and W through registers into LDS for every 128 x 64 tile (1.3 GB of
 // L2 -> LDS traffic per launch against 805 MB of HBM traffic) and runs at 0.25 of the HBM roofline; round 3's
-// stream kernel (u1_heads_stream_h_kernel) keeps a wavefront's 16 columns x 3 heads x K = 256 of W in 96
-// VGPRs, which leaves no registers for a second stage of operand prefetch (0.475 ms against 0.42).  Here
+// one-step stream kernel (since retired) kept a wavefront's 16 columns x 3 heads x K = 256 of W in 96
+// VGPRs, which left no registers for a second stage of operand prefetch (0.475 ms against 0.42).  Here
 //   * a workgroup = 8 wavefronts owns 64 entries (columns) and a range of chains.  Wavefront (cg, kh) keeps the
 //     three heads' weights of columns 16 cg .. 16 cg + 15 for K-half kh: 3 x 4 MFMA operands = 48 VGPRs;
 //   * the chains stream by in steps of 32 rows.  Per step a wavefront multiplies both 16-row tiles by its
@@ -24,9 +24,9 @@
 //     is bound by the VALU issue of its epilogue (97 instructions per entry, 10 of them quarter-rate, two wavefronts
 //     per SIMD in lockstep); with packed conversions, the bare v_log_f32 and compare-select min / max: 399 -> 259 VALU
 //     instructions per 4 entries, 0.324 -> 0.274 ms.
-// Same MFMA instruction and operand roles as the other two kernels; the K = 256 sum is formed as (k < 128) +
+// Same MFMA instruction and operand roles as the tile kernel; the K = 256 sum is formed as (k < 128) +
 // (k >= 128) in fp32 instead of one running accumulator: a rounding-level difference in front of the 16-bit
-// rounding of the head (rare 1-ulp16 flips, as between the tile and the stream kernel).
+// rounding of the head (rare 1-ulp16 flips).
 #include <type_traits>
 #include "heads_h_common.hpp"
 

@@ -11,29 +11,19 @@ namespace l2q {
 void set_error(const char* fmt, ...);
 
 struct Tuning {
-  int plaq_occ = 2;
-  int force_occ = 2;
   int xcd_swizzle = 1;
-  int plaq_sweep = 2;     // 2: slice-resident thread-per-site kernel (LDS + register prefetch), 3: slice-resident
-                          // with the six planes split over wavefronts (su3_plaq_nu.hip; measured slower),
-                          // 1: L2 t-sweep, 0: flat
   int heads_dma = 1;      // heads + v-update: LDS-DMA staged kernel (0: register-staged kernel of round 1)
   int force_tsplit = 0;   // su3_force_link.hip: 0 = t-range chunks chosen by the launcher, n = that many chunks per chain
   int force_stagger = 0;  // x ~2k cycles initial delay of the 2nd resident workgroup set (su3_force_link.hip)
   int heads_stagger = 0;  // x ~8k cycles initial delay of the 2nd resident block set (heads kernel)
   int force_tile = 5;     // 7: plaquettes shared between their four links, one 8-wavefront workgroup per CU (su3_force_plaq.hip;
                           //    plain force on lattices whose (y, z) plane is the 64-site tile: 1.17x HBM traffic, not faster),
-                          // 6: as 5 with two adjacent x-planes per workgroup (su3_force_pair.hip: half the x-halo),
-                          // 5: slice-resident thread-per-link, streamed factors, 2 workgroups / CU
-                          // (su3_force_link.hip), 4: staples split by plane over wavefronts (su3_force_nu.hip), 3: rows
-                          // split over wavefronts (su3_force_rows.hip), 2: slice-resident
-                          // thread-per-link, 1: LDS-tiled (64 sites x 4 mu), 0: flat
+                          // 5: slice-resident thread-per-link, streamed factors, 2 workgroups / CU (su3_force_link.hip),
+                          // 2: slice-resident thread-per-link (su3_force_slice_kernel; by default only on lattices too
+                          //    large for 5); each falls back down this list, ending at the LDS-tiled kernel (64 sites x 4 mu)
   int u1_fused_ch = 0;    // chains per workgroup of the fused U(1) kernels (0: auto; 1, 2, 4, 8)
-  int gemm_h_wide_fused = 0;  // large half GEMMs: 128 x 256 tile with 512 threads (measured slower)
   int conv_patch = 1;         // half conv: input patch staged in LDS by persistent workgroups for layers with
                               // <= 16 output channels (2: every layer it fits, 0: gather kernel only)
-  int conv_stream = 0;        // half conv: 1 = persistent whole-K kernel (conv_stream_f16.hip; measured slower at cfg-3:
-                              // 3.7 / 1.8 ms against the gather kernel's 2.6 / 1.2 ms), 0 = gather kernel
   int gemm_h_lt = 1;          // plain 16-bit layers with M, N, K >= 2048: hipBLASLt (gemm_lt.hip; 0: own kernels only)
   int gemm_h_dma = 1;         // big half GEMMs (M, N % 256 == 0, K % 64 == 0): LDS-DMA 256 x 256 kernel (0: off)
   int gemm_h_skinny = 1;      // wide-K fp32-operand input layer, N <= 256: streaming kernel (gemm_f16_skinny.hip);
@@ -42,9 +32,8 @@ struct Tuning {
   int gemm_h_patch = 1;       // half GEMM: 8 x 8 tile patches per XCD (0: row-major tile order)
   int heads_h_stream = 2; // half-precision heads+update: 2 = K-split stream kernel where its shape conditions hold
                           // (heads_kstream_f16.hip: K = 256 / 128 / 64, long streams; cfg-3: 0.22 / 0.32 ms per v- / x-update
-                          // against the tile kernel's 0.36 / 0.42), 1 = round 3's weights-stationary stream kernel
-                          // (0.475 ms), 0 = tile kernel only, 3 = as 2 for streams of any length (tests)
-  int heads_h_bm = 128;   // chains per workgroup of the half-precision heads+update kernel (64 | 128)
+                          // against the tile kernel's 0.36 / 0.42), 0 = tile kernel only, 3 = as 2 for streams of
+                          // any length (tests)
   int heads_h_order = 1;  // half-precision heads+update kernel: 0 m-tiles fastest, 1 n-tiles fastest (consecutive
                           // workgroups walk along the rows of the fp32 field: 0.50 -> 0.41 ms at cfg-3)
 };

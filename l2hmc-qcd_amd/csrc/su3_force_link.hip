@@ -5,8 +5,8 @@
 //   staple in the (mu, nu) plane    (the reference: autograd of the Wilson action + projectTAH,
 //   lattice/su3/pytorch/lattice.py:299-308)
 //
-// The same arithmetic and tile as su3_force_nu.hip, without its cross-wavefront exchange: a
-// wavefront owns direction mu of the tile's 64 sites and walks the three planes of mu itself.
+// The same arithmetic and tile as the retired plane-split kernel, without its cross-wavefront exchange:
+// a wavefront owns direction mu of the tile's 64 sites and walks the three planes of mu itself.
 // With the right-hand factors streamed (live set: acc, t, a = three 36-VGPR matrices + one row)
 // plus the carried t-staple and the 9-entry prefetch of the thread's own link, a thread needs
 // 210-246 registers: TWO wavefronts per SIMD.  A workgroup is 64 sites x 4 directions =
@@ -23,7 +23,7 @@
 // (A struct field set from a template constant does not do: it is folded after inlining.)
 //
 // MI355X, cfg-4 (8^4 x 256 chains): plain force 0.39-0.41 ms (0.37-0.39 of the 8 TB/s roofline; the
-// plane-split kernel su3_force_nu.hip: 0.43-0.45 ms), fused kick 0.51 ms (0.44; 0.61 ms);
+// retired plane-split kernel: 0.43-0.45 ms), fused kick 0.51 ms (0.44; 0.61 ms);
 // 16^4 x 64 chains: 1.89 / 2.39 ms (2.11 / 2.79 ms).  Results are bit-identical to the thread-per-link
 // slice kernel (same operation order per link).
 #include "su3_force_tile.hpp"

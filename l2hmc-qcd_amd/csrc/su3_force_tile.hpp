@@ -1,6 +1,6 @@
-// su3_force_tile.hpp -- addressing helpers shared by the slice-resident force kernels that split a
-// link's work over wavefronts (su3_force_rows.hip, su3_force_nu.hip): buffer loads with the
-// uniform part of the address in the scalar offset, ds_read_b128 with immediate entry offsets.
+// su3_force_tile.hpp -- addressing helpers shared by the 64-site-tile force kernels
+// (su3_force_link.hip, su3_force_plaq.hip): buffer loads with the uniform part of the address in
+// the scalar offset, ds_read_b128 with immediate entry offsets.
 #pragma once
 #include "l2q_common.hpp"
 #include "su3_math.hpp"
@@ -43,11 +43,6 @@ struct R3 {
   double re[3], im[3];
 };
 
-__device__ __forceinline__ void r3_zero(R3& a) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { a.re[k] = 0.0; a.im[k] = 0.0; }
-}
-
 // one periodic hop of a spatial site index q = (x*Y + y)*Z + z in direction dir (1, 2, 3)
 __device__ __forceinline__ int hop(int q, int x, int y, int z, int dir, int sgn, const Dims& d) {
   const int n = dir == 1 ? d.X : dir == 2 ? d.Y : d.Z;
@@ -83,16 +78,6 @@ __device__ __forceinline__ void ld_row(R3& a, int lds, __amdgpu_buffer_rsrc_t rs
   for (int k = 0; k < 3; ++k) {
     const double2 d = IN ? lds_ld(lds + (3 * row + k) * ENT) : buf_ld(rs, voff, soff + (3 * row + k) * V16);
     a.re[k] = d.x; a.im[k] = d.y;
-  }
-}
-
-// conj of column `col` of the link = row `col` of its adjoint
-template <bool IN>
-__device__ __forceinline__ void ld_colc(R3& a, int lds, __amdgpu_buffer_rsrc_t rs, int voff, int soff, int V16, int col) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double2 d = IN ? lds_ld(lds + (3 * k + col) * kEnt) : buf_ld(rs, voff, soff + (3 * k + col) * V16);
-    a.re[k] = d.x; a.im[k] = -d.y;
   }
 }
 

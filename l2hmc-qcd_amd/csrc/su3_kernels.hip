@@ -52,68 +52,6 @@ __global__ __launch_bounds__(kBlock, OCC) void su3_plaq_kernel(const double2* __
   }
 }
 
-// ------------------------------------------------------------------ staple force
-// KICK = false: fn[c][mu] = coef * TAH(U A);  KICK = true: vn[c][mu] += coef * TAH(U A)
-// A_mu(s) = sum_{nu != mu} [ U_nu(s+mu) U_mu(s+nu)^H U_nu(s)^H
-//                           + U_nu(s+mu-nu)^H U_mu(s-nu)^H U_nu(s-nu) ]
-template <bool KICK, int OCC>
-__global__ __launch_bounds__(kBlock, OCC) void su3_force_kernel(const double2* __restrict__ xn,
-                                                                Dims d, long nblk, int swz, double coef,
-                                                                double2* __restrict__ out) {
-  const long total = (long)gridDim.x;
-  const long w = xcd_swizzle(blockIdx.x, total, swz);
-  // logical order: chain-major, then site block, then mu (4 consecutive blocks share sites)
-  const int mu = (int)(w & 3);
-  const long cb = w >> 2;
-  const long c = cb / nblk, blk = cb % nblk;
-  const int s = (int)blk * kBlock + threadIdx.x;
-  if (s >= d.V) return;
-  const int V = d.V;
-  const double2* xc = xn + c * 36L * V;
-  const double2* fm = xc + mu * 9 * V;
-  const Site p = site_coords(s, d);
-  const int cmu = coord_of(p, mu);
-  const int s_pmu = fwd(s, cmu, d, mu);
-  M3 acc;
-  m3_zero(acc);
-#pragma unroll 1
-  for (int nu = 0; nu < 4; ++nu) {
-    if (nu == mu) continue;
-    const double2* fn = xc + nu * 9 * V;
-    const int cnu = coord_of(p, nu);
-    const int s_pnu = fwd(s, cnu, d, nu);
-    const int s_mnu = bwd(s, cnu, d, nu);
-    const int s_pmu_mnu = bwd(s_pmu, cnu, d, nu);     // nu-coordinate unchanged by the mu hop
-    M3 a, b, t;
-    // up:   U_nu(s+mu) U_mu(s+nu)^H U_nu(s)^H
-    load_link(a, fn, V, s_pmu);
-    load_link(b, fm, V, s_pnu);
-    m3_mul_na(t, a, b);
-    load_link(a, fn, V, s);
-    m3_mac_na(acc, t, a);
-    // down: U_nu(s+mu-nu)^H U_mu(s-nu)^H U_nu(s-nu)
-    load_link(a, fn, V, s_pmu_mnu);
-    load_link(b, fm, V, s_mnu);
-    m3_mul_aa(t, a, b);
-    load_link(a, fn, V, s_mnu);
-    m3_mac_nn(acc, t, a);
-  }
-  M3 u, ua, f;
-  load_link(u, fm, V, s);
-  m3_mul_nn(ua, u, acc);
-  m3_tah(f, ua);
-  double2* o = out + (c * 4 + mu) * 9L * V;
-#pragma unroll
-  for (int e = 0; e < 9; ++e) {
-    double2 r = make_double2(coef * f.re[e], coef * f.im[e]);
-    if (KICK) {
-      const double2 v = o[e * V + s];
-      r.x += v.x; r.y += v.y;
-    }
-    o[e * V + s] = r;
-  }
-}
-
 // Per-plane variant for LatticeLoss._plaq_loss (loss/pytorch/loss.py:57-70 sums each of the 6
 // planes separately): partial[c][blk][plane][re|im]; same site loop, one block reduction per
 // plane.
@@ -204,60 +142,6 @@ __global__ __launch_bounds__(kBlock) void diff_norm2_kernel(const double* __rest
   }
   const double r = block_sum(acc, lds);
   if (threadIdx.x == 0) partial[c * nblk + blk] = r;
-}
-
-// ------------------------------------------------------------------ plaquette, t-sweep
-// One workgroup = 256 spatial sites of one chain, sweeping a range of t.  The +t neighbours
-// loaded in iteration t (U_x, U_y, U_z at t+1) are the same lines the block asks for as its
-// own links one iteration later, i.e. within ~1 us on the same XCD -> L2 hits instead of a
-// second trip through the fabric (the flat kernel re-fetched them: 2.7x algorithmic bytes).
-template <int OCC>
-__global__ __launch_bounds__(kBlock, OCC) void su3_plaq_sweep_kernel(
-    const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz,
-    double* __restrict__ partial) {
-  __shared__ double lds[8];
-  const long w = xcd_swizzle(blockIdx.x, gridDim.x, swz);
-  const int per_chain = nsb * tsplit;
-  const long c = w / per_chain;
-  const int r = (int)(w % per_chain);
-  const int tc = r / nsb, sb = r % nsb;
-  const int Vs = d.X * d.Y * d.Z;
-  const int sp = sb * kBlock + threadIdx.x;             // spatial site
-  const int tlen = (d.T + tsplit - 1) / tsplit;
-  const int t0 = tc * tlen, t1 = min(d.T, t0 + tlen);
-  double sr = 0.0, si = 0.0;
-  if (sp < Vs) {
-    const double2* xc = xn + c * 36L * d.V;
-    const int V = d.V;
-    Site p = site_coords(sp, d);                         // p.t == 0 here (sp < Vs)
-#pragma unroll 1
-    for (int t = t0; t < t1; ++t) {
-      p.t = t;
-      const int s = t * Vs + sp;
-#pragma unroll 1
-      for (int u = 1; u < 4; ++u) {
-        const int s_pu = fwd(s, coord_of(p, u), d, u);
-        M3 au;
-        load_link(au, xc + u * 9 * V, V, s);
-#pragma unroll 1
-        for (int v = 0; v < u; ++v) {
-          const int s_pv = fwd(s, coord_of(p, v), d, v);
-          M3 a, b, yuv;
-          load_link(b, xc + v * 9 * V, V, s_pu);
-          m3_mul_nn(yuv, au, b);
-          load_link(a, xc + v * 9 * V, V, s);
-          load_link(b, xc + u * 9 * V, V, s_pv);
-          m3_trace_y_abh(sr, si, yuv, a, b);
-        }
-      }
-    }
-  }
-  const double br = block_sum(sr, lds);
-  const double bi = block_sum(si, lds + 4);
-  if (threadIdx.x == 0) {
-    partial[(c * per_chain + r) * 2 + 0] = br;
-    partial[(c * per_chain + r) * 2 + 1] = bi;
-  }
 }
 
 // ------------------------------------------------------------------ plaquette, slice-resident
@@ -421,12 +305,15 @@ __global__ __launch_bounds__(kSlice, 1) void su3_plaq_slice_kernel(
 }
 
 // ------------------------------------------------------------------ staple force, LDS tile
+// KICK = false: fn[c][mu] = coef * TAH(U A);  KICK = true: vn[c][mu] += coef * TAH(U A)
+// A_mu(s) = sum_{nu != mu} [ U_nu(s+mu) U_mu(s+nu)^H U_nu(s)^H
+//                           + U_nu(s+mu-nu)^H U_mu(s-nu)^H U_nu(s-nu) ]
 // One workgroup = 64 consecutive sites x 4 directions (wavefront w <-> mu = w).  The 4 own
 // links of the 64 sites are staged once in LDS ([4][9][64] complex = 36 KiB); every operand
 // whose site falls inside the tile (the site itself and, for 8^4 / 16^4 lattices, all +-y,
 // +-z neighbours of a (y,z) plane) is then an LDS read instead of a 9 KiB trip to L2.
-// For 8^4 that turns 42 of the 76 matrix loads per site into LDS reads (the flat kernel is
-// L2-bandwidth-bound: 12 GB of L2->L1 traffic per launch at cfg-4).
+// For 8^4 that turns 42 of the 76 matrix loads per site into LDS reads (a flat thread-per-link
+// kernel is L2-bandwidth-bound: 12 GB of L2->L1 traffic per launch at cfg-4).
 struct TileRef {
   const double2* lds;    // [4][9][64]
   int s0;                // first site of the tile
@@ -519,7 +406,7 @@ __global__ __launch_bounds__(kBlock, OCC) void su3_force_tile_kernel(
 // spatial link in the t direction, built from slice t-1 links only) are computed one
 // iteration early and carried in registers, so slice t-1 is never needed again.
 // Per site and sweep the links are read from HBM once (+ the x-halo of the tile); ~17 of the
-// 19 operands of a link come from LDS instead of L2 (the flat kernel issues 76 matrix loads
+// 19 operands of a link come from LDS instead of L2 (a flat thread-per-link kernel issues 76 matrix loads
 // per site to L2 and leaves the SIMDs idle 53 % of the time waiting for them).
 // Register budget decides this kernel.  A workgroup is 64 sites x 4 directions = 4 wavefronts and
 // is compiled for ONE wavefront per SIMD (__launch_bounds__(256, 1)): the unified register file
@@ -1011,19 +898,6 @@ __global__ void check_finalize_kernel(const double* __restrict__ psum,
 }  // namespace l2q
 
 namespace l2q {
-// su3_force_rows.hip
-bool force_rows_applicable(const Dims& d);
-int force_rows_inmask(const Dims& d);
-// su3_force_nu.hip
-bool force_nu_applicable(const Dims& d);
-int force_nu_inmask(const Dims& d);
-bool plaq_nu_applicable(const Dims& d);
-long plaq_nu_per_chain(const Dims& d, int nb);
-void launch_plaq_nu(const double2* xn, Dims d, int nb, double* partial, hipStream_t st);
-void launch_force_nu(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out,
-                     hipStream_t st);
-void launch_force_rows(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out,
-                       hipStream_t st);
 // su3_force_link.hip
 bool force_link_applicable(const Dims& d);
 int force_link_inmask(const Dims& d);
@@ -1035,29 +909,16 @@ bool gemm_h_lt_available();
 // su3_force_plaq.hip
 bool force_plaq_applicable(const Dims& d);
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);
-// su3_force_pair.hip
-bool force_pair_applicable(const Dims& d);
-int force_pair_inmask(const Dims& d);
-void launch_force_pair(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out,
-                       hipStream_t st, const double2* vin = nullptr);
 }  // namespace l2q
 
 using namespace l2q;
 
-// force_tile = 4 picks per lattice (same-box A/B, tools/force_bench.py): the plane-split kernel
-// wins when its 64-site tile holds whole (y,z)-planes (8^4: 0.466 vs 0.575 ms) and for the fused
-// kick; on 16^4 (tile = 4 z-rows: y AND x leave the tile) the plain force is 7 % faster with the
-// 128-site thread-per-link kernel (2.11 vs 2.26 ms at 64 chains).
+// The force kernel ladder: tuning force_tile = 7 (plain force only) the plaquette-sharing kernel, 5 (the
+// default) and 7 the thread-per-link kernel, where they apply; then the slice-resident kernel where the
+// spatial volume is whole tiles, else the LDS-tiled kernel, which takes any lattice.  force_tile = 2 starts
+// at the slice-resident kernel (the only way to reach it below the link kernel's size limit).
 template <bool KICK>
-static bool nu_preferred(const Dims& d) {
-  const int Vs_ = d.X * d.Y * d.Z;
-  const bool slice_ok = Vs_ % (KICK ? kFSKick : kFSPlain) == 0;
-  return KICK || !slice_ok || (force_nu_inmask(d) & 2) != 0;
-}
-
-template <bool KICK>
-static void launch_force(const double2* xn, Dims d, int nb, long nblk, double coef, double2* out,
-                         hipStream_t st) {
+static void launch_force(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
   const int Vs_ = d.X * d.Y * d.Z;
   constexpr int kFS = KICK ? kFSKick : kFSPlain;
   constexpr int kVar = KICK ? 2 : 0;
@@ -1066,23 +927,11 @@ static void launch_force(const double2* xn, Dims d, int nb, long nblk, double co
     launch_force_plaq(xn, d, nb, coef, out, st);               // plaquettes shared between their four links
     return;
   }
-  if (tuning().force_tile == 6 && force_pair_applicable(d)) {
-    launch_force_pair(KICK, xn, d, nb, coef, out, st);
-    return;
-  }
   if (tuning().force_tile >= 5 && force_link_applicable(d)) {
     launch_force_link(KICK, xn, d, nb, coef, out, st);
     return;
   }
-  if (tuning().force_tile >= 4 && force_nu_applicable(d) && nu_preferred<KICK>(d)) {
-    launch_force_nu(KICK, xn, d, nb, coef, out, st);
-    return;
-  }
-  if (tuning().force_tile == 3 && force_rows_applicable(d)) {
-    launch_force_rows(KICK, xn, d, nb, coef, out, st);
-    return;
-  }
-  if (tuning().force_tile >= 2 && Vs_ % kFS == 0) {
+  if (Vs_ % kFS == 0) {
     const int nsb = Vs_ / kFS;
     int tsplit = (int)cdiv(512, (long)nb * nsb);       // >= ~2 resident rounds of 256 CUs
     if (tsplit > d.T) tsplit = d.T;
@@ -1100,24 +949,9 @@ static void launch_force(const double2* xn, Dims d, int nb, long nblk, double co
                        tsplit, tuning().xcd_swizzle, coef, out);
     return;
   }
-  if (tuning().force_tile) {
-    const long ntile = cdiv(d.V, 64);
-    const dim3 grid((unsigned)(nb * ntile)), block(kBlock);
-    const int swz = tuning().xcd_swizzle;
-    switch (tuning().force_occ) {
-      case 4: hipLaunchKernelGGL((su3_force_tile_kernel<KICK, 4>), grid, block, 0, st, xn, d, ntile, swz, coef, out); break;
-      case 3: hipLaunchKernelGGL((su3_force_tile_kernel<KICK, 3>), grid, block, 0, st, xn, d, ntile, swz, coef, out); break;
-      default: hipLaunchKernelGGL((su3_force_tile_kernel<KICK, 2>), grid, block, 0, st, xn, d, ntile, swz, coef, out); break;
-    }
-    return;
-  }
-  const dim3 grid((unsigned)(nb * nblk * 4)), block(kBlock);
-  const int swz = tuning().xcd_swizzle;
-  switch (tuning().force_occ) {
-    case 4: hipLaunchKernelGGL((su3_force_kernel<KICK, 4>), grid, block, 0, st, xn, d, nblk, swz, coef, out); break;
-    case 3: hipLaunchKernelGGL((su3_force_kernel<KICK, 3>), grid, block, 0, st, xn, d, nblk, swz, coef, out); break;
-    default: hipLaunchKernelGGL((su3_force_kernel<KICK, 2>), grid, block, 0, st, xn, d, nblk, swz, coef, out); break;
-  }
+  const long ntile = cdiv(d.V, 64);
+  hipLaunchKernelGGL((su3_force_tile_kernel<KICK, 2>), dim3((unsigned)(nb * ntile)), dim3(kBlock), 0, st, xn, d,
+                     ntile, tuning().xcd_swizzle, coef, out);
 }
 
 static bool dims_ok(int nb, int T, int X, int Y, int Z) {
@@ -1132,32 +966,21 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
   const Tuning& t = tuning();
   buf[0] = 0;
   if (!strcmp(entry, "l2q_su3_plaq_reduce")) {
-    const Dims dq{T, X, Y, Z, T * X * Y * Z};
-    if (t.plaq_sweep == 3 && plaq_nu_applicable(dq))
-      snprintf(buf, buf_bytes, "su3_plaq_nu_kernel<%d>", force_nu_inmask(dq));
-    else if (t.plaq_sweep >= 2 && Vs % kSlice == 0)
+    if (Vs % kSlice == 0)
       snprintf(buf, buf_bytes, "su3_plaq_slice_kernel<%s>", (kSlice % (Y * Z)) == 0 ? "true" : "false");
-    else if (t.plaq_sweep == 1) snprintf(buf, buf_bytes, "su3_plaq_sweep_kernel<%d>", t.plaq_occ);
-    else snprintf(buf, buf_bytes, "su3_plaq_kernel<%d>", t.plaq_occ);
+    else snprintf(buf, buf_bytes, "su3_plaq_kernel<2>");
   } else if (!strcmp(entry, "l2q_su3_force") || !strcmp(entry, "l2q_su3_force_kick")) {
     const bool kick = !strcmp(entry, "l2q_su3_force_kick");
     const int fs = kick ? kFSKick : kFSPlain;
     const Dims dd{T, X, Y, Z, T * X * Y * Z};
     if (!kick && t.force_tile == 7 && force_plaq_applicable(dd))
       snprintf(buf, buf_bytes, "su3_force_plaq_kernel");
-    else if (t.force_tile == 6 && force_pair_applicable(dd))
-      snprintf(buf, buf_bytes, "su3_force_pair_kernel<%d, %d>", kick ? 1 : 0, force_pair_inmask(dd));
     else if (t.force_tile >= 5 && force_link_applicable(dd))
       snprintf(buf, buf_bytes, "su3_force_link_kernel<%d, %d>", kick ? 1 : 0, force_link_inmask(dd));
-    else if (t.force_tile >= 4 && force_nu_applicable(dd) && (kick ? nu_preferred<true>(dd) : nu_preferred<false>(dd)))
-      snprintf(buf, buf_bytes, "su3_force_nu_kernel<%d, %d>", kick ? 1 : 0, force_nu_inmask(dd));
-    else if (t.force_tile == 3 && Vs % 64 == 0)
-      snprintf(buf, buf_bytes, "su3_force_rows_kernel<%d, %d>", kick ? 1 : 0, force_rows_inmask(Dims{T, X, Y, Z, T * X * Y * Z}));
-    else if (t.force_tile >= 2 && Vs % fs == 0)
+    else if (Vs % fs == 0)
       snprintf(buf, buf_bytes, "su3_force_slice_kernel<%s, %d, %d, %d>", kick ? "true" : "false", fs,
                kick ? 2 : 0, kick ? 1 : kLptPlain);
-    else if (t.force_tile) snprintf(buf, buf_bytes, "su3_force_tile_kernel<%s, %d>", kick ? "true" : "false", t.force_occ);
-    else snprintf(buf, buf_bytes, "su3_force_kernel<%s, %d>", kick ? "true" : "false", t.force_occ);
+    else snprintf(buf, buf_bytes, "su3_force_tile_kernel<%s, 2>", kick ? "true" : "false");
   } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64")) {
     snprintf(buf, buf_bytes, "heads_sliced_kernel");
   } else if (!strncmp(entry, "l2q_vnet_heads_vupdate", 22)) {
@@ -1188,16 +1011,7 @@ int l2q_su3_plaq_reduce(const void* xn, int nb, int T, int X, int Y, int Z, doub
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)ws;
   const int swz = tuning().xcd_swizzle;
-  if (tuning().plaq_sweep == 3 && plaq_nu_applicable(d)) {
-    // six planes of a site over six wavefronts, 3 wavefronts per SIMD (su3_plaq_nu.hip)
-    const long per_chain = plaq_nu_per_chain(d, nb);
-    L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 2 * sizeof(double), L2Q_ESHAPE,
-                "workspace too small");
-    launch_plaq_nu((const double2*)xn, d, nb, partial, st);
-    launch_finalize(partial, out, nb, per_chain, 2, 1.0, 0.0, st);
-    return check_launch("l2q_su3_plaq_reduce");
-  }
-  if (tuning().plaq_sweep >= 2 && (X * Y * Z) % kSlice == 0) {
+  if ((X * Y * Z) % kSlice == 0) {
     const int Vs = X * Y * Z;
     const int nsb = Vs / kSlice;
     int tsplit = (int)cdiv(1024, (long)nb * nsb);      // keep >= ~1024 workgroups
@@ -1217,34 +1031,10 @@ int l2q_su3_plaq_reduce(const void* xn, int nb, int T, int X, int Y, int Z, doub
     launch_finalize(partial, out, nb, per_chain, 2, 1.0, 0.0, st);
     return check_launch("l2q_su3_plaq_reduce");
   }
-  if (tuning().plaq_sweep == 1) {
-    const int Vs = X * Y * Z;
-    const int nsb = (int)cdiv(Vs, kBlock);
-    int tsplit = (int)cdiv(1024, (long)nb * nsb);      // keep >= ~1024 workgroups in flight
-    if (tsplit > T) tsplit = T;
-    if (tsplit < 1) tsplit = 1;
-    const int tlen = (int)cdiv(T, tsplit);
-    tsplit = (int)cdiv(T, tlen);
-    const long per_chain = (long)nsb * tsplit;
-    L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 2 * sizeof(double), L2Q_ESHAPE,
-                "workspace too small");
-    const dim3 grid((unsigned)(nb * per_chain)), block(kBlock);
-    switch (tuning().plaq_occ) {
-      case 4: hipLaunchKernelGGL(su3_plaq_sweep_kernel<4>, grid, block, 0, st, (const double2*)xn, d, nsb, tsplit, swz, partial); break;
-      case 3: hipLaunchKernelGGL(su3_plaq_sweep_kernel<3>, grid, block, 0, st, (const double2*)xn, d, nsb, tsplit, swz, partial); break;
-      default: hipLaunchKernelGGL(su3_plaq_sweep_kernel<2>, grid, block, 0, st, (const double2*)xn, d, nsb, tsplit, swz, partial); break;
-    }
-    launch_finalize(partial, out, nb, per_chain, 2, 1.0, 0.0, st);
-    return check_launch("l2q_su3_plaq_reduce");
-  }
   const long nblk = cdiv(d.V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * 2 * sizeof(double), L2Q_ESHAPE, "workspace too small");
-  const dim3 grid((unsigned)(nb * nblk)), block(kBlock);
-  switch (tuning().plaq_occ) {
-    case 4: hipLaunchKernelGGL(su3_plaq_kernel<4>, grid, block, 0, st, (const double2*)xn, d, nblk, swz, partial); break;
-    case 3: hipLaunchKernelGGL(su3_plaq_kernel<3>, grid, block, 0, st, (const double2*)xn, d, nblk, swz, partial); break;
-    default: hipLaunchKernelGGL(su3_plaq_kernel<2>, grid, block, 0, st, (const double2*)xn, d, nblk, swz, partial); break;
-  }
+  hipLaunchKernelGGL(su3_plaq_kernel<2>, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, st, (const double2*)xn, d,
+                     nblk, swz, partial);
   launch_finalize(partial, out, nb, nblk, 2, 1.0, 0.0, st);
   return check_launch("l2q_su3_plaq_reduce");
 }
@@ -1292,8 +1082,7 @@ int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, i
   L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(xn != fn, L2Q_EINVAL, "force output must not alias the gauge field");
   Dims d{T, X, Y, Z, T * X * Y * Z};
-  const long nblk = cdiv(d.V, kBlock);
-  launch_force<false>((const double2*)xn, d, nb, nblk, beta / 3.0, (double2*)fn, (hipStream_t)stream);
+  launch_force<false>((const double2*)xn, d, nb, beta / 3.0, (double2*)fn, (hipStream_t)stream);
   return check_launch("l2q_su3_force");
 }
 
@@ -1302,8 +1091,7 @@ int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int n
   L2Q_REQUIRE(xn && vn, L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   Dims d{T, X, Y, Z, T * X * Y * Z};
-  const long nblk = cdiv(d.V, kBlock);
-  launch_force<true>((const double2*)xn, d, nb, nblk, coef * beta / 3.0, (double2*)vn, (hipStream_t)stream);
+  launch_force<true>((const double2*)xn, d, nb, coef * beta / 3.0, (double2*)vn, (hipStream_t)stream);
   return check_launch("l2q_su3_force_kick");
 }
 
@@ -1313,11 +1101,6 @@ int l2q_su3_force_kick_to(const void* xn, double beta, double coef, const void* 
   L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   Dims d{T, X, Y, Z, T * X * Y * Z};
   hipStream_t st = (hipStream_t)stream;
-  if (v_in != v_out && tuning().force_tile == 6 && force_pair_applicable(d)) {
-    launch_force_pair(true, (const double2*)xn, d, nb, coef * beta / 3.0, (double2*)v_out, st,
-                      (const double2*)v_in);
-    return check_launch("l2q_su3_force_kick_to");
-  }
   if (v_in != v_out && tuning().force_tile >= 5 && force_link_applicable(d)) {
     launch_force_link(true, (const double2*)xn, d, nb, coef * beta / 3.0, (double2*)v_out, st,
                       (const double2*)v_in);

@@ -171,7 +171,7 @@ def load() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _lib = lib
-        # L2Q_TUNING="force_tile=7,plaq_sweep=2": tuning knobs of include/l2q.h (l2q_set_tuning) for a whole process --
+        # L2Q_TUNING="force_tile=7,xcd_swizzle=0": tuning knobs of include/l2q.h (l2q_set_tuning) for a whole process --
         # A/B runs of bench.py / the tests without code changes (the table is per device: applies to the current one)
         for kv in filter(None, os.environ.get('L2Q_TUNING', '').split(',')):
             k, _, v = kv.partition('=')

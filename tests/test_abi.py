@@ -26,15 +26,64 @@ def test_library_exports_header():
     assert lib.l2q_version() >= 100
 
 
-def test_argument_validation_without_gpu():
+def test_argument_errors_without_gpu():
     from l2hmc import native
     lib = native.load()
     assert lib.l2q_su3_force(None, 6.0, None, 1, 2, 2, 2, 2, None) == -1          # L2Q_EINVAL
     assert b'null pointer' in lib.l2q_last_error()
     assert lib.l2q_transpose(1, 2, 1, 4, 4, 3, None) == -1                       # bad elem size
-    assert lib.l2q_set_tuning(b'force_occ', 7) == -1
-    assert lib.l2q_set_tuning(b'force_occ', 2) in (2, 3, 4)
+    assert lib.l2q_set_tuning(b'xcd_swizzle', 7) == -1
+    assert lib.l2q_set_tuning(b'xcd_swizzle', 1) in (0, 1)
     assert lib.l2q_reduce_ws_bytes(4, 1000) > 0 and lib.l2q_gemm_ws_bytes(256, 256, 262144, 0) > 0
+
+
+def test_tuning_keys_and_values():
+    """Retired knobs and values are unknown to l2q_set_tuning (L2Q_EINVAL, as any unknown key); the kept values of
+    the two narrowed knobs are accepted."""
+    from l2hmc import native
+    lib = native.load()
+    for key in (b'plaq_occ', b'force_occ', b'plaq_sweep', b'conv_stream', b'gemm_h_wide_fused', b'heads_h_bm'):
+        for value in (0, 1, 2, 3, 4, 64, 128):
+            assert lib.l2q_set_tuning(key, value) == -1, (key, value)
+    for key, retired, kept, default in ((b'force_tile', (0, 1, 3, 4, 6, 8), (2, 7, 5), 5),
+                                        (b'heads_h_stream', (1, 4), (0, 3, 2), 2)):
+        for value in retired:
+            assert lib.l2q_set_tuning(key, value) == -1, (key, value)
+        try:
+            for value in kept:
+                assert lib.l2q_set_tuning(key, value) >= 0, (key, value)
+                assert lib.l2q_set_tuning(key, value) == value, (key, value)
+        finally:
+            lib.l2q_set_tuning(key, default)
+
+
+def test_kernel_dispatch_names():
+    """Host-side kernel choice of the SU(3) stencils under the default tuning (no GPU work): the names that the
+    recorded PMC profiles are matched against (8^4, 16^4), the LDS-tiled force and the flat plaquette on lattices
+    whose spatial volume is no whole tile, the thread-per-link force with the flat plaquette, and the slice-resident
+    force on a lattice too large for the thread-per-link kernel; then force_tile 2 and 7 at 8^4."""
+    from l2hmc import native
+    ents = ('l2q_su3_force', 'l2q_su3_force_kick', 'l2q_su3_plaq_reduce')
+    expect = {
+        (8, 8, 8, 8): ('su3_force_link_kernel<0, 6>', 'su3_force_link_kernel<1, 6>', 'su3_plaq_slice_kernel<true>'),
+        (16, 16, 16, 16): ('su3_force_link_kernel<0, 4>', 'su3_force_link_kernel<1, 4>',
+                           'su3_plaq_slice_kernel<false>'),
+        (1, 3, 2, 5): ('su3_force_tile_kernel<false, 2>', 'su3_force_tile_kernel<true, 2>', 'su3_plaq_kernel<2>'),
+        (3, 5, 2, 7): ('su3_force_tile_kernel<false, 2>', 'su3_force_tile_kernel<true, 2>', 'su3_plaq_kernel<2>'),
+        (2, 4, 4, 12): ('su3_force_link_kernel<0, 0>', 'su3_force_link_kernel<1, 0>', 'su3_plaq_kernel<2>'),
+        (8192, 8, 8, 8): ('su3_force_slice_kernel<false, 128, 0, 2>', 'su3_force_slice_kernel<true, 128, 2, 1>',
+                          'su3_plaq_slice_kernel<true>'),
+    }
+    for L, names in expect.items():
+        assert tuple(native.kernel_name(e, L) for e in ents) == names, L
+    L = (8, 8, 8, 8)
+    try:
+        assert native.set_tuning('force_tile', 2) >= 0
+        assert native.kernel_name('l2q_su3_force', L) == 'su3_force_slice_kernel<false, 128, 0, 2>'
+        assert native.set_tuning('force_tile', 7) >= 0
+        assert native.kernel_name('l2q_su3_force', L) == 'su3_force_plaq_kernel'
+    finally:
+        native.set_tuning('force_tile', 5)
 
 
 def test_half_layer_kernel_plan_host_logic():
@@ -64,7 +113,7 @@ def test_half_layer_kernel_plan_host_logic():
         assert lib.l2q_gemm_h_ws_bytes(8192, 256, 8192, 8192) < need
     finally:
         lib.l2q_set_tuning(b'gemm_h_skinny', prev if prev >= 0 else 1)
-    assert lib.l2q_set_tuning(b'heads_h_stream', 4) == -1 and lib.l2q_set_tuning(b'heads_h_stream', 2) in (0, 1, 2, 3)
+    assert lib.l2q_set_tuning(b'heads_h_stream', 4) == -1 and lib.l2q_set_tuning(b'heads_h_stream', 2) in (0, 2, 3)
     assert lib.l2q_set_tuning(b'gemm_h_small', 1) in (0, 1)
 
 

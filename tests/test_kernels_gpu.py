@@ -109,39 +109,30 @@ def test_su3_stencils_vs_oracle(ops, L):
     f = host(ops.su3_unpack(ops.su3_force_n(xn, 5.7, L), L))
     assert err(f, osu3.grad_action(x, 5.7)) < 1e-12
     from l2hmc import native
-    # every kernel variant (register budget, flat vs t-sweep plaquette, flat vs LDS-tiled
-    # force, with / without the XCD remap) must give the same numbers
-    # (force_tile 7 = plaquettes shared between their four links, one 8-wavefront workgroup per CU,
-    # su3_force_plaq.hip: taken where the (y, z) plane is the 64-site tile and T >= 2 -- (3,8,8,8), (2,2,8,8),
+    # every force kernel design, with and without the XCD remap, must give the same numbers.  The plaquette runs
+    # the slice kernel where X Y Z % 128 == 0 and the flat kernel elsewhere, whatever the force design.
+    # force_tile 7 = plaquettes shared between their four links, one 8-wavefront workgroup per CU, su3_force_plaq.hip
+    # (plain force only): taken where the (y, z) plane is the 64-site tile and T >= 2 -- (3,8,8,8), (2,2,8,8),
     # (4,3,8,8): x extent 8, 2 (both x neighbours are the same plane) and odd -- and falls back to 5 elsewhere;
-    # force_tile 6 = two x-planes per workgroup, su3_force_pair.hip -- (3,8,8,8), (2,2,8,8), (1,2,8,8) with
-    # whole (y,z) planes per group, (2,4,8,16) with half planes; it falls back to 5 elsewhere;
-    # force_tile 7 = plaquettes shared between their four links, one 8-wavefront workgroup per CU, su3_force_plaq.hip:
-    # taken where the (y, z) plane is the 64-site tile -- (3,8,8,8), (2,2,8,8), (1,2,8,8) with one / both x neighbours
-    # being the site itself or its only other plane, (4,3,8,8) with an odd x extent; elsewhere the variant falls back
-    # to the thread-per-link kernel;
-    # force_tile 5 = thread per link with streamed factors, su3_force_link.hip; plaq_sweep 3 = planes
-    # over wavefronts, su3_plaq_nu.hip;
-    # force_tile 3 = rows split over wavefronts, su3_force_rows.hip: the lattices above cover its
-    # four tile-residency specialisations -- Z | 64, Y Z | 64, X Y Z | 64, none -- and T = 1)
-    for occ in (2, 3, 4):
-        for variant in (0, 1, 2, 3, 4, 5, 6, 7):
-            for swz in (0, 1):
-                native.set_tuning('force_occ', occ); native.set_tuning('plaq_occ', occ)
-                native.set_tuning('plaq_sweep', min(variant, 3)); native.set_tuning('force_tile', variant)
-                native.set_tuning('xcd_swizzle', swz)
-                assert err(host(ops.su3_plaq_sums_n(xn, L)), s) < 1e-10
-                assert err(host(ops.su3_unpack(ops.su3_force_n(xn, 5.7, L), L)), f) < 1e-13
-                v = xn.clone()
-                ops.su3_force_kick_n(xn, 5.7, -0.3, v, L)
-                assert err(host(ops.su3_unpack(v, L)), x - 0.3 * f) < 1e-12
-                # out of place (l2q_su3_force_kick_to): the same bits, the source untouched
-                src = xn.clone(); v2 = torch.full_like(xn, float('nan'))
-                ops.su3_force_kick_n(xn, 5.7, -0.3, v2, L, v_src=src)
-                assert torch.equal(v2, v) and torch.equal(src, xn)
-    for k, val in (('force_occ', 2), ('plaq_occ', 2), ('plaq_sweep', 2), ('force_tile', 5),
-                   ('xcd_swizzle', 1)):
-        native.set_tuning(k, val)
+    # force_tile 5 (the default) = thread per link with streamed factors, su3_force_link.hip, where X Y Z % 64 == 0;
+    # its four tile-residency specialisations -- Z | 64, Y Z | 64, X Y Z | 64, none -- and T = 1 are covered above;
+    # force_tile 2 = the slice-resident thread-per-link kernel where X Y Z % 128 == 0.
+    # Both 5 and 2 fall back to the LDS-tiled kernel on the other lattices.
+    for variant in (2, 5, 7):
+        for swz in (0, 1):
+            native.set_tuning('force_tile', variant)
+            native.set_tuning('xcd_swizzle', swz)
+            assert err(host(ops.su3_plaq_sums_n(xn, L)), s) < 1e-10
+            assert err(host(ops.su3_unpack(ops.su3_force_n(xn, 5.7, L), L)), f) < 1e-13
+            v = xn.clone()
+            ops.su3_force_kick_n(xn, 5.7, -0.3, v, L)
+            assert err(host(ops.su3_unpack(v, L)), x - 0.3 * f) < 1e-12
+            # out of place (l2q_su3_force_kick_to): the same bits, the source untouched
+            src = xn.clone(); v2 = torch.full_like(xn, float('nan'))
+            ops.su3_force_kick_n(xn, 5.7, -0.3, v2, L, v_src=src)
+            assert torch.equal(v2, v) and torch.equal(src, xn)
+    native.set_tuning('force_tile', 5)
+    native.set_tuning('xcd_swizzle', 1)
 
 
 def test_su3_cold_start(ops):
@@ -918,13 +909,6 @@ def test_conv_gemm_periodic_h(hd, layout, dims):
             alt = ops.conv2d_periodic_gemm_h(xin.cuda(), layout, w16.cuda(), b.cuda(), pool, act)
             assert torch.equal(alt, got), (cp, float((alt.float() - got.float()).abs().max()))
         native.set_tuning('conv_patch', 1)
-        # the persistent whole-K kernel (conv_stream_f16.hip, off by default): same products, same order
-        native.set_tuning('conv_stream', 1)
-        try:
-            alt = ops.conv2d_periodic_gemm_h(xin.cuda(), layout, w16.cuda(), b.cuda(), pool, act)
-        finally:
-            native.set_tuning('conv_stream', 0)
-        assert torch.equal(alt, got), ('conv_stream', float((alt.float() - got.float()).abs().max()))
         if pool == 2:
             # conv + MaxPool2d(2) + act in one kernel (the default) == conv, then the pool kernel
             ops.FUSE_CONV_POOL_H[0] = False
@@ -1150,52 +1134,6 @@ def test_lattice_edge_shapes_vs_oracle():
             xh = host(x).astype(np.float64)
             assert err(host(lat.action(x, b)), ou1.action(xh, 2.5)) < 2e-5, L
             assert err(host(lat.grad_action(x, b)).reshape(xh.shape), ou1.grad_action(xh, 2.5)) < 1e-5, L
-
-
-@pytest.mark.parametrize('hd', [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize('dims', [(37, 64, 128), (200, 256, 512), (64, 32, 64), (33, 128, 260)])
-def test_u1_heads_update_h_stream_equals_tile(hd, dims):
-    """Tuning `heads_h_stream` (the weights-stationary form of l2q_u1_heads_update_h, off by default):
-    same MFMA operands and k order as the tile kernel, so the accumulators are identical and the updated
-    field agrees to within a rare 16-bit rounding flip; the per-chain log-det is summed in a different
-    fixed order (fp32 rounding)."""
-    from l2hmc import _ops as ops, native
-    m, k, n = dims
-    g = torch.Generator().manual_seed(29)
-    z = torch.randn(m, k, generator=g).to(hd).cuda()
-    heads = {}
-    for nm in 'stq':
-        w = (torch.randn(n, k, generator=g) / k ** 0.5).to(hd).cuda()
-        b = (0.1 * torch.randn(n, generator=g)).cuda()
-        c = None if nm == 't' else (0.7 * torch.exp(0.3 * torch.randn(n, generator=g))).cuda()
-        heads[nm] = (w, b, c)
-    mask = (torch.rand(n, generator=g) < 0.5).float().cuda()
-    try:
-        for xupd in (False, True):
-            for forward in (True, False):
-                a0 = (torch.randn(m, n, generator=g) if not xupd
-                      else (2 * np.pi * torch.rand(m, n, generator=g) - np.pi)).cuda()
-                b0 = torch.randn(m, n, generator=g).cuda()
-                res = {}
-                for stream in (0, 1):
-                    assert native.set_tuning('heads_h_stream', stream) >= 0
-                    a = a0.clone()
-                    ld = ops.u1_heads_update_h_(z, heads, 0.9, a, b0, 0.17, forward,
-                                                mask=mask if xupd else None, complement=False)
-                    res[stream] = (a, ld)
-                # same accumulators; hipcc contracts the fp32 epilogue differently in the two kernels, so a
-                # 16-bit rounding of a head can flip where its argument sits on a tie: rare, 1 ulp16
-                d = res[0][0] - res[1][0]
-                if xupd:
-                    d = torch.remainder(d + np.pi, 2 * np.pi) - np.pi
-                ulp = 2.0 ** -10 if hd == torch.float16 else 2.0 ** -7
-                scale = max(1.0, float(res[0][0].abs().max()))
-                assert float(d.abs().max()) < 2 * ulp * scale, (xupd, forward, float(d.abs().max()))
-                assert float((d != 0).float().mean()) < 0.05, (xupd, forward)
-                dl = float((res[0][1] - res[1][1]).abs().max())
-                assert dl < (1e-5 * max(1.0, float(res[0][1].abs().max())) + 2 * ulp * 0.17) * n ** 0.5, dl
-    finally:
-        native.set_tuning('heads_h_stream', 2)
 
 
 @pytest.mark.parametrize('hd', [torch.float16, torch.bfloat16])

@@ -1,5 +1,5 @@
 """cfg-3 heads + update alone (8192 chains x 8192 entries, K = 256, fp16): v- and x-update per value of the
-`heads_h_stream` tuning (0 tile kernel, 1 stream kernel, 2 K-split stream kernel).  Interleaved rounds, median;
+`heads_h_stream` tuning (0 tile kernel, 2 K-split stream kernel).  Interleaved rounds, median;
 four rotating operand sets (the fields are 268 MB each: beyond the 256 MB L3)."""
 import os
 import sys
@@ -39,7 +39,7 @@ def run(xupd, reps=12):
     return (time.perf_counter() - t0) / reps * 1e6
 
 
-variants = [int(a) for a in sys.argv[1:]] or [0, 1, 2]
+variants = [int(a) for a in sys.argv[1:]] or [0, 2]
 res = {(v, x): [] for v in variants for x in (0, 1)}
 for rnd in range(5):
     for v in variants:
