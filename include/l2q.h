@@ -543,6 +543,22 @@ int l2q_act_fwd(const void* x, int act, long n, int elem_bytes, void* y, void* s
  * (network.py:447-451, 536-538) */
 int l2q_act_bwd(const void* dy, const void* y, int act, long n, int elem_bytes, void* dx,
                 void* stream);
+/* l2q_act_bwd over y[M][N] with the bias gradient formed in the same pass: dz = dy * act'(y) (swish:
+ * `y` holds the PRE-activation, as in l2q_act_bwd) and bgrad[n] += sum_m dz[m][n].  The column sums go
+ * through double-precision partials over the row blocks of l2q_colsum, in a fixed order: the result
+ * depends on (M, N) only, not on the launch grid.  dz holds the bits l2q_act_bwd gives and may alias
+ * dy.  elem_bytes 4 | 8; ws_bytes >= l2q_colsum_ws_bytes(M, N).  The training tape uses it for the
+ * un-pooled swish conv layers (M = chains x Ho x Wo rows of `cout` channels), where it replaces a copy
+ * of dy, l2q_act_bwd and l2q_colsum. */
+int l2q_act_bwd_sums(const void* dy, const void* y, int act, long M, int N, int elem_bytes, void* dz,
+                     void* bgrad, void* ws, size_t ws_bytes, void* stream);
+/* y = r16(act(r16(x))) element-wise on fp32 containers, r16 = round to half_type (L2Q_HALF_F16 |
+ * L2Q_HALF_BF16) and back: torch.autocast's two rounding points around an activation, with the
+ * conversion and the arithmetic of the l2q_gemm_h epilogues, so that a layer whose activation runs
+ * here rounds like one whose activation is fused.  The 16-bit training tape uses it for swish: the
+ * GEMM runs without its activation, the (16-bit valued) pre-activation stays on the tape.  y may
+ * alias x. */
+int l2q_act_fwd_r16(int half_type, const float* x, int act, long n, float* y, void* stream);
 /* out = alpha * a * b element-wise (nn.Dropout mask, network.py:540-541); out may alias a */
 int l2q_mul(const void* a, const void* b, double alpha, long n, int elem_bytes, void* out,
             void* stream);
@@ -585,7 +601,9 @@ int l2q_col2im_periodic_f64(const double* dcol, long sn, long sc, long sh, long 
                             int H, int W, int k, int channels_last_cols, double* dx,
                             void* stream);
 /* adjoint of l2q_maxpool_act_nhwc_f32: din[nb][H][W][C] overwritten (first maximum of each
- * window receives dout * act'(out)) */
+ * window receives dout * act'(out)).  swish is not invertible: it differentiates at the window
+ * maximum of `in` (the pre-activation, which the kernel finds anyway); `out` is then not read and
+ * may be NULL. */
 int l2q_maxpool_act_nhwc_bwd_f32(const float* dout, const float* out, const float* in, int nb,
                                  int H, int W, int C, int pool, int act, float* din,
                                  void* stream);

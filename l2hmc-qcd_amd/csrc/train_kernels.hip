@@ -7,32 +7,35 @@
 // cotangent kernel and the host replays the trajectory tape in reverse (dynamics/pytorch/
 // training.py).  Per-chain reductions (d eps) finish inside one workgroup in a fixed order.
 #include "l2q_common.hpp"
+#include "half_common.hpp"
 #include "u1_math.hpp"
 #include <limits>
 
 namespace l2q {
 
 // ------------------------------------------------------------------ element-wise helpers
+// act'(z) from the activation OUTPUT y (swish: from the PRE-activation z, passed as `yy`)
+template <typename T>
+__device__ __forceinline__ T act_grad(T yy, int act) {
+  switch (act) {
+    case L2Q_ACT_TANH: return (T)1 - yy * yy;
+    case L2Q_ACT_RELU: return yy > (T)0 ? (T)1 : (T)0;
+    case L2Q_ACT_LEAKY_RELU: return yy > (T)0 ? (T)1 : (T)0.01;
+    case L2Q_ACT_ELU: return yy > (T)0 ? (T)1 : yy + (T)1;           // y = e^z - 1 -> dy/dz = y + 1
+    case L2Q_ACT_SWISH: {                                           // `yy` holds the PRE-activation z
+      const T sg = (T)1 / ((T)1 + exp(-yy));
+      return sg * ((T)1 + yy * ((T)1 - sg));
+    }
+    default: return (T)1;
+  }
+}
+
 template <typename T>
 __global__ void act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, int act, long n,
                                T* __restrict__ dx) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const T yy = y[i];
-  T d;
-  switch (act) {
-    case L2Q_ACT_TANH: d = (T)1 - yy * yy; break;
-    case L2Q_ACT_RELU: d = yy > (T)0 ? (T)1 : (T)0; break;
-    case L2Q_ACT_LEAKY_RELU: d = yy > (T)0 ? (T)1 : (T)0.01; break;
-    case L2Q_ACT_ELU: d = yy > (T)0 ? (T)1 : yy + (T)1; break;     // y = e^z - 1 -> dy/dz = y + 1
-    case L2Q_ACT_SWISH: {                                           // `y` holds the PRE-activation z
-      const T sg = (T)1 / ((T)1 + exp(-yy));
-      d = sg * ((T)1 + yy * ((T)1 - sg));
-      break;
-    }
-    default: d = (T)1; break;
-  }
-  dx[i] = dy[i] * d;
+  dx[i] = dy[i] * act_grad<T>(y[i], act);
 }
 
 template <typename T>
@@ -171,6 +174,83 @@ __global__ __launch_bounds__(1024) void scaled_tanh_bwd_sums_kernel(
   }
 }
 
+// dz = dy * act'(y) with the bias gradient's column sums formed in the same pass: partial[r][n] = the sum
+// of dz over row block r (rows [r rpb, (r + 1) rpb), the partition of l2q_colsum), in double, in a fixed
+// order -- per thread over its rows, a butterfly over the row lanes of each wavefront, the 4 wavefronts
+// in order -- so the result depends on (M, N) only.  A thread owns VEC adjacent columns (one 16-byte
+// access when the row length allows: VEC = 4 fp32 / 2 fp64, else 1); blockDim = (CX column groups,
+// 256 / CX row lanes), CX a power of two <= 64 chosen by N so that a wavefront reads whole rows.  (256
+// threads per row block, not colsum's 1024: with 64 .. 256 rows per block a thread keeps several rows
+// to sum before the cross-lane reduction, which otherwise costs more than the pass over memory.)
+// IDX: element offsets in 32 bits when M N < 2^31.
+template <typename T, int VEC, typename IDX>
+__global__ __launch_bounds__(kBlock) void act_bwd_sums_kernel(
+    const T* __restrict__ dy, const T* __restrict__ y, int act, long M, int N, long rpb,
+    T* __restrict__ dz, double* __restrict__ partial) {
+  typedef T vec_t __attribute__((ext_vector_type(VEC)));
+  __shared__ double part[kBlock / 64][64 * VEC];
+  const int CX = blockDim.x, RY = blockDim.y;
+  const int cx = threadIdx.x, ry = threadIdx.y;
+  const int col0 = (blockIdx.x * CX + cx) * VEC;
+  const long r0 = (long)blockIdx.y * rpb;
+  long r1 = r0 + rpb; if (r1 > M) r1 = M;
+  double s[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) s[k] = 0.0;
+  if (col0 < N) {                                   // (N % VEC == 0: a group is inside the row or outside)
+    for (long m = r0 + ry; m < r1; m += RY) {
+      const IDX i = (IDX)m * (IDX)N + (IDX)col0;
+      const vec_t d = *reinterpret_cast<const vec_t*>(dy + i);
+      const vec_t yy = *reinterpret_cast<const vec_t*>(y + i);
+      vec_t o;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const T ok = d[k] * act_grad<T>(yy[k], act);
+        o[k] = ok;
+        s[k] += (double)ok;
+      }
+      *reinterpret_cast<vec_t*>(dz + i) = o;
+    }
+  }
+  // lanes l and l ^ off (off = CX, 2 CX, ..) hold the same column group: every lane ends with the same sum
+#pragma unroll
+  for (int k = 0; k < VEC; ++k)
+    for (int off = CX; off < 64; off <<= 1) s[k] += __shfl_xor(s[k], off, 64);
+  const int tid = ry * CX + cx, wave = tid >> 6, lane = tid & 63;
+  if (lane < CX) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) part[wave][lane * VEC + k] = s[k];
+  }
+  __syncthreads();
+  if (tid < CX * VEC) {
+    const int col = blockIdx.x * CX * VEC + tid;
+    if (col < N) {
+      double r = 0.0;
+      for (int w = 0; w < kBlock / 64; ++w) r += part[w][tid];
+      partial[(long)blockIdx.y * N + col] = r;
+    }
+  }
+}
+
+// y = r16(act(r16(x))): autocast's two rounding points around an activation (rnd / act_h of
+// half_common.hpp -- the conversions and the arithmetic of the gemm_h epilogues), fp32 containers.
+// Thread i takes the 16-byte group i of the first 4 n4 elements and element 4 n4 + i of the `rem` left over.
+template <typename HT, typename IDX>
+__global__ __launch_bounds__(kBlock) void act_fwd_r16_kernel(const float* __restrict__ x, int act, IDX n4,
+                                                             IDX rem, float* __restrict__ y) {
+  const IDX i = (IDX)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n4) {
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    float4 r;
+    r.x = rnd<HT>(act_h(rnd<HT>(v.x), act));
+    r.y = rnd<HT>(act_h(rnd<HT>(v.y), act));
+    r.z = rnd<HT>(act_h(rnd<HT>(v.z), act));
+    r.w = rnd<HT>(act_h(rnd<HT>(v.w), act));
+    reinterpret_cast<float4*>(y)[i] = r;
+  }
+  if (i < rem) y[4 * n4 + i] = rnd<HT>(act_h(rnd<HT>(x[4 * n4 + i]), act));
+}
+
 // ------------------------------------------------------------------ BatchNorm1d (train mode)
 // One workgroup per feature column (N is 16..256 here, M = chains).
 template <typename T>
@@ -280,9 +360,10 @@ __global__ __launch_bounds__(kBlock) void col2im_periodic_kernel(
   dx[b * sn + ci * sc + r * sh + c * sw] = acc;
 }
 
-// out = act(maxpool(in)) (NHWC, floor mode).  din[window argmax] = dout * act'(out); every
-// other input element (and the rows / columns the floor drops) gets 0.  First maximum in
-// row-major window order wins, like nn.MaxPool2d.
+// out = act(maxpool(in)) (NHWC, floor mode).  din[window argmax] = dout * act'(out) (swish:
+// act' at the window maximum of `in`, `out` is not read); every other input element (and the
+// rows / columns the floor drops) gets 0.  First maximum in row-major window order wins, like
+// nn.MaxPool2d.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_bwd_kernel(
     const T* __restrict__ dout, const T* __restrict__ out, const T* __restrict__ in,
@@ -305,15 +386,10 @@ __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_bwd_kernel(
       }
     if (ho * pool + bh == h && wo * pool + bw == w) {
       const long o = ((b * Ho + ho) * (long)Wo + wo) * C + c;
-      const T y = out[o];
-      T d;
-      switch (act) {
-        case L2Q_ACT_TANH: d = (T)1 - y * y; break;
-        case L2Q_ACT_RELU: d = y > (T)0 ? (T)1 : (T)0; break;
-        case L2Q_ACT_LEAKY_RELU: d = y > (T)0 ? (T)1 : (T)0.01; break;
-        case L2Q_ACT_ELU: d = y > (T)0 ? (T)1 : y + (T)1; break;
-        default: d = (T)1; break;
-      }
+      // swish is not invertible: its derivative is taken at the window maximum of `in` (the
+      // pre-activation); every other activation differentiates from its output
+      const T y = act == L2Q_ACT_SWISH ? best : out[o];
+      const T d = act_grad<T>(y, act);
       g = dout[o] * d;
     }
   }
@@ -531,9 +607,8 @@ int col2im_periodic_launch(const T* dcol, long sn, long sc, long sh, long sw, in
 template <typename T>
 int maxpool_act_nhwc_bwd_launch(const T* dout, const T* out, const T* in, int nb, int H, int W, int C,
                                 int pool, int act, T* din, hipStream_t st, const char* what) {
-  L2Q_REQUIRE_W(dout && out && in && din, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(dout && (out || act == L2Q_ACT_SWISH) && in && din, L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE_W(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
-  L2Q_REQUIRE_W(act != L2Q_ACT_SWISH, L2Q_EINVAL, "swish is not supported by the training path");
   const int Ho = H / pool, Wo = W / pool;
   L2Q_REQUIRE_W(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
   const long total = (long)nb * H * W * C;
@@ -542,6 +617,19 @@ int maxpool_act_nhwc_bwd_launch(const T* dout, const T* out, const T* in, int nb
   return check_launch(what);
 }
 #undef L2Q_REQUIRE_W
+
+template <typename T, int VEC>
+static void act_bwd_sums_launch(const T* dy, const T* y, int act, long M, int N, long rpb, long R, T* dz,
+                                double* partial, hipStream_t st) {
+  const int groups = N / VEC;
+  int cx = 64;
+  while (cx > 1 && cx / 2 >= groups) cx /= 2;
+  const dim3 blk(cx, kBlock / cx), grid((unsigned)cdiv(groups, cx), (unsigned)R);
+  if (M * (long)N < 0x7fffffffL)
+    hipLaunchKernelGGL((act_bwd_sums_kernel<T, VEC, int>), grid, blk, 0, st, dy, y, act, M, N, rpb, dz, partial);
+  else
+    hipLaunchKernelGGL((act_bwd_sums_kernel<T, VEC, long>), grid, blk, 0, st, dy, y, act, M, N, rpb, dz, partial);
+}
 
 extern "C" {
 
@@ -653,6 +741,51 @@ int l2q_scaled_tanh_bwd_sums(const void* ds, const void* s, const void* coeff, d
                          N, 1.0, 1, (T*)cgrad);
   });
   return check_launch("l2q_scaled_tanh_bwd_sums");
+}
+
+int l2q_act_bwd_sums(const void* dy, const void* y, int act, long M, int N, int elem_bytes, void* dz,
+                     void* bgrad, void* ws, size_t ws_bytes, void* stream) {
+  L2Q_REQUIRE(dy && y && dz && bgrad && ws, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(M > 0 && N > 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  L2Q_REQUIRE(ws_bytes >= l2q_colsum_ws_bytes(M, N), L2Q_EINVAL, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const long rpb = colsum_rows_per_block(M);
+  const long R = cdiv(M, rpb);
+  L2Q_DISPATCH_T(elem_bytes, {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (N % V == 0 && al16(dy) && al16(y) && al16(dz))
+      (act_bwd_sums_launch<T, V>)((const T*)dy, (const T*)y, act, M, N, rpb, R, (T*)dz, (double*)ws, st);
+    else
+      (act_bwd_sums_launch<T, 1>)((const T*)dy, (const T*)y, act, M, N, rpb, R, (T*)dz, (double*)ws, st);
+    hipLaunchKernelGGL(colsum_final_kernel<T>, dim3(grid1(N, 64)), dim3(kBlock), 0, st, (const double*)ws, R, N,
+                       1.0, 1, (T*)bgrad);
+  });
+  return check_launch("l2q_act_bwd_sums");
+}
+
+int l2q_act_fwd_r16(int half_type, const float* x, int act, long n, float* y, void* stream) {
+  L2Q_REQUIRE(x && y, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(n > 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half_type");
+  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = al16(x) && al16(y);
+  const long n4 = vec ? n / 4 : 0, rem = n - 4 * n4;
+  const long threads = n4 > rem ? n4 : rem;
+  L2Q_REQUIRE(cdiv(threads, kBlock) < 0x7fffffffL, L2Q_ESHAPE, "grid too large");
+#define L2Q_R16(HT)                                                                                         \
+  do {                                                                                                      \
+    if (n < 0x7fffffffL)                                                                                    \
+      hipLaunchKernelGGL((act_fwd_r16_kernel<HT, int>), dim3(grid1(threads)), dim3(kBlock), 0, st, x, act,  \
+                         (int)n4, (int)rem, y);                                                             \
+    else                                                                                                    \
+      hipLaunchKernelGGL((act_fwd_r16_kernel<HT, long>), dim3(grid1(threads)), dim3(kBlock), 0, st, x, act, \
+                         n4, rem, y);                                                                       \
+  } while (0)
+  if (half_type == L2Q_HALF_F16) L2Q_R16(_Float16); else L2Q_R16(__bf16);
+#undef L2Q_R16
+  return check_launch("l2q_act_fwd_r16");
 }
 
 int l2q_bn_train_fwd(const void* x, const void* gamma, const void* beta, double eps,

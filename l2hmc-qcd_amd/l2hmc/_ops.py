@@ -1021,6 +1021,34 @@ def act_bwd(dy: torch.Tensor, y: torch.Tensor, act: Optional[str],
     return dy
 
 
+def act_fwd_r16(x: torch.Tensor, act: Optional[str], half: torch.dtype) -> torch.Tensor:
+    """r16(act(r16(x))) on fp32 containers (new tensor), r16 = round to `half` and back: autocast's two
+    rounding points around an activation, rounded like the fused epilogue of gemm_h."""
+    if x.dtype != torch.float32 or half not in HALF_TYPES:
+        raise N.L2QError(f'act_fwd_r16: fp32 containers and a 16-bit type, got {x.dtype} / {half}')
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    N.call('l2q_act_fwd_r16', HALF_TYPES[half], x, N.ACT[act], x.numel(), y)
+    return y
+
+
+def act_bwd_sums(dy: torch.Tensor, y: torch.Tensor, act: Optional[str], bgrad: torch.Tensor,
+                 from_preact: bool = False) -> torch.Tensor:
+    """dz = dy * act'(z) over [m, n] (new tensor) and `bgrad += colsum(dz)` in one pass; `y` and
+    `from_preact` as in act_bwd."""
+    if (act == 'swish') != bool(from_preact):
+        raise ValueError("act_bwd_sums: swish differentiates from the pre-activation (from_preact=True), "
+                         "every other activation from its output")
+    m, n = dy.shape
+    if y.shape != dy.shape or y.dtype != dy.dtype or bgrad.dtype != dy.dtype or bgrad.numel() != n:
+        raise N.L2QError(f'act_bwd_sums: dy {tuple(dy.shape)} {dy.dtype}, y {tuple(y.shape)} {y.dtype}, '
+                         f'bgrad {tuple(bgrad.shape)} {bgrad.dtype}')
+    dz = torch.empty_like(dy)
+    ws = N.workspace(int(N.load().l2q_colsum_ws_bytes(m, n)), dy.device)
+    N.call('l2q_act_bwd_sums', dy, y, N.ACT[act], m, n, dy.element_size(), dz, bgrad, ws, ws.numel())
+    return dz
+
+
 def mul(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     out = torch.empty_like(a) if out is None else out
@@ -1173,7 +1201,16 @@ def conv2d_periodic_gemm_train(x: torch.Tensor, layout: str, w: torch.Tensor, b:
     N.call('l2q_im2col_periodic_' + sfx, x, *strides, nb, C, H, W, k, int(clast), col)
     pool = max(int(pool), 1)
     wk = (w.permute(0, 2, 3, 1) if clast else w).reshape(cout, Kc).contiguous()
-    if half is not None and pool == 1 and act is not None:
+    pre = pool == 1 and act == 'swish'
+    out = None
+    if pre:
+        # swish is not invertible: the tape keeps the pre-activation z (16-bit valued under `half`), the
+        # activation runs as a pass of its own
+        y = gemm(col, wk, b.contiguous(), act=None)
+        if half is not None:
+            y = act_fwd_r16(y, None, half)          # rounding point between the convolution and its activation
+        out = act_fwd(y, act) if half is None else act_fwd_r16(y, act, half)
+    elif half is not None and pool == 1 and act is not None:
         # rounding point between the convolution and its activation
         y = act_fwd(gemm(col, wk, b.contiguous(), act=None).to(half).float(), act).to(half).float()
     else:
@@ -1181,9 +1218,9 @@ def conv2d_periodic_gemm_train(x: torch.Tensor, layout: str, w: torch.Tensor, b:
         if half is not None:
             y = y.to(half).float()
     ctx = {'col': col, 'strides': strides, 'dims': (nb, C, H, W, k, cout), 'pool': pool,
-           'act': act, 'y': y, 'clast': clast, 'wk': wk}
+           'act': act, 'y': y, 'pre': pre, 'clast': clast, 'wk': wk}
     if pool == 1:
-        out = y.reshape(nb, Ho, Wo, cout)
+        out = (out if pre else y).reshape(nb, Ho, Wo, cout)
     else:
         out = torch.empty((nb, Ho // pool, Wo // pool, cout), dtype=x.dtype, device=x.device)
         N.call('l2q_maxpool_act_nhwc_' + sfx, y, nb, Ho, Wo, cout, pool, N.ACT[act], out)
@@ -1199,19 +1236,23 @@ def conv2d_periodic_gemm_bwd(ctx: dict, dout: torch.Tensor, w: torch.Tensor, dw:
     nb, C, H, W, k, cout = ctx['dims']
     Ho, Wo, Kc = H + k - 1, W + k - 1, C * k * k
     pool, act = ctx['pool'], ctx['act']
-    if act == 'swish':
-        # the fused conv kernels keep the activation OUTPUT only; swish' needs the pre-activation
-        raise NotImplementedError('conv backward with swish: the conv tape holds post-activations')
     sfx = _conv_suffix('conv2d_periodic_gemm_bwd', dout, ctx['y'], w, dw, db)
     dout = dout.contiguous()
     if pool > 1:
+        # ctx['y'] is the pre-pool GEMM output: swish differentiates at its window maximum
         dy = torch.empty_like(ctx['y'])
         N.call('l2q_maxpool_act_nhwc_bwd_' + sfx, dout, ctx['out'], ctx['y'], nb, Ho, Wo, cout, pool,
                N.ACT[act], dy)
+    elif act == 'swish':
+        if not ctx.get('pre'):
+            raise N.L2QError('conv2d_periodic_gemm_bwd: the swish tape must hold the pre-activation')
+        # the activation's VJP and the bias gradient in one pass over (dout, z)
+        dy = act_bwd_sums(dout.reshape(nb * Ho * Wo, cout), ctx['y'], act, db, from_preact=True)
     else:
         dy = act_bwd(dout.reshape(nb * Ho * Wo, cout).clone(), ctx['y'], act)
     dy = dy.reshape(nb * Ho * Wo, cout)
-    colsum_(db, dy)
+    if pool > 1 or act != 'swish':
+        colsum_(db, dy)
     clast = ctx.get('clast', False)
     dwk = gemm(t2d(dy), t2d(ctx['col']))                             # dW = dy^T col, [cout, Kc]
     if clast:                                                        # (i, j, ci) -> (ci, i, j)

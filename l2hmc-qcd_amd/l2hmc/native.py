@@ -115,6 +115,8 @@ SIGNATURES = {
     'l2q_u1_xstep_f32': (I, [P, P, P, I, D, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, D, P, P, P, I, I, P, P]),
     'l2q_act_fwd': (I, [P, I, L, I, P, P]),
     'l2q_act_bwd': (I, [P, P, I, L, I, P, P]),
+    'l2q_act_bwd_sums': (I, [P, P, I, L, I, I, P, P, P, Z, P]),
+    'l2q_act_fwd_r16': (I, [I, P, I, L, P, P]),
     'l2q_mul': (I, [P, P, D, L, I, P, P]),
     'l2q_axpy_rows': (I, [P, P, I, L, I, P, P]),
     'l2q_colsum': (I, [P, P, L, I, D, I, I, P, P, Z, P]),

@@ -385,20 +385,28 @@ class ConvStack(nn.Module):
             x = ops.transpose(x.reshape(nb, H * W, C), nb, H * W, C)
         flat = x.reshape(nb, -1).contiguous()
         lin = self.layers[self.linear_index]
+        # swish is not invertible: the trailing Linear runs without its fused activation and the tape
+        # keeps its pre-activation (ctx['pre']) next to the output
+        swish = self.act == 'swish'
+        fused = None if swish else self.act
         if half is not None:
             y = ops.gemm_h(flat, lin.weight.detach().to(half).contiguous(),
-                           lin.bias.detach().to(half).float().contiguous(), act=self.act,
+                           lin.bias.detach().to(half).float().contiguous(), act=fused,
                            out_dtype=torch.float32)
         else:
-            y = ops.gemm(flat, lin.weight.detach(), lin.bias.detach(), act=self.act)
-        return y, {'convs': ctxs, 'nhwc_shape': nhwc_shape, 'flat': flat, 'y': y}
+            y = ops.gemm(flat, lin.weight.detach(), lin.bias.detach(), act=fused)
+        pre = None
+        if swish:
+            pre = y
+            y = ops.act_fwd(pre, 'swish') if half is None else ops.act_fwd_r16(pre, 'swish', half)
+        return y, {'convs': ctxs, 'nhwc_shape': nhwc_shape, 'flat': flat, 'y': y, 'pre': pre}
 
     def backward(self, ctx: dict, dy: Tensor) -> Tensor:
         """Accumulates the layers' .grad; returns dL/dx [nb, C, T, X]."""
         lin = self.layers[self.linear_index]
-        if self.act == 'swish':
-            raise NotImplementedError('ConvStack.backward with swish: the tape holds post-activations')
-        dpre = ops.act_bwd(dy.contiguous().clone(), ctx['y'], self.act)
+        pre = ctx.get('pre') is not None
+        dpre = ops.act_bwd(dy.contiguous().clone(), ctx['pre'] if pre else ctx['y'], self.act,
+                           from_preact=pre)
         d = _linear_bwd(dpre, ctx['flat'], lin.weight, lin.bias)
         nb = d.shape[0]
         if ctx['nhwc_shape'] is not None:
@@ -846,9 +854,6 @@ class LeapfrogLayer(nn.Module):
         # swish is not invertible: its derivative needs the pre-activation, so for swish the
         # layers run without the fused activation and the tape keeps z_pre next to act(z_pre)
         swish = self.act == 'swish'
-        if swish and conv_ctx is not None:
-            raise NotImplementedError('training: swish inside the conv stack (its kernels fuse the '
-                                      'activation with the max-pool) -- use another activation_fn')
         fused = None if swish else self.act
         nw_ = self._nat['w'] if self.native_active() else None     # inputs / outputs in native order
         imgs = self.sliced_train_input_images(nb) if (sliced_input_exp is not None and nw_ is not None
@@ -940,8 +945,6 @@ class LeapfrogLayer(nn.Module):
         on the fp32 master weights, in fp32 -- the reference runs those products in 16 bit; the difference is
         below its own fp16-vs-fp32 distance, which is what the tests pin."""
         il = self.input_layer
-        if self.act == 'swish':
-            raise NotImplementedError('half-precision training: swish keeps pre-activations; use another activation_fn')
         hd = self.half_dtype
         nb = x.shape[0]
         h = self._half_train_weights()
@@ -951,12 +954,33 @@ class LeapfrogLayer(nn.Module):
         else:
             xf = x.reshape(nb, -1).float().contiguous()
         vf = v.reshape(nb, -1).float().contiguous()
-        z = ops.gemm_h(xf, h['wx'], h['bx'], a2=vf, w2=h['wv'], bias2=h['bv'], act=self.act)
-        acts = [z.float()]
-        for hw, hb in h['hidden']:
-            z = ops.gemm_h(z, hw, hb, act=self.act)
-            acts.append(z.float())
-        ctx: dict = {'xf': xf, 'vf': vf, 'acts': acts, 'pre': None, 'conv': conv_ctx,
+        # swish is not invertible: the GEMMs run without their fused activation, the 16-bit valued
+        # pre-activations stay on the tape (fp32 containers) and the activation is a pass of its own with
+        # the epilogue's two rounding points
+        swish = self.act == 'swish'
+        f32 = torch.float32
+        if swish:
+            # the input layer as autocast runs it: xlayer(x) and vlayer(v) rounded separately, their sum
+            # rounded (act_fwd_r16 without an activation is r16).  The fused two-operand GEMM rounds the
+            # sum once; the last-bit differences in z move swish'(z) enough to put the step's gradients
+            # ten times further from the reference's 16-bit step than that step is from its fp32 one.
+            zx = ops.gemm_h(xf, h['wx'], h['bx'], act=None, out_dtype=f32)
+            zv = ops.gemm_h(vf, h['wv'], h['bv'], act=None, out_dtype=f32)
+            z = ops.act_fwd_r16(ops.add_(zx, zv), None, hd)
+            pre = [z]
+            acts = [ops.act_fwd_r16(z, 'swish', hd)]
+            for hw, hb in h['hidden']:
+                z = ops.gemm_h(acts[-1], hw, hb, act=None, out_dtype=f32)
+                pre.append(z)
+                acts.append(ops.act_fwd_r16(z, 'swish', hd))
+        else:
+            pre = None
+            z = ops.gemm_h(xf, h['wx'], h['bx'], a2=vf, w2=h['wv'], bias2=h['bv'], act=self.act)
+            acts = [z.float()]
+            for hw, hb in h['hidden']:
+                z = ops.gemm_h(z, hw, hb, act=self.act)
+                acts.append(z.float())
+        ctx: dict = {'xf': xf, 'vf': vf, 'acts': acts, 'pre': pre, 'conv': conv_ctx,
                      'xshape': tuple(x.shape), 'vshape': tuple(v.shape), 'native': False}
         zf = acts[-1]
         p = float(self.net_config.dropout_prob)
@@ -975,7 +999,6 @@ class LeapfrogLayer(nn.Module):
             zf = zf.to(hd).float()
         ctx['z'] = zf
         z16 = zf.to(hd)
-        f32 = torch.float32
         s = ops.gemm_h(z16, h['ws'], h['bs'], coeff=h['cs'], scale=self.nw.s, act='tanh', out_dtype=f32)
         t = ops.gemm_h(z16, h['wt'], h['bt'], scale=self.nw.t, out_dtype=f32)
         q = ops.gemm_h(z16, h['wq'], h['bq'], coeff=h['cq'], scale=self.nw.q, act='tanh', out_dtype=f32)
