@@ -64,8 +64,8 @@ int l2q_version(void);
  * (The Python binding applies L2Q_TUNING="key=value,..." from the environment when it loads the library.) */
 int l2q_set_tuning(const char* key, int value);
 /* Name (template instantiation as rocprofv3 prints it, without the l2q:: prefix) of the device
- * kernel that `entry` ("l2q_su3_force", "l2q_su3_force_kick", "l2q_su3_plaq_reduce",
- * "l2q_vnet_heads_vupdate[_pair]_f64", "l2q_gemm_f64": kernel family only) dispatches
+ * kernel that `entry` ("l2q_su3_force", "l2q_su3_force_kick", "l2q_su3_plaq_reduce", "l2q_su3_clover_reduce",
+ * "l2q_su3_flow_stage": its launches joined by " + ", "l2q_vnet_heads_vupdate[_pair]_f64", "l2q_gemm_f64": kernel family only) dispatches
  * for a T x X x Y x Z lattice under the current tuning; "" for entry points with a single
  * kernel.  entry "l2q_gemm_h" with (T, X, Y) = (M, N, K): "hipblaslt" when that plain 16-bit layer goes to the
  * vendor library (gemm_lt.hip: library present, shape taken), "" when it runs on this build's kernels.  Lets a profile (rocprofv3 --pmc) be matched to the build that is running. */
@@ -190,6 +190,32 @@ int l2q_su3_assemble_tah(const double* normals, void* vn, long nfields, long V, 
  * (checkSU, utils.py:376-391): out[c][0] = sqrt(mean/20), out[c][1] = sqrt(max/20). */
 int l2q_su3_check_su(const void* xn, int nb, long V, double* out, void* ws, size_t ws_bytes,
                      void* stream);
+
+/* ---------------------------------------------------------------- Wilson flow and clover observables */
+/* Clover sums per chain, raw (before 1/V and 1/4 pi^2): with F_{mu nu}(x) = TAH(Q_{mu nu}(x)) / 4, Q_{mu nu} the sum
+ * of the four counter-clockwise plaquette leaves of the (mu, nu) plane that start and end at x,
+ *   out[c][0] = sum_x sum_{mu<nu} -tr F_{mu nu} F_{mu nu}            (E = out[c][0] / V >= 0)
+ *   out[c][1] = sum_x -tr(F01 F23 - F02 F13 + F03 F12)               (Q = out[c][1] / (4 pi^2))
+ *   out[c][2] = sum_x sum_{mu<nu} Re tr P_{mu nu}(x)                 (= out[c][0] of l2q_su3_plaq_reduce)
+ * Anchor of sign and normalisation: uniform abelian fluxes n01, n23 along diag(1, -1, 0) give
+ * Q = 2 n01 n23 (sin phi01 / phi01)(sin phi23 / phi23), E = 2 (sin^2 phi01 + sin^2 phi23).
+ * Takes any lattice (extents 1 and 2 included); where X Y Z is whole 64-site tiles (8^4, 16^4) a slice-resident
+ * kernel keeps three time slices of a tile in LDS.  ws as for l2q_su3_plaq_reduce.  Algorithmic traffic: 576 B
+ * per (chain, site). */
+int l2q_su3_clover_reduce(const void* xn, int nb, int T, int X, int Y, int Z, double* out,
+                          void* ws, size_t ws_bytes, void* stream);
+/* One low-storage stage of the Wilson flow (always the plaquette action):
+ *   P_out = P_in + c * TAH(U A)  (A = the 6 staples of l2q_su3_force; p_in NULL = 0),   X_out = exp(s * P_out) X_in
+ * on all links, out of place: x_out != x_in, p_out is required and may alias p_in.  Two launches (the force kick
+ * at beta = 3 into p_out, then the unmasked l2q_su3_expm_mul) on every lattice. */
+int l2q_su3_flow_stage(const void* x_in, const void* p_in, double c, double s, void* p_out, void* x_out,
+                       int nb, int T, int X, int Y, int Z, void* stream);
+/* One third-order step of size eps of dV/dt = Z(V) V, Z = -TAH(V A) (Luescher, arXiv:1006.4518):
+ * three stages with (P_in, c, s) = (0, 1, -eps/4), (P, -32/17, 17 eps/36), (P, 27/17, -17 eps/36), the links
+ * going x_in -> x_out -> ws_x -> x_out.  x_in is only read; ws_p and ws_x are scratch fields of the links' size;
+ * x_in, x_out, ws_x must be three different fields. */
+int l2q_su3_flow_step(const void* x_in, void* x_out, void* ws_p, void* ws_x, double eps, int nb, int T, int X,
+                      int Y, int Z, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

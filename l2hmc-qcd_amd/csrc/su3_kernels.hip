@@ -906,6 +906,8 @@ void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef
 // gemm_lt.hip
 bool gemm_h_lt_shape(int M, int N, long K);
 bool gemm_h_lt_available();
+// su3_flow.hip
+bool clover_slice_applicable(const Dims& d);
 // su3_force_plaq.hip
 bool force_plaq_applicable(const Dims& d);
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);
@@ -981,6 +983,16 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
       snprintf(buf, buf_bytes, "su3_force_slice_kernel<%s, %d, %d, %d>", kick ? "true" : "false", fs,
                kick ? 2 : 0, kick ? 1 : kLptPlain);
     else snprintf(buf, buf_bytes, "su3_force_tile_kernel<%s, 2>", kick ? "true" : "false");
+  } else if (!strcmp(entry, "l2q_su3_clover_reduce")) {
+    const Dims dd{T, X, Y, Z, T * X * Y * Z};
+    snprintf(buf, buf_bytes, "%s", clover_slice_applicable(dd) ? "su3_clover_slice_kernel" : "su3_clover_kernel");
+  } else if (!strcmp(entry, "l2q_su3_flow_stage")) {
+    // the kick of l2q_su3_force_kick_to (out of place: only the thread-per-link kernel has that form, the others
+    // follow a copy), then the unmasked x-update
+    char kick[128];
+    const int rc = l2q_kernel_name("l2q_su3_force_kick", T, X, Y, Z, kick, sizeof(kick));
+    if (rc != L2Q_OK) return rc;
+    snprintf(buf, buf_bytes, "%s + su3_expm_mul_kernel<false, false>", kick);
   } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64")) {
     snprintf(buf, buf_bytes, "heads_sliced_kernel");
   } else if (!strncmp(entry, "l2q_vnet_heads_vupdate", 22)) {

@@ -252,6 +252,36 @@ def su3_check_su_n(xn: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def su3_clover_sums_n(xn: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
+    """[nb, 3] raw clover sums over sites: (sum_{mu<nu} -tr F F, -tr(F01 F23 - F02 F13 + F03 F12),
+    sum_{mu<nu} Re tr P); E = [:, 0] / V, Q = [:, 1] / (4 pi^2) (see l2q.h)."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    out = torch.empty((nb, 3), dtype=torch.float64, device=xn.device)
+    ws = _ws(nb, T * X * Y * Z * 36, xn.device)
+    N.call('l2q_su3_clover_reduce', xn, nb, T, X, Y, Z, out, ws, ws.numel())
+    return out
+
+
+def su3_flow_stage_n(xn: torch.Tensor, pn: Optional[torch.Tensor], c: float, s: float, lat: Sequence[int],
+                     p_out: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None):
+    """One low-storage stage of the Wilson flow: p_out = pn + c TAH(U A) (pn None = 0), x_out = exp(s p_out) xn.
+    Returns (p_out, x_out); p_out may be pn itself, x_out is never xn."""
+    T, X, Y, Z = (int(i) for i in lat)
+    p_out = torch.empty_like(xn) if p_out is None else p_out
+    x_out = torch.empty_like(xn) if x_out is None else x_out
+    N.call('l2q_su3_flow_stage', xn, pn, float(c), float(s), p_out, x_out, xn.shape[0], T, X, Y, Z)
+    return p_out, x_out
+
+
+def su3_flow_step_n(xn: torch.Tensor, x_out: torch.Tensor, ws_p: torch.Tensor, ws_x: torch.Tensor, eps: float,
+                    lat: Sequence[int]) -> torch.Tensor:
+    """One third-order Wilson-flow step of size eps: xn (only read) -> x_out; ws_p, ws_x are scratch fields."""
+    T, X, Y, Z = (int(i) for i in lat)
+    N.call('l2q_su3_flow_step', xn, x_out, ws_p, ws_x, float(eps), xn.shape[0], T, X, Y, Z)
+    return x_out
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

@@ -9,7 +9,7 @@ gets the force by autograd; here ``action``, ``plaqs`` and the charges come from
 from __future__ import annotations
 
 import logging
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -48,6 +48,15 @@ class PlaqSums:
     def __init__(self, sums: Tensor):
         self.re = sums[:, 0].contiguous()
         self.im = sums[:, 1].contiguous()
+
+
+class Clover(NamedTuple):
+    """Per-chain clover observables, [nb] float64 each: energy density ``E = -(1/V) sum_x sum_{mu<nu} tr F F``,
+    topological charge ``Q = -(1/4 pi^2) sum_x tr(F01 F23 - F02 F13 + F03 F12)`` and the plaquette energy
+    density ``Eplaq = 36 (1 - plaqs)``, from ONE pass of `l2q_su3_clover_reduce`."""
+    E: Tensor
+    Q: Tensor
+    Eplaq: Tensor
 
 
 def _site_sum(w: Tensor) -> Tensor:
@@ -98,6 +107,87 @@ class LatticeSU3(Lattice):
             return ops.su3_force_n(xn, b, self._lattice_shape)
         f = ops.su3_force_n(xn, b * (1.0 - 8.0 * self.c1), self._lattice_shape)
         return ops.su3_rect_force_add_n(xn, b * self.c1 / 3.0, f, self._lattice_shape)
+
+    # ------------------------------------------------------------ Wilson flow and clover observables
+    def clover_n(self, xn: Tensor) -> Clover:
+        s = ops.su3_clover_sums_n(xn, self._lattice_shape)
+        return Clover(E=s[:, 0] / self.volume, Q=s[:, 1] / (4 * np.pi ** 2),
+                      Eplaq=36.0 - (2.0 / self.volume) * s[:, 2])
+
+    def clover(self, x: Tensor) -> Clover:
+        """Clover energy density, topological charge and plaquette energy density of x (reference layout)."""
+        self._no_grad(x, 'clover')
+        return self.clover_n(self.pack(x))
+
+    def topological_charge(self, x: Tensor) -> Tensor:
+        return self.clover(x).Q
+
+    def energy_density(self, x: Tensor, kind: str = 'clover') -> Tensor:
+        if kind not in ('clover', 'plaq'):
+            raise ValueError(f"energy_density: kind must be 'clover' or 'plaq', got {kind!r}")
+        c = self.clover(x)
+        return c.E if kind == 'clover' else c.Eplaq
+
+    @staticmethod
+    def _no_grad(x: Tensor, what: str) -> None:
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise RuntimeError(f'LatticeSU3.{what}: no autograd through the Wilson flow / clover observables')
+
+    @staticmethod
+    def _flow_steps(t: float, eps: float) -> int:
+        if not eps > 0 or t < 0:
+            raise ValueError(f'flow: need eps > 0 and t >= 0, got t = {t}, eps = {eps}')
+        n = round(t / eps)
+        if abs(t / eps - n) > 1e-9:
+            raise ValueError(f'flow: t / eps must be an integer, got t = {t}, eps = {eps}')
+        return int(n)
+
+    def _flow_iter(self, xn: Tensor, nsteps: int, eps: float):
+        """yields the native field after 1, 2, ..., nsteps steps (a buffer that the step after next overwrites);
+        three ping-pong fields and the generator field are allocated once, xn is never written"""
+        bufs = [torch.empty_like(xn) for _ in range(2)]
+        ws_x, ws_p = torch.empty_like(xn), torch.empty_like(xn)
+        cur = xn
+        for k in range(nsteps):
+            out = bufs[k & 1]
+            ops.su3_flow_step_n(cur, out, ws_p, ws_x, eps, self._lattice_shape)
+            cur = out
+            yield cur
+
+    def flow_n(self, xn: Tensor, nsteps: int, eps: float = 0.01) -> Tensor:
+        """`nsteps` third-order steps of size eps of the Wilson flow dV/dt = -TAH(V A) V (always the plaquette
+        action, whatever c1) on a native field; returns a new field (xn itself for nsteps = 0)."""
+        cur = xn
+        for cur in self._flow_iter(xn, int(nsteps), float(eps)):
+            pass
+        return cur
+
+    def flow(self, x: Tensor, t: float, eps: float = 0.01) -> Tensor:
+        """x flowed to time t in round(t / eps) steps; reference layout in and out."""
+        self._no_grad(x, 'flow')
+        n = self._flow_steps(float(t), float(eps))
+        return self.unpack(self.flow_n(self.pack(x), n, eps))
+
+    def flow_observables(self, x: Tensor, t: float, eps: float = 0.01, every: int = 1) -> dict[str, Tensor]:
+        """Clover observables along the flow: 't' [n+1], 'E', 'Eplaq', 'Q', 't2E' [n+1, nb], measured every
+        `every` steps (row 0 = unflowed).  Packs once and stays in the native layout between steps."""
+        self._no_grad(x, 'flow_observables')
+        nsteps = self._flow_steps(float(t), float(eps))
+        every = int(every)
+        if every < 1 or nsteps % every != 0:
+            raise ValueError(f'flow_observables: every = {every} must divide the {nsteps} steps')
+        xn = self.pack(x)
+        ts, rows = [0.0], [self.clover_n(xn)]
+        for k, cur in enumerate(self._flow_iter(xn, nsteps, float(eps)), start=1):
+            if k % every == 0:
+                ts.append(k * float(eps))
+                rows.append(self.clover_n(cur))
+        tt = torch.tensor(ts, dtype=torch.float64, device=xn.device)
+        out = {'t': tt}
+        for name in Clover._fields:
+            out[name] = torch.stack([getattr(r, name) for r in rows])
+        out['t2E'] = tt[:, None] ** 2 * out['E']
+        return out
 
     # ------------------------------------------------------------ reference API
     def coeffs(self, beta: Tensor) -> dict[str, Tensor]:
@@ -249,7 +339,10 @@ class LatticeSU3(Lattice):
         return self.unpack(self.grad_action_n(self.pack(x), beta))
 
     def calc_metrics(self, x: Tensor, beta: Optional[Tensor] = None,
-                     xinit: Optional[Tensor] = None) -> dict[str, Tensor]:
+                     xinit: Optional[Tensor] = None, flow_time: Optional[float] = None,
+                     flow_eps: float = 0.01) -> dict[str, Tensor]:
+        """The reference's metrics; with `flow_time` also the clover charge and t^2 E of x flowed to that time
+        ('Qflow', 't2E', and 'dQflow' = |Qflow(x) - Qflow(xinit)| when xinit is given)."""
         w = self.plaq_sums(x)
         q = self._charges(w)
         metrics = {'plaqs': self._plaqs(w), 'sinQ': q.sinQ, 'intQ': q.intQ}
@@ -265,4 +358,11 @@ class LatticeSU3(Lattice):
             metrics.update({'dplaqs': (metrics['plaqs'] - self._plaqs(w_)).abs(),
                             'dQint': (q.intQ - q_.intQ).abs(),
                             'dQsin': (q.sinQ - q_.sinQ).abs()})
+        if flow_time is not None:
+            n = self._flow_steps(float(flow_time), float(flow_eps))
+            c = self.clover_n(self.flow_n(self.pack(x), n, flow_eps))
+            metrics.update({'Qflow': c.Q, 't2E': float(flow_time) ** 2 * c.E})
+            if xinit is not None:
+                c_ = self.clover_n(self.flow_n(self.pack(xinit), n, flow_eps))
+                metrics['dQflow'] = (c.Q - c_.Q).abs()
         return metrics

@@ -25,8 +25,45 @@ def timeit(fn, iters=10, warm=3):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
+def torch_clover_sums(x):
+    """The clover sums of l2q_su3_clover_reduce written with torch ops on the reference layout
+    x[nb, 4, T, X, Y, Z, 3, 3] (roll + matmul: what a user without the kernel would write) -- the baseline of
+    the `su3_clover_reduce` row under --torch-clover."""
+    def sh(f, mu, n=1):
+        return torch.roll(f, -n, dims=mu + 1)
+
+    def adj(m):
+        return m.conj().transpose(-1, -2)
+
+    def tr(m):
+        return m.diagonal(dim1=-2, dim2=-1).sum(-1)
+
+    def field(mu, nu):
+        um, un = x[:, mu], x[:, nu]
+        um_m, un_n = sh(um, mu, -1), sh(un, nu, -1)
+        l1 = um @ sh(un, mu) @ adj(sh(um, nu)) @ adj(un)
+        q = l1 + un @ adj(sh(um_m, nu)) @ adj(sh(un, mu, -1)) @ um_m
+        q = q + adj(um_m) @ adj(sh(sh(un, mu, -1), nu, -1)) @ sh(um_m, nu, -1) @ un_n
+        q = q + adj(un_n) @ sh(um, nu, -1) @ sh(sh(un, mu), nu, -1) @ adj(um)
+        a = 0.5 * (q - adj(q))
+        a = a - (tr(a) / 3.0)[..., None, None] * torch.eye(3, dtype=x.dtype, device=x.device)
+        return 0.25 * a, tr(l1).real
+    nb = x.shape[0]
+    e = q = p = 0.0
+    for k, (a, b), sign in ((1, (2, 3), 1.0), (2, (1, 3), -1.0), (3, (1, 2), 1.0)):
+        f, p1 = field(0, k)
+        g, p2 = field(a, b)
+        e = e - tr(f @ f).real.reshape(nb, -1).sum(-1) - tr(g @ g).real.reshape(nb, -1).sum(-1)
+        q = q - sign * tr(f @ g).real.reshape(nb, -1).sum(-1)
+        p = p + p1.reshape(nb, -1).sum(-1) + p2.reshape(nb, -1).sum(-1)
+    return torch.stack([e, q, p], 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--torch-clover', action='store_true',
+                    help='also time the clover sums written with torch roll / matmul and compare the outputs')
+    ap.add_argument('--flow-only', action='store_true', help='only the Wilson-flow / clover rows')
     ap.add_argument('--nb', type=int, default=256)
     ap.add_argument('--L', type=int, nargs=4, default=[8, 8, 8, 8])
     ap.add_argument('--gemm', action='store_true')
@@ -50,6 +87,30 @@ def main():
         print(f'{name:34s} {t*1e3:8.3f} ms  {gbs:8.1f} GB/s  ({gbs/8000*100:5.1f}% of 8 TB/s)'
               + (f'  {tf:6.2f} TFLOP/s' if flop_per_site else ''), flush=True)
 
+    # Wilson flow / clover observables: the clover pass reads the links once (576 B / site, 72 3x3 products); a flow
+    # stage is the force kick (reads X and P, writes P) and the x-update (reads P and X, writes X): 3456 B / site
+    rec('su3_clover_reduce', timeit(lambda: ops.su3_clover_sums_n(xn, L)), 576, 72 * 216)
+    if a.torch_clover:
+        xr = ops.su3_unpack(xn, L)
+        t = timeit(lambda: torch_clover_sums(xr), iters=3, warm=1)
+        got, want = ops.su3_clover_sums_n(xn, L), torch_clover_sums(xr)
+        rel = float(((got - want).abs() / want.abs().clamp(min=float(V))).max())
+        rec('  torch roll/matmul clover', t, 576, 72 * 216)
+        print(f'{"  kernel vs torch clover":34s} max |d| / max(|sum|, V) = {rel:.2e}', flush=True)
+        del xr, want
+    p2, x2 = torch.empty_like(xn), torch.empty_like(xn)
+    cc, ss = -32.0 / 17.0, 17.0 / 36.0 * 0.01
+    rec('su3_flow_stage', timeit(lambda: ops.su3_flow_stage_n(xn, vn, cc, ss, L, p_out=p2, x_out=x2)), 3456)
+
+    def two_launch():
+        ops.su3_force_kick_n(xn, 3.0, cc, p2, L, v_src=vn)
+        ops.su3_expm_mul_n(xn, p2, ss, out=x2)
+    rec('  force_kick_to + expm_mul', timeit(two_launch), 3456)
+    x3 = torch.empty_like(xn)
+    rec('su3_flow_step (3 stages)', timeit(lambda: ops.su3_flow_step_n(xn, x2, p2, x3, 0.01, L)), 2880 + 2 * 3456)
+    del p2, x2, x3
+    if a.flow_only:
+        return
     rec('su3_plaq_reduce', timeit(lambda: ops.su3_plaq_sums_n(xn, L)), 576, 2800)
     native.set_tuning('xcd_swizzle', 0)
     rec('su3_plaq_reduce noswz', timeit(lambda: ops.su3_plaq_sums_n(xn, L)), 576, 2800)
