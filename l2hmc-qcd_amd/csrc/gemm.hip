@@ -1142,23 +1142,15 @@ template <typename T>
 int conv_gemm_launch(const T* in, long sn, long sc, long sh, long sw, int nb, int C, int H, int W,
                      int k, const T* weight, int channels_last_cols, const T* bias, int cout, int act,
                      T* out, hipStream_t st, const char* what) {
-#define L2Q_CONV_REQUIRE(cond, code, msg)                       \
-  do {                                                          \
-    if (!(cond)) {                                              \
-      ::l2q::set_error("%s: %s", what, msg);                    \
-      return code;                                              \
-    }                                                           \
-  } while (0)
-  L2Q_CONV_REQUIRE(in && weight && out, L2Q_EINVAL, "null pointer");
-  L2Q_CONV_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL,
-                   "non-positive size");
-  L2Q_CONV_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  L2Q_REQUIRE_W(in && weight && out, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE_W(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
   ConvGeom g;
   g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
   g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
   g.clast = channels_last_cols ? 1 : 0;
   g.M = (long)nb * g.Ho * g.Wo;
-  L2Q_CONV_REQUIRE(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
+  L2Q_REQUIRE_W(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
   Epilogue<T> epi{bias, nullptr, nullptr, (T)1, act, 0};
   const int bn = cout <= 32 ? 32 : cout <= 64 ? 64 : 128;
   const dim3 grid((unsigned)cdiv(cout, bn), (unsigned)cdiv(g.M, 128)), block(kBlock);
@@ -1189,7 +1181,6 @@ int conv_gemm_launch(const T* in, long sn, long sc, long sh, long sw, int nb, in
   }
 #undef L2Q_CG
 #undef L2Q_CGB
-#undef L2Q_CONV_REQUIRE
   return check_launch(what);
 }
 

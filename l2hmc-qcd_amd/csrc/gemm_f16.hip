@@ -924,7 +924,6 @@ template <typename HT>
 bool gemm_h_small_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,
                          hipStream_t st);
 // gemm_lt.hip: hipBLASLt for plain layers with M, N, K in the thousands; false -> not taken
-bool gemm_h_lt_shape(int M, int N, long K);
 size_t gemm_h_lt_ws_bytes(int M, int N, long K);
 template <typename HT>
 bool gemm_h_lt_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,

@@ -69,6 +69,15 @@ inline int check_launch(const char* what) {
     }                                         \
   } while (0)
 
+// the same inside a launcher shared by several entry points: `what` names the entry point
+#define L2Q_REQUIRE_W(cond, code, msg)                          \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      ::l2q::set_error("%s: %s", what, msg);                    \
+      return code;                                              \
+    }                                                           \
+  } while (0)
+
 constexpr int kBlock = 256;          // 4 wavefronts of 64
 constexpr int kXcds = 8;             // MI355X: 8 XCDs, block b is observed on XCD b % 8
 
@@ -127,5 +136,9 @@ void launch_finalize(const double* partial, double* out, int nb, long nblk, int 
 // corrupted by a >= 512 KB device-to-host copy on the null stream (round 5: every later replay of a captured SU(3)
 // trajectory came out NaN; profiles/r05k_graph_memset_node.txt).  No launch path of this library records a memset node.
 void launch_zero(void* p, size_t bytes, hipStream_t st);
+
+// gemm_lt.hip: the shapes the hipBLASLt route of the plain 16-bit layers takes, and whether the library loaded
+bool gemm_h_lt_shape(int M, int N, long K);
+bool gemm_h_lt_available();
 
 }  // namespace l2q

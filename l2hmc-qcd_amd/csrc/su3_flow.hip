@@ -15,9 +15,7 @@
 // Flow: one low-storage stage is P_out = P_in + c TAH(U A), X_out = exp(s P_out) X_in with A the six
 // staples of l2q_su3_force; here it is the force kick at beta = 3 into P_out followed by the unmasked
 // expm_mul, out of place, so no neighbour ever sees a new link.
-#include "l2q_common.hpp"
-#include "su3_math.hpp"
-#include "su3_links.hpp"
+#include "su3_launch.hpp"
 
 namespace l2q {
 
@@ -157,24 +155,6 @@ struct CSite {
   int q;                 // spatial site
 };
 
-struct CPos {
-  int q, x, y, z;
-};
-
-// one periodic hop in spatial direction dir (1, 2, 3 = x, y, z); dir and sgn are wave-uniform
-__device__ __forceinline__ CPos c_move(CPos p, int dir, int sgn, const Dims& d) {
-  const int n = dir == 1 ? d.X : dir == 2 ? d.Y : d.Z;
-  const int st = dir == 1 ? d.Y * d.Z : dir == 2 ? d.Z : 1;
-  int c = dir == 1 ? p.x : dir == 2 ? p.y : p.z;
-  if (sgn > 0) {
-    if (c + 1 == n) { p.q -= (n - 1) * st; c = 0; } else { p.q += st; c += 1; }
-  } else {
-    if (c == 0) { p.q += (n - 1) * st; c = n - 1; } else { p.q -= st; c -= 1; }
-  }
-  if (dir == 1) p.x = c; else if (dir == 2) p.y = c; else p.z = c;
-  return p;
-}
-
 __global__ __launch_bounds__(kCThreads, 1) void su3_clover_slice_kernel(const double2* __restrict__ xn, Dims d,
                                                                        int nsb, int tsplit, int swz, int lo,
                                                                        double* __restrict__ partial) {
@@ -205,7 +185,7 @@ __global__ __launch_bounds__(kCThreads, 1) void su3_clover_slice_kernel(const do
     for (int i = 0; i < kCPre; ++i) cl_lds[sl * kCSlot + i * kCThreads + threadIdx.x] = *stage_addr(t, i);
   }
   __syncthreads();
-  CPos p;
+  SPos p;
   p.q = tile0 + lt;
   {
     int q = p.q;
@@ -215,10 +195,10 @@ __global__ __launch_bounds__(kCThreads, 1) void su3_clover_slice_kernel(const do
   }
   // the dual of plane (0, k): (a, b) = the two other spatial directions, eps_{0 k a b} = +, -, +
   const int a = k == 1 ? 2 : 1, b = k == 3 ? 2 : 3;
-  const CPos pkp = c_move(p, k, +1, d), pkm = c_move(p, k, -1, d);
-  const CPos pap = c_move(p, a, +1, d), pam = c_move(p, a, -1, d);
-  const CPos pbp = c_move(p, b, +1, d), pbm = c_move(p, b, -1, d);
-  const int q_am_bp = c_move(pam, b, +1, d).q, q_am_bm = c_move(pam, b, -1, d).q, q_ap_bm = c_move(pap, b, -1, d).q;
+  const SPos pkp = sp_move(p, k, +1, d), pkm = sp_move(p, k, -1, d);
+  const SPos pap = sp_move(p, a, +1, d), pam = sp_move(p, a, -1, d);
+  const SPos pbp = sp_move(p, b, +1, d), pbm = sp_move(p, b, -1, d);
+  const int q_am_bp = sp_move(pam, b, +1, d).q, q_am_bm = sp_move(pam, b, -1, d).q, q_ap_bm = sp_move(pap, b, -1, d).q;
   const auto ld = [=](M3& m, int dir, const CSite& s) {
     const int li = s.q - tile0;
     if (__all((unsigned)li < (unsigned)kCT)) {
@@ -312,26 +292,18 @@ bool clover_slice_applicable(const Dims& d) { return (d.X * d.Y * d.Z) % kCT == 
 
 using namespace l2q;
 
-static bool flow_dims_ok(int nb, int T, int X, int Y, int Z) {
-  return nb > 0 && T > 0 && X > 0 && Y > 0 && Z > 0 && (double)T * X * Y * Z * 36.0 < 2.0e9;
-}
-
 extern "C" {
 
 int l2q_su3_clover_reduce(const void* xn, int nb, int T, int X, int Y, int Z, double* out, void* ws,
                           size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(flow_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   hipStream_t st = (hipStream_t)stream;
   const int swz = tuning().xcd_swizzle;
   if (clover_slice_applicable(d)) {
     const int nsb = X * Y * Z / kCT;
-    int tsplit = (int)cdiv(512, (long)nb * nsb);       // >= ~2 rounds of 256 CUs, one workgroup each
-    if (tsplit > T) tsplit = T;
-    if (tsplit < 1) tsplit = 1;
-    const int tlen = (int)cdiv(T, tsplit);
-    tsplit = (int)cdiv(T, tlen);
+    const int tsplit = t_chunks((long)nb * nsb, T, 512);       // >= ~2 rounds of 256 CUs, one workgroup each
     const long per_chain = (long)nsb * tsplit;
     L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 3 * sizeof(double), L2Q_ESHAPE, "workspace too small");
     const size_t lds = 3ul * kCSlot * sizeof(double2);
@@ -356,7 +328,7 @@ int l2q_su3_clover_reduce(const void* xn, int nb, int T, int X, int Y, int Z, do
 int l2q_su3_flow_stage(const void* x_in, const void* p_in, double c, double s, void* p_out, void* x_out,
                        int nb, int T, int X, int Y, int Z, void* stream) {
   L2Q_REQUIRE(x_in && p_out && x_out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(flow_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(x_out != x_in, L2Q_EINVAL, "x_out must not alias x_in");
   L2Q_REQUIRE(p_out != x_in && p_out != x_out, L2Q_EINVAL, "p_out must not alias the links");
   // P_out = P_in + c TAH(U A): the force (kick) at beta = 3
@@ -370,7 +342,7 @@ int l2q_su3_flow_stage(const void* x_in, const void* p_in, double c, double s, v
 int l2q_su3_flow_step(const void* x_in, void* x_out, void* ws_p, void* ws_x, double eps, int nb, int T, int X,
                       int Y, int Z, void* stream) {
   L2Q_REQUIRE(x_in && x_out && ws_p && ws_x, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(flow_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(x_out != x_in && x_out != ws_x && x_in != ws_x, L2Q_EINVAL,
               "x_in, x_out and ws_x must be three different fields");
   L2Q_REQUIRE(ws_p != x_in && ws_p != x_out && ws_p != ws_x, L2Q_EINVAL, "ws_p must not alias the links");

@@ -27,6 +27,7 @@
 // 16^4 x 64 chains: 1.89 / 2.39 ms (2.11 / 2.79 ms).  Results are bit-identical to the thread-per-link
 // slice kernel (same operation order per link).
 #include "su3_force_tile.hpp"
+#include "su3_launch.hpp"
 
 namespace l2q {
 
@@ -408,11 +409,7 @@ void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const
                            hipStream_t st) {
   const int Vs = d.X * d.Y * d.Z;
   const int nsb = Vs / kRS;
-  int tsplit = (int)cdiv(1024, (long)nb * nsb);
-  if (tsplit > d.T) tsplit = d.T;
-  if (tsplit < 1) tsplit = 1;
-  const int tlen = (int)cdiv(d.T, tsplit);
-  tsplit = (int)cdiv(d.T, tlen);
+  const int tsplit = t_chunks((long)nb * nsb, d.T, 1024);
   switch (force_link_inmask(d)) {
     case 7: launch_link_variant<2, 7>(xn, d, nb, nsb, tsplit, coef, gf, gx, st); break;
     case 6: launch_link_variant<2, 6>(xn, d, nb, nsb, tsplit, coef, gf, gx, st); break;
@@ -421,18 +418,13 @@ void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const
   }
 }
 
-// kick: out = vin + coef * F (vin == nullptr or out: in place)
-void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out,
-                       hipStream_t st, const double2* vin) {
+void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st,
+                       const double2* vin) {
   if (vin == nullptr) vin = out;
   const int Vs = d.X * d.Y * d.Z;
   const int nsb = Vs / kRS;
-  int tsplit = (int)cdiv(1024, (long)nb * nsb);        // >= ~2 resident rounds of 2 x 256 workgroups
-  if (tuning().force_tsplit > 0) tsplit = tuning().force_tsplit;
-  if (tsplit > d.T) tsplit = d.T;
-  if (tsplit < 1) tsplit = 1;
-  const int tlen = (int)cdiv(d.T, tsplit);
-  tsplit = (int)cdiv(d.T, tlen);
+  // >= ~2 resident rounds of 2 x 256 workgroups
+  const int tsplit = t_chunks((long)nb * nsb, d.T, 1024, tuning().force_tsplit);
 #define L2Q_LK_CASE(M)                                                                    \
   case M:                                                                                 \
     if (kick) launch_link_variant<1, M>(xn, d, nb, nsb, tsplit, coef, vin, out, st);           \

@@ -39,6 +39,7 @@
 // refresh) the kernel draws enough for the socket's 1400 W cap to set the clock, which is what bounds the
 // thread-per-link kernel as well (profiles/r06_force_clock_power.txt).
 #include "su3_force_tile.hpp"
+#include "su3_launch.hpp"
 
 namespace l2q {
 
@@ -515,9 +516,6 @@ __global__ __launch_bounds__(kPqfThreads, 2) void su3_force_plaq_kernel(
   }
 }
 
-int force_link_inmask(const Dims& d);
-bool force_link_applicable(const Dims& d);
-
 // the (y, z) plane must be the 64-site tile (8^4-like lattices); everything else stays on su3_force_link.hip
 bool force_plaq_applicable(const Dims& d) {
   return force_link_applicable(d) && d.Y * d.Z == kRS && d.T >= 2 && d.X >= 2;
@@ -526,12 +524,8 @@ bool force_plaq_applicable(const Dims& d) {
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
   const int Vs = d.X * d.Y * d.Z;
   const int nsb = Vs / kRS;
-  int tsplit = (int)cdiv(512, (long)nb * nsb);                 // one workgroup per CU: >= 2 rounds of 256
-  if (tuning().force_tsplit > 0) tsplit = tuning().force_tsplit;
-  if (tsplit > d.T) tsplit = d.T;
-  if (tsplit < 1) tsplit = 1;
-  const int tlen = (int)cdiv(d.T, tsplit);
-  tsplit = (int)cdiv(d.T, tlen);
+  // one workgroup per CU: >= 2 rounds of 256
+  const int tsplit = t_chunks((long)nb * nsb, d.T, 512, tuning().force_tsplit);
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute((const void*)su3_force_plaq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

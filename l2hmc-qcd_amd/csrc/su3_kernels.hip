@@ -4,9 +4,7 @@
 // matrix entry is one coalesced 16 B/lane wavefront load; the 3x3 algebra lives in
 // registers (su3_math.hpp).  Stencil neighbours are re-read through L1/L2; the 1-D grids
 // are XCD-swizzled so the blocks that share a chain's links share an XCD's L2.
-#include "l2q_common.hpp"
-#include "su3_math.hpp"
-#include "su3_links.hpp"
+#include "su3_launch.hpp"
 
 namespace l2q {
 
@@ -427,24 +425,6 @@ constexpr int kFSPlain = 128, kFSKick = 128, kLptPlain = 2;
 // compiler-only fence: keeps hipcc from hoisting the next staple's operand loads above the
 // current staple's arithmetic
 #define L2Q_SCHED_FENCE() asm volatile("" ::: "memory")
-
-struct SPos {
-  int q, x, y, z;        // spatial site index and coordinates
-};
-
-// one periodic hop in spatial direction dir (1, 2, 3 = x, y, z); dir and sgn are wave-uniform
-__device__ __forceinline__ SPos sp_move(SPos p, int dir, int sgn, const Dims& d) {
-  const int n = dir == 1 ? d.X : dir == 2 ? d.Y : d.Z;
-  const int st = dir == 1 ? d.Y * d.Z : dir == 2 ? d.Z : 1;
-  int c = dir == 1 ? p.x : dir == 2 ? p.y : p.z;
-  if (sgn > 0) {
-    if (c + 1 == n) { p.q -= (n - 1) * st; c = 0; } else { p.q += st; c += 1; }
-  } else {
-    if (c == 0) { p.q += (n - 1) * st; c = n - 1; } else { p.q -= st; c -= 1; }
-  }
-  if (dir == 1) p.x = c; else if (dir == 2) p.y = c; else p.z = c;
-  return p;
-}
 
 // link rho of spatial site q in a slice: LDS copy if q is inside the tile (wave-uniform),
 // else the global slice; one code path through a flat pointer
@@ -897,101 +877,96 @@ __global__ void check_finalize_kernel(const double* __restrict__ psum,
 
 }  // namespace l2q
 
-namespace l2q {
-// su3_force_link.hip
-bool force_link_applicable(const Dims& d);
-int force_link_inmask(const Dims& d);
-void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out,
-                       hipStream_t st, const double2* vin = nullptr);
-// gemm_lt.hip
-bool gemm_h_lt_shape(int M, int N, long K);
-bool gemm_h_lt_available();
-// su3_flow.hip
-bool clover_slice_applicable(const Dims& d);
-// su3_force_plaq.hip
-bool force_plaq_applicable(const Dims& d);
-void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);
-}  // namespace l2q
-
 using namespace l2q;
 
-// The force kernel ladder: tuning force_tile = 7 (plain force only) the plaquette-sharing kernel, 5 (the
-// default) and 7 the thread-per-link kernel, where they apply; then the slice-resident kernel where the
-// spatial volume is whole tiles, else the LDS-tiled kernel, which takes any lattice.  force_tile = 2 starts
-// at the slice-resident kernel (the only way to reach it below the link kernel's size limit).
+// The slice-resident and LDS-tiled instantiations launch_force<KICK> runs; force_kernel_name prints the same constants.
+template <bool KICK>
+struct ForceInst {
+  static constexpr int kFS = KICK ? kFSKick : kFSPlain, kVar = KICK ? 2 : 0, kLpt = KICK ? 1 : kLptPlain, kTileOcc = 2;
+};
+
+namespace l2q {
+ForceKernel pick_force(const Dims& d, bool kick) {
+  const int ft = tuning().force_tile;
+  if (!kick && ft == 7 && force_plaq_applicable(d)) return ForceKernel::PlaqShare;
+  if (ft >= 5 && force_link_applicable(d)) return ForceKernel::Link;
+  return (d.X * d.Y * d.Z) % (kick ? kFSKick : kFSPlain) == 0 ? ForceKernel::Slice : ForceKernel::Tile;
+}
+}  // namespace l2q
+
 template <bool KICK>
 static void launch_force(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
-  const int Vs_ = d.X * d.Y * d.Z;
-  constexpr int kFS = KICK ? kFSKick : kFSPlain;
-  constexpr int kVar = KICK ? 2 : 0;
-  constexpr int kLpt = KICK ? 1 : kLptPlain;
-  if (!KICK && tuning().force_tile == 7 && force_plaq_applicable(d)) {
-    launch_force_plaq(xn, d, nb, coef, out, st);               // plaquettes shared between their four links
-    return;
-  }
-  if (tuning().force_tile >= 5 && force_link_applicable(d)) {
-    launch_force_link(KICK, xn, d, nb, coef, out, st);
-    return;
-  }
-  if (Vs_ % kFS == 0) {
-    const int nsb = Vs_ / kFS;
-    int tsplit = (int)cdiv(512, (long)nb * nsb);       // >= ~2 resident rounds of 256 CUs
-    if (tsplit > d.T) tsplit = d.T;
-    if (tsplit < 1) tsplit = 1;
-    const int tlen = (int)cdiv(d.T, tsplit);
-    tsplit = (int)cdiv(d.T, tlen);
-    const size_t lds = 2ul * 4 * 9 * kFS * sizeof(double2);
-    static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-      (void)hipFuncSetAttribute((const void*)su3_force_slice_kernel<KICK, kFS, kVar, kLpt>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  using I = ForceInst<KICK>;
+  switch (pick_force(d, KICK)) {
+    case ForceKernel::PlaqShare: launch_force_plaq(xn, d, nb, coef, out, st); return;
+    case ForceKernel::Link: launch_force_link(KICK, xn, d, nb, coef, out, st); return;
+    case ForceKernel::Slice: {
+      const int nsb = d.X * d.Y * d.Z / I::kFS;
+      const int tsplit = t_chunks((long)nb * nsb, d.T, 512);       // >= ~2 resident rounds of 256 CUs
+      const size_t lds = 2ul * 4 * 9 * I::kFS * sizeof(double2);
+      static PerDeviceOnce attr_once;
+      if (attr_once.first()) {
+        (void)hipFuncSetAttribute((const void*)su3_force_slice_kernel<KICK, I::kFS, I::kVar, I::kLpt>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      }
+      hipLaunchKernelGGL((su3_force_slice_kernel<KICK, I::kFS, I::kVar, I::kLpt>),
+                         dim3((unsigned)((long)nb * nsb * tsplit)), dim3(4 * I::kFS / I::kLpt), lds, st, xn, d, nsb,
+                         tsplit, tuning().xcd_swizzle, coef, out);
+      return;
     }
-    hipLaunchKernelGGL((su3_force_slice_kernel<KICK, kFS, kVar, kLpt>),
-                       dim3((unsigned)((long)nb * nsb * tsplit)), dim3(4 * kFS / kLpt), lds, st, xn, d, nsb,
-                       tsplit, tuning().xcd_swizzle, coef, out);
-    return;
+    case ForceKernel::Tile: {
+      const long ntile = cdiv(d.V, 64);
+      hipLaunchKernelGGL((su3_force_tile_kernel<KICK, I::kTileOcc>), dim3((unsigned)(nb * ntile)), dim3(kBlock), 0,
+                         st, xn, d, ntile, tuning().xcd_swizzle, coef, out);
+    }
   }
-  const long ntile = cdiv(d.V, 64);
-  hipLaunchKernelGGL((su3_force_tile_kernel<KICK, 2>), dim3((unsigned)(nb * ntile)), dim3(kBlock), 0, st, xn, d,
-                     ntile, tuning().xcd_swizzle, coef, out);
 }
 
-static bool dims_ok(int nb, int T, int X, int Y, int Z) {
-  return nb > 0 && T > 0 && X > 0 && Y > 0 && Z > 0 && (double)T * X * Y * Z * 36.0 < 2.0e9;
+template <bool KICK>
+static void force_kernel_name(const Dims& d, char* buf, size_t n) {
+  using I = ForceInst<KICK>;
+  const char* k = KICK ? "true" : "false";
+  switch (pick_force(d, KICK)) {
+    case ForceKernel::PlaqShare: snprintf(buf, n, "su3_force_plaq_kernel"); break;
+    case ForceKernel::Link: snprintf(buf, n, "su3_force_link_kernel<%d, %d>", KICK, force_link_inmask(d)); break;
+    case ForceKernel::Slice:
+      snprintf(buf, n, "su3_force_slice_kernel<%s, %d, %d, %d>", k, I::kFS, I::kVar, I::kLpt);
+      break;
+    case ForceKernel::Tile: snprintf(buf, n, "su3_force_tile_kernel<%s, %d>", k, I::kTileOcc);
+  }
+}
+
+// The plaquette sum: the slice-resident kernel where the spatial volume is whole tiles -- <true> where the tile is
+// whole (y, z) planes (Y*Z | 128), which keeps +y, +z inside it -- else the flat kernel.
+enum class PlaqKernel { SliceYZ, Slice, Flat };
+constexpr int kPlaqOcc = 2;
+static PlaqKernel pick_plaq(const Dims& d) {
+  if ((d.X * d.Y * d.Z) % kSlice != 0) return PlaqKernel::Flat;
+  return kSlice % (d.Y * d.Z) == 0 ? PlaqKernel::SliceYZ : PlaqKernel::Slice;
 }
 
 extern "C" {
 
 int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, size_t buf_bytes) {
   L2Q_REQUIRE(entry && buf && buf_bytes > 0, L2Q_EINVAL, "null pointer");
-  const int Vs = X * Y * Z;
   const Tuning& t = tuning();
+  const Dims dd = strncmp(entry, "l2q_su3_", 8) ? Dims{} : make_dims(T, X, Y, Z);   // (other entries: not a lattice)
   buf[0] = 0;
   if (!strcmp(entry, "l2q_su3_plaq_reduce")) {
-    if (Vs % kSlice == 0)
-      snprintf(buf, buf_bytes, "su3_plaq_slice_kernel<%s>", (kSlice % (Y * Z)) == 0 ? "true" : "false");
-    else snprintf(buf, buf_bytes, "su3_plaq_kernel<2>");
-  } else if (!strcmp(entry, "l2q_su3_force") || !strcmp(entry, "l2q_su3_force_kick")) {
-    const bool kick = !strcmp(entry, "l2q_su3_force_kick");
-    const int fs = kick ? kFSKick : kFSPlain;
-    const Dims dd{T, X, Y, Z, T * X * Y * Z};
-    if (!kick && t.force_tile == 7 && force_plaq_applicable(dd))
-      snprintf(buf, buf_bytes, "su3_force_plaq_kernel");
-    else if (t.force_tile >= 5 && force_link_applicable(dd))
-      snprintf(buf, buf_bytes, "su3_force_link_kernel<%d, %d>", kick ? 1 : 0, force_link_inmask(dd));
-    else if (Vs % fs == 0)
-      snprintf(buf, buf_bytes, "su3_force_slice_kernel<%s, %d, %d, %d>", kick ? "true" : "false", fs,
-               kick ? 2 : 0, kick ? 1 : kLptPlain);
-    else snprintf(buf, buf_bytes, "su3_force_tile_kernel<%s, 2>", kick ? "true" : "false");
+    const PlaqKernel pk = pick_plaq(dd);
+    if (pk == PlaqKernel::Flat) snprintf(buf, buf_bytes, "su3_plaq_kernel<%d>", kPlaqOcc);
+    else snprintf(buf, buf_bytes, "su3_plaq_slice_kernel<%s>", pk == PlaqKernel::SliceYZ ? "true" : "false");
+  } else if (!strcmp(entry, "l2q_su3_force")) {
+    force_kernel_name<false>(dd, buf, buf_bytes);
+  } else if (!strcmp(entry, "l2q_su3_force_kick")) {
+    force_kernel_name<true>(dd, buf, buf_bytes);
   } else if (!strcmp(entry, "l2q_su3_clover_reduce")) {
-    const Dims dd{T, X, Y, Z, T * X * Y * Z};
     snprintf(buf, buf_bytes, "%s", clover_slice_applicable(dd) ? "su3_clover_slice_kernel" : "su3_clover_kernel");
   } else if (!strcmp(entry, "l2q_su3_flow_stage")) {
     // the kick of l2q_su3_force_kick_to (out of place: only the thread-per-link kernel has that form, the others
     // follow a copy), then the unmasked x-update
     char kick[128];
-    const int rc = l2q_kernel_name("l2q_su3_force_kick", T, X, Y, Z, kick, sizeof(kick));
-    if (rc != L2Q_OK) return rc;
+    force_kernel_name<true>(dd, kick, sizeof(kick));
     snprintf(buf, buf_bytes, "%s + su3_expm_mul_kernel<false, false>", kick);
   } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64")) {
     snprintf(buf, buf_bytes, "heads_sliced_kernel");
@@ -1018,26 +993,20 @@ size_t l2q_reduce_ws_bytes(int nb, long n_per_chain) {
 int l2q_su3_plaq_reduce(const void* xn, int nb, int T, int X, int Y, int Z, double* out, void* ws,
                         size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)ws;
   const int swz = tuning().xcd_swizzle;
-  if ((X * Y * Z) % kSlice == 0) {
-    const int Vs = X * Y * Z;
-    const int nsb = Vs / kSlice;
-    int tsplit = (int)cdiv(1024, (long)nb * nsb);      // keep >= ~1024 workgroups
-    if (tsplit > T) tsplit = T;
-    if (tsplit < 1) tsplit = 1;
-    const int tlen = (int)cdiv(T, tsplit);
-    tsplit = (int)cdiv(T, tlen);
+  const PlaqKernel pk = pick_plaq(d);
+  if (pk != PlaqKernel::Flat) {
+    const int nsb = X * Y * Z / kSlice;
+    const int tsplit = t_chunks((long)nb * nsb, T, 1024);      // keep >= ~1024 workgroups
     const long per_chain = (long)nsb * tsplit;
-    L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 2 * sizeof(double), L2Q_ESHAPE,
-                "workspace too small");
-    // a 128-site tile made of whole (y,z) rows with Y*Z | 128 keeps +y, +z inside the tile
-    const bool yz = (kSlice % (Y * Z)) == 0;
-    if (yz) hipLaunchKernelGGL(su3_plaq_slice_kernel<true>, dim3((unsigned)(nb * per_chain)), dim3(kSlice), 0, st,
-                               (const double2*)xn, d, nsb, tsplit, swz, partial);
+    L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 2 * sizeof(double), L2Q_ESHAPE, "workspace too small");
+    if (pk == PlaqKernel::SliceYZ)
+      hipLaunchKernelGGL(su3_plaq_slice_kernel<true>, dim3((unsigned)(nb * per_chain)), dim3(kSlice), 0, st,
+                         (const double2*)xn, d, nsb, tsplit, swz, partial);
     else hipLaunchKernelGGL(su3_plaq_slice_kernel<false>, dim3((unsigned)(nb * per_chain)), dim3(kSlice), 0, st,
                             (const double2*)xn, d, nsb, tsplit, swz, partial);
     launch_finalize(partial, out, nb, per_chain, 2, 1.0, 0.0, st);
@@ -1045,16 +1014,16 @@ int l2q_su3_plaq_reduce(const void* xn, int nb, int T, int X, int Y, int Z, doub
   }
   const long nblk = cdiv(d.V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * 2 * sizeof(double), L2Q_ESHAPE, "workspace too small");
-  hipLaunchKernelGGL(su3_plaq_kernel<2>, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, st, (const double2*)xn, d,
-                     nblk, swz, partial);
+  hipLaunchKernelGGL(su3_plaq_kernel<kPlaqOcc>, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, st,
+                     (const double2*)xn, d, nblk, swz, partial);
   launch_finalize(partial, out, nb, nblk, 2, 1.0, 0.0, st);
   return check_launch("l2q_su3_plaq_reduce");
 }
 
 int l2q_su3_wilson_loops(const void* xn, int nb, int T, int X, int Y, int Z, void* out, void* stream) {
   L2Q_REQUIRE(xn && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   hipLaunchKernelGGL(su3_wloops_kernel, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, (hipStream_t)stream,
                      (const double2*)xn, d, nblk, (long)nb, (double2*)out);
@@ -1064,8 +1033,8 @@ int l2q_su3_wilson_loops(const void* xn, int nb, int T, int X, int Y, int Z, voi
 int l2q_su3_plaq_planes(const void* xn, int nb, int T, int X, int Y, int Z, double* out, void* ws,
                         size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * 12 * sizeof(double), L2Q_ESHAPE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -1091,9 +1060,9 @@ int l2q_diff_norm2_reduce(const double* a, const double* b, int nb, long n, doub
 int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, int Y, int Z,
                   void* stream) {
   L2Q_REQUIRE(xn && fn, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(xn != fn, L2Q_EINVAL, "force output must not alias the gauge field");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  const Dims d = make_dims(T, X, Y, Z);
   launch_force<false>((const double2*)xn, d, nb, beta / 3.0, (double2*)fn, (hipStream_t)stream);
   return check_launch("l2q_su3_force");
 }
@@ -1101,8 +1070,8 @@ int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, i
 int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int nb, int T, int X,
                        int Y, int Z, void* stream) {
   L2Q_REQUIRE(xn && vn, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   launch_force<true>((const double2*)xn, d, nb, coef * beta / 3.0, (double2*)vn, (hipStream_t)stream);
   return check_launch("l2q_su3_force_kick");
 }
@@ -1110,10 +1079,10 @@ int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int n
 int l2q_su3_force_kick_to(const void* xn, double beta, double coef, const void* v_in, void* v_out,
                           int nb, int T, int X, int Y, int Z, void* stream) {
   L2Q_REQUIRE(xn && v_in && v_out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   hipStream_t st = (hipStream_t)stream;
-  if (v_in != v_out && tuning().force_tile >= 5 && force_link_applicable(d)) {
+  if (v_in != v_out && force_link_runs(d)) {
     launch_force_link(true, (const double2*)xn, d, nb, coef * beta / 3.0, (double2*)v_out, st,
                       (const double2*)v_in);
     return check_launch("l2q_su3_force_kick_to");
@@ -1127,7 +1096,7 @@ int l2q_su3_force_kick_to(const void* xn, double beta, double coef, const void* 
 int l2q_su3_expm_mul(const void* xn, const void* vn, double eps, const float* mask_n,
                      int complement, void* out, int nb, long V, void* stream) {
   L2Q_REQUIRE(xn && vn && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL((su3_expm_mul_kernel<false, false>), dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock),
                      0, (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n,
@@ -1138,7 +1107,7 @@ int l2q_su3_expm_mul(const void* xn, const void* vn, double eps, const float* ma
 int l2q_su3_expm_mul2(const void* xn, const void* vn, double eps, const float* mask_n,
                       int complement_first, void* out, int nb, long V, void* stream) {
   L2Q_REQUIRE(xn && vn && out && mask_n, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL((su3_expm_mul_kernel<true, false>), dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock),
                      0, (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n,
@@ -1150,7 +1119,7 @@ int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const flo
                            int complement_first, void* out, double* vec, int nb, long V,
                            void* stream) {
   L2Q_REQUIRE(xn && vn && out && mask_n && vec, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL((su3_expm_mul_kernel<true, true>), dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock),
                      0, (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n,
@@ -1160,7 +1129,7 @@ int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const flo
 
 int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* stream) {
   L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_project_kernel<0>, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)in, (double2*)out, (double*)nullptr, (int)V,
@@ -1170,7 +1139,7 @@ int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* st
 
 int l2q_su3_projsu_vec8(const void* in, double* vec, long nfields, long V, void* stream) {
   L2Q_REQUIRE(in && vec, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_project_kernel<1>, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)in, (double2*)nullptr, vec, (int)V, nblk);
@@ -1179,7 +1148,7 @@ int l2q_su3_projsu_vec8(const void* in, double* vec, long nfields, long V, void*
 
 int l2q_su3_project_tah(const void* in, void* out, long nfields, long V, void* stream) {
   L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_project_kernel<2>, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)in, (double2*)out, (double*)nullptr, (int)V,
@@ -1189,7 +1158,7 @@ int l2q_su3_project_tah(const void* in, void* out, long nfields, long V, void* s
 
 int l2q_su3_project_u(const void* in, void* out, long nfields, long V, void* stream) {
   L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_project_kernel<3>, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)in, (double2*)out, (double*)nullptr, (int)V,
@@ -1200,7 +1169,7 @@ int l2q_su3_project_u(const void* in, void* out, long nfields, long V, void* str
 int l2q_su3_mul(const void* a, const void* b, int adjoint_a, int adjoint_b, void* out,
                 long nfields, long V, void* stream) {
   L2Q_REQUIRE(a && b && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_mul_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)a, (const double2*)b, adjoint_a, adjoint_b,
@@ -1211,7 +1180,7 @@ int l2q_su3_mul(const void* a, const void* b, int adjoint_a, int adjoint_b, void
 int l2q_su3_kinetic_reduce(const void* vn, int nb, long V, double* out, void* ws, size_t ws_bytes,
                            void* stream) {
   L2Q_REQUIRE(vn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long n = 36 * V;
   const long nblk = cdiv(n, 4L * kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * sizeof(double), L2Q_ESHAPE, "workspace too small");
@@ -1225,7 +1194,7 @@ int l2q_su3_kinetic_reduce(const void* vn, int nb, long V, double* out, void* ws
 
 int l2q_su3_assemble_tah(const double* normals, void* vn, long nfields, long V, void* stream) {
   L2Q_REQUIRE(normals && vn, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_assemble_tah_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, normals, (double2*)vn, V, nblk, nfields * V);
@@ -1235,7 +1204,7 @@ int l2q_su3_assemble_tah(const double* normals, void* vn, long nfields, long V, 
 int l2q_su3_check_su(const void* xn, int nb, long V, double* out, void* ws, size_t ws_bytes,
                      void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(4 * V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * 2 * sizeof(double), L2Q_ESHAPE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;

@@ -1,0 +1,49 @@
+// su3_launch.hpp -- host side of the SU(3) kernels: the argument checks, the t-chunking and the kernel choice that the
+// entry points share, and the prototype of every function that one SU(3) .hip defines and another one calls.
+#pragma once
+#include "su3_links.hpp"
+
+namespace l2q {
+
+inline Dims make_dims(int T, int X, int Y, int Z) { return Dims{T, X, Y, Z, T * X * Y * Z}; }
+
+// positive sizes, and the 36 V complex entries of a chain fit an int (in double: no product of ints can overflow)
+inline bool su3_dims_ok(int nb, int T, int X, int Y, int Z) {
+  return nb > 0 && T > 0 && X > 0 && Y > 0 && Z > 0 && (double)T * X * Y * Z * 36.0 < 2.0e9;
+}
+// the same for the per-link entry points, which take n chains or fields of V sites
+inline bool su3_field_ok(long n, long V) { return n > 0 && V > 0 && V <= 200000000L; }
+
+// Slice-resident kernels sweep t with one workgroup per (chain, spatial tile, t-chunk): the chunks per tile that bring
+// `groups` = chains x tiles to about `target` workgroups, at most T, evened out so that no chunk is empty.
+// forced > 0 (tuning force_tsplit) replaces the count asked for.
+inline int t_chunks(long groups, int T, int target, int forced = 0) {
+  long tsplit = forced > 0 ? forced : cdiv(target, groups);
+  if (tsplit > T) tsplit = T;
+  if (tsplit < 1) tsplit = 1;
+  return (int)cdiv(T, cdiv(T, tsplit));
+}
+
+// su3_force_link.hip: thread-per-link force, fused kick (out = vin + coef F; vin == nullptr or out: in place) and VJP
+bool force_link_applicable(const Dims& d);
+int force_link_inmask(const Dims& d);
+void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st,
+                       const double2* vin = nullptr);
+void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const double2* gf, double2* gx,
+                           hipStream_t st);
+// su3_force_plaq.hip: plaquettes shared between their four links (plain force only)
+bool force_plaq_applicable(const Dims& d);
+void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);
+// su3_flow.hip
+bool clover_slice_applicable(const Dims& d);
+
+// su3_kernels.hip: the force kernel ladder.  Tuning force_tile = 7 (plain force only) the plaquette-sharing kernel, 5
+// (the default) and 7 the thread-per-link kernel, where they apply; then the slice-resident kernel where the spatial
+// volume is whole tiles, else the LDS-tiled kernel, which takes any lattice.  force_tile = 2 starts at the
+// slice-resident kernel (the only way to reach it below the link kernel's size limit).
+enum class ForceKernel { PlaqShare, Link, Slice, Tile };
+ForceKernel pick_force(const Dims& d, bool kick);
+// the thread-per-link family (kick out of place, VJP) runs on this lattice: the kick has no kernel above it
+inline bool force_link_runs(const Dims& d) { return pick_force(d, true) == ForceKernel::Link; }
+
+}  // namespace l2q

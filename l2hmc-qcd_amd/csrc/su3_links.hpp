@@ -58,4 +58,23 @@ __device__ __forceinline__ int bwd(int s, int cm, const Dims& d, int mu) {
   return (cm == 0) ? s + (n - 1) * st : s - st;
 }
 
+// the slice-resident kernels sweep t and keep a thread's place inside a time slice
+struct SPos {
+  int q, x, y, z;        // spatial site index and coordinates
+};
+
+// one periodic hop in spatial direction dir (1, 2, 3 = x, y, z); dir and sgn are wave-uniform
+__device__ __forceinline__ SPos sp_move(SPos p, int dir, int sgn, const Dims& d) {
+  const int n = dir == 1 ? d.X : dir == 2 ? d.Y : d.Z;
+  const int st = dir == 1 ? d.Y * d.Z : dir == 2 ? d.Z : 1;
+  int c = dir == 1 ? p.x : dir == 2 ? p.y : p.z;
+  if (sgn > 0) {
+    if (c + 1 == n) { p.q -= (n - 1) * st; c = 0; } else { p.q += st; c += 1; }
+  } else {
+    if (c == 0) { p.q += (n - 1) * st; c = n - 1; } else { p.q -= st; c -= 1; }
+  }
+  if (dir == 1) p.x = c; else if (dir == 2) p.y = c; else p.z = c;
+  return p;
+}
+
 }  // namespace l2q

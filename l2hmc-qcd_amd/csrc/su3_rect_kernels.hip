@@ -9,7 +9,7 @@
 // long side along nu).  Everything here follows a lattice path link by link, so each kernel is a
 // table of hop sequences plus one product routine; the loops over loops are not unrolled (three
 // live matrices, as in the plaquette kernels).
-#include "su3_links.hpp"
+#include "su3_launch.hpp"
 
 namespace l2q {
 
@@ -179,10 +179,6 @@ __global__ __launch_bounds__(kBlock, 2) void su3_rect_staple_kernel(const double
   }
 }
 
-static bool rect_dims_ok(int nb, int T, int X, int Y, int Z) {
-  return nb > 0 && T > 0 && X > 0 && Y > 0 && Z > 0 && (long)T * X * Y * Z * 36 < 2000000000L;
-}
-
 }  // namespace l2q
 
 using namespace l2q;
@@ -192,8 +188,8 @@ extern "C" {
 int l2q_su3_rect_reduce(const void* xn, int nb, int T, int X, int Y, int Z, double* out, void* ws,
                         size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(rect_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * sizeof(double), L2Q_ESHAPE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -206,8 +202,8 @@ int l2q_su3_rect_reduce(const void* xn, int nb, int T, int X, int Y, int Z, doub
 int l2q_su3_rect_force_add(const void* xn, double coef, void* fn, int nb, int T, int X, int Y, int Z,
                            void* stream) {
   L2Q_REQUIRE(xn && fn, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(rect_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   hipLaunchKernelGGL(su3_rect_staple_kernel<0>, dim3((unsigned)(nb * nblk * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)xn, d, nblk, coef, (const double*)nullptr,
@@ -218,8 +214,8 @@ int l2q_su3_rect_force_add(const void* xn, double coef, void* fn, int nb, int T,
 int l2q_su3_rect_bwd(const void* xn, const double* w, void* gx, int nb, int T, int X, int Y, int Z,
                      void* stream) {
   L2Q_REQUIRE(xn && w && gx, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(rect_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "bad size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   hipLaunchKernelGGL(su3_rect_staple_kernel<1>, dim3((unsigned)(nb * nblk * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)xn, d, nblk, 0.0, w, (double2*)gx);

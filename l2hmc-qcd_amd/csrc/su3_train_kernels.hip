@@ -7,8 +7,7 @@
 //   F = TAH(M)   =>  g_M = TAH(g_F)                   (orthogonal projector, self-adjoint)
 // The reference obtains all of these from torch.autograd over torch.matrix_exp, the closed-form
 // projectSU (group/su3/pytorch/utils.py:227-346) and autograd.grad(action) (lattice.py:299-308).
-#include "l2q_common.hpp"
-#include "su3_links.hpp"
+#include "su3_launch.hpp"
 #include "su3_train_math.hpp"
 
 namespace l2q {
@@ -264,11 +263,6 @@ __global__ __launch_bounds__(kBlock, L2Q_PVB_OCC) void su3_projsu_vec8_bwd_kerne
   }
 }
 
-// su3_force_link.hip
-bool force_link_applicable(const Dims& d);
-void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const double2* gf, double2* gx,
-                           hipStream_t st);
-
 // ------------------------------------------------------------------ staple-type VJPs
 // Both use the up / down staples of link (s, mu) in direction nu
 //   S_up = U_nu(s+mu) U_mu(s+nu)^H U_nu(s)^H,  S_dn = U_nu(s+mu-nu)^H U_mu(s-nu)^H U_nu(s-nu).
@@ -500,17 +494,13 @@ __global__ void diff_bwd_kernel(const double* __restrict__ x, const double* __re
 
 using namespace l2q;
 
-static bool dims_ok4(int nb, int T, int X, int Y, int Z) {
-  return nb > 0 && T > 0 && X > 0 && Y > 0 && Z > 0 && (double)T * X * Y * Z * 36.0 < 2.0e9;
-}
-
 extern "C" {
 
 int l2q_su3_expm_mul_bwd(const void* xn, const void* vn, double eps, const float* mask_n,
                          int complement, const void* gxnew, void* gx, void* gv, double* deps,
                          int nb, long V, void* ws, size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && vn && gxnew && gx && gv && deps && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * 4 * nblk * sizeof(double), L2Q_EINVAL, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -530,7 +520,7 @@ int l2q_su3_expm_mul2_bwd(const void* xn, const void* vn, double eps, const floa
                           int complement_first, const void* gxnew, void* gx, void* gv, double* deps,
                           int nb, long V, void* ws, size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && vn && mask_n && gxnew && gx && gv && deps && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * 4 * nblk * sizeof(double), L2Q_EINVAL, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -549,7 +539,7 @@ int l2q_su3_expm_mul2_bwd(const void* xn, const void* vn, double eps, const floa
 int l2q_su3_projsu_vec8_bwd(const void* in, const double* gvec, void* gm, long nfields, long V,
                             void* stream) {
   L2Q_REQUIRE(in && gvec && gm, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nfields > 0 && V > 0 && V <= 200000000L, L2Q_EINVAL, "bad size");
+  L2Q_REQUIRE(su3_field_ok(nfields, V), L2Q_EINVAL, "bad size");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_projsu_vec8_bwd_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)in, gvec, (double2*)gm, (int)V, nblk);
@@ -559,11 +549,11 @@ int l2q_su3_projsu_vec8_bwd(const void* in, const double* gvec, void* gm, long n
 int l2q_su3_force_bwd(const void* xn, const void* gf, double beta, void* gx, int nb, int T, int X,
                       int Y, int Z, void* stream) {
   L2Q_REQUIRE(xn && gf && gx, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok4(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   // the slice-resident force sweep with the VJP epilogue (su3_force_link.hip, MODE 2) where the force itself
   // runs on it: the staple sum of the link from LDS-resident slices instead of 18 flat matrix loads per link
-  if (tuning().force_tile >= 5 && force_link_applicable(d)) {
+  if (force_link_runs(d)) {
     launch_force_link_bwd((const double2*)xn, d, nb, beta / 3.0, (const double2*)gf, (double2*)gx,
                           (hipStream_t)stream);
     return check_launch("l2q_su3_force_bwd");
@@ -578,8 +568,8 @@ int l2q_su3_force_bwd(const void* xn, const void* gf, double beta, void* gx, int
 int l2q_su3_plaq_bwd(const void* xn, const double* w, void* gx, int nb, int T, int X, int Y, int Z,
                      void* stream) {
   L2Q_REQUIRE(xn && w && gx, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok4(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   hipLaunchKernelGGL(su3_staple_bwd_kernel<1>, dim3((unsigned)(nb * nblk * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)xn, d, nblk, tuning().xcd_swizzle, 1.0,
@@ -590,8 +580,8 @@ int l2q_su3_plaq_bwd(const void* xn, const double* w, void* gx, int nb, int T, i
 int l2q_su3_wilson_loops_bwd(const void* xn, const void* w, void* gx, int nb, int T, int X, int Y, int Z,
                              void* stream) {
   L2Q_REQUIRE(xn && w && gx, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(dims_ok4(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  Dims d{T, X, Y, Z, T * X * Y * Z};
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   hipLaunchKernelGGL(su3_staple_bwd_kernel<2>, dim3((unsigned)(nb * nblk * 4)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)xn, d, nblk, tuning().xcd_swizzle, 1.0,

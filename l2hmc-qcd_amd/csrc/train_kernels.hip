@@ -583,14 +583,6 @@ using namespace l2q;
 static inline unsigned grid1(long n, int block = kBlock) { return (unsigned)cdiv(n, block); }
 
 // ---- host side of the conv-stack backward kernels, fp32 / fp64 (entry point name `what` in errors)
-#define L2Q_REQUIRE_W(cond, code, msg)                          \
-  do {                                                          \
-    if (!(cond)) {                                              \
-      ::l2q::set_error("%s: %s", what, msg);                    \
-      return code;                                              \
-    }                                                           \
-  } while (0)
-
 template <typename T>
 int col2im_periodic_launch(const T* dcol, long sn, long sc, long sh, long sw, int nb, int C, int H, int W,
                            int k, int channels_last_cols, T* dx, hipStream_t st, const char* what) {
@@ -616,7 +608,6 @@ int maxpool_act_nhwc_bwd_launch(const T* dout, const T* out, const T* in, int nb
                      in, H, W, C, pool, act, Ho, Wo, total, din);
   return check_launch(what);
 }
-#undef L2Q_REQUIRE_W
 
 template <typename T, int VEC>
 static void act_bwd_sums_launch(const T* dy, const T* y, int act, long M, int N, long rpb, long R, T* dz,

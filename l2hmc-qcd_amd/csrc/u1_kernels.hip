@@ -327,14 +327,6 @@ __global__ __launch_bounds__(kBlock) void maxpool_act_nhwc_kernel(const T* __res
 }
 
 // ---- host side of the conv-stack helpers, fp32 / fp64 (entry point name `what` in errors)
-#define L2Q_REQUIRE_W(cond, code, msg)                          \
-  do {                                                          \
-    if (!(cond)) {                                              \
-      ::l2q::set_error("%s: %s", what, msg);                    \
-      return code;                                              \
-    }                                                           \
-  } while (0)
-
 template <typename T>
 int nchw_to_nhwc_pad_launch(const T* in, int nb, int C, int H, int W, int cpad, T* out, hipStream_t st,
                             const char* what) {
@@ -387,7 +379,6 @@ int maxpool_act_nhwc_launch(const T* in, int nb, int H, int W, int C, int pool, 
                           Wo, total, out);
   return check_launch(what);
 }
-#undef L2Q_REQUIRE_W
 
 }  // namespace l2q
 

@@ -80,8 +80,12 @@ def test_kernel_dispatch_names():
     try:
         assert native.set_tuning('force_tile', 2) >= 0
         assert native.kernel_name('l2q_su3_force', L) == 'su3_force_slice_kernel<false, 128, 0, 2>'
+        assert native.kernel_name('l2q_su3_force_kick', L) == 'su3_force_slice_kernel<true, 128, 2, 1>'
         assert native.set_tuning('force_tile', 7) >= 0
         assert native.kernel_name('l2q_su3_force', L) == 'su3_force_plaq_kernel'
+        # the plaquette-sharing kernel has no kick form, and takes only lattices whose (y, z) plane is its tile
+        assert native.kernel_name('l2q_su3_force_kick', L) == 'su3_force_link_kernel<1, 6>'
+        assert native.kernel_name('l2q_su3_force', (16, 16, 16, 16)) == 'su3_force_link_kernel<0, 4>'
     finally:
         native.set_tuning('force_tile', 5)
 
