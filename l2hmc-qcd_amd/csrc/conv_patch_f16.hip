@@ -200,9 +200,8 @@ __global__ __launch_bounds__(kBlock, BN >= 128 ? 2 : 3) void conv_patch_h_kernel
 }
 
 // LDS-patch kernel when the layer fits it; false -> the caller uses the gather kernel
-template <typename HT>
-bool conv_patch_launch(const void* in, const ConvGeomH& g, const void* w, const float* bias,
-                              int cout, int act, void* out, hipStream_t st) {
+bool conv_patch_launch(int half_type, const void* in, const ConvGeomH& g, const void* w, const float* bias, int cout,
+                       int act, void* out, hipStream_t st) {
   const int C = g.C;
   if (C < 8 || (C & (C - 1)) != 0 || C > 128 || cout % 4 != 0 || cout > 128) return false;
   // Measured at cfg-3 (8192 chains, 64 x 64, filters [8, 16, 32, 64, 128]; profiles/r02_conv_patch_ab.txt):
@@ -247,17 +246,13 @@ bool conv_patch_launch(const void* in, const ConvGeomH& g, const void* w, const 
     }                                                                                            \
     hipLaunchKernelGGL((conv_patch_h_kernel<HT, BNV, MIV>), dim3((unsigned)nwg), dim3(kBlock), lds, st, a); \
   } while (0)
-  if (bn == 16) L2Q_CP(16, 8);
-  else if (bn == 32) L2Q_CP(32, 8);
-  else if (bn == 64) L2Q_CP(64, 2);
-  else L2Q_CP(128, 2);
+  L2Q_WITH_HALF(half_type,
+    if (bn == 16) L2Q_CP(16, 8);
+    else if (bn == 32) L2Q_CP(32, 8);
+    else if (bn == 64) L2Q_CP(64, 2);
+    else L2Q_CP(128, 2));
 #undef L2Q_CP
   return true;
 }
-
-template bool conv_patch_launch<_Float16>(const void*, const ConvGeomH&, const void*, const float*, int, int,
-                                          void*, hipStream_t);
-template bool conv_patch_launch<__bf16>(const void*, const ConvGeomH&, const void*, const float*, int, int,
-                                        void*, hipStream_t);
 
 }  // namespace l2q

@@ -1049,11 +1049,18 @@ static int pick_splits(int M, int N, long Kt) {
   return (int)(s < 1 ? 1 : s);
 }
 
+// The LDS-DMA kernels of the fp64 layers and heads run where tuning heads_dma is on and the call allows it (whole
+// K-slabs, aligned operands: `call_ok`); l2q_kernel_name answers for calls that do.
+static bool f64_use_dma(bool call_ok) { return tuning().heads_dma && call_ok; }
+const char* gemm_f64_kernel_name() { return f64_use_dma(true) ? "gemm_dma_f64_kernel" : "gemm_nt_kernel"; }
+const char* heads_f64_kernel_name() {
+  return f64_use_dma(true) ? "fused_heads_dma_kernel" : "fused_heads_vupdate_kernel";
+}
+
 template <typename T>
 static bool vec_ok(const T* A, const T* W, const T* A2, const T* W2, long K, long K2) {
   constexpr long V = Mfma<T>::VEC;
-  auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return K % V == 0 && K2 % V == 0 && al(A) && al(W) && al(A2) && al(W2);
+  return K % V == 0 && K2 % V == 0 && al16(A) && al16(W) && al16(A2) && al16(W2);
 }
 
 // ta / tw: operand stored transposed (see TileLoaderT); accumulate: C += result.
@@ -1069,11 +1076,10 @@ static int gemm_launch(const T* A, const T* W, int M, int N, long K, const T* A2
   Epilogue<T> epi{bias, bias2, coeff, scale, act, accumulate};
   const dim3 grid((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 128), (unsigned)splits);
   constexpr long V = Mfma<T>::VEC;
-  auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // per-operand vector-load conditions: K-contiguous operands need K % VEC, transposed ones
   // their leading dimension (M resp. N) % VEC
-  const bool veca = ta ? (M % V == 0 && al(A)) : (K % V == 0 && K2 % V == 0 && al(A) && al(A2));
-  const bool vecw = tw ? (N % V == 0 && al(W)) : (K % V == 0 && K2 % V == 0 && al(W) && al(W2));
+  const bool veca = ta ? (M % V == 0 && al16(A)) : (K % V == 0 && K2 % V == 0 && al16(A) && al16(A2));
+  const bool vecw = tw ? (N % V == 0 && al16(W)) : (K % V == 0 && K2 % V == 0 && al16(W) && al16(W2));
   if ((ta || tw) && (K2 != 0 || !veca || !vecw)) {
     set_error("l2q_gemm: transposed operands need K2 == 0 and 16-byte aligned rows");
     return L2Q_ESHAPE;
@@ -1102,9 +1108,9 @@ static int gemm_launch(const T* A, const T* W, int M, int N, long K, const T* A2
   // fp64, 16-byte aligned operands, whole K-slabs: LDS-DMA staged kernel
   bool dma = false;
   if constexpr (std::is_same<T, double>::value) {
-    dma = tuning().heads_dma && vec && K % BK == 0 && K2 % BK == 0 && kchunk % BK == 0 &&
-          (ta ? (M % 2 == 0 && M >= 2) : 128 * K * 8 < (1L << 32)) &&
-          (tw ? (N % 2 == 0 && N >= 2) : 128 * K * 8 < (1L << 32)) && 128 * K2 * 8 < (1L << 32);
+    dma = f64_use_dma(vec && K % BK == 0 && K2 % BK == 0 && kchunk % BK == 0 &&
+                      (ta ? (M % 2 == 0 && M >= 2) : 128 * K * 8 < (1L << 32)) &&
+                      (tw ? (N % 2 == 0 && N >= 2) : 128 * K * 8 < (1L << 32)) && 128 * K2 * 8 < (1L << 32));
     if (dma) {
       const double* A2p = K2 ? A2 : A;            // never dereferenced when K2 == 0
       const double* W2p = K2 ? W2 : W;
@@ -1267,8 +1273,7 @@ static int heads_launch(const double* Z, int M, int K, long N, const double* Ws,
               "null pointer");
   L2Q_REQUIRE(M > 0 && K > 0 && N > 0 && N < 2000000000L, L2Q_EINVAL, "bad size");
   L2Q_REQUIRE(K % 2 == 0, L2Q_ESHAPE, "K (last hidden width) must be even");
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  L2Q_REQUIRE(al(Z) && al(Ws) && al(Wt) && al(Wq) && al(v) && al(force), L2Q_ESHAPE,
+  L2Q_REQUIRE(al16(Z) && al16(Ws) && al16(Wt) && al16(Wq) && al16(v) && al16(force), L2Q_ESHAPE,
               "operands must be 16-byte aligned");
   const long ntile = cdiv(N, kHeadsBN), mtile = cdiv(M, 64);
   const bool mid = logdet1 != nullptr;
@@ -1282,7 +1287,7 @@ static int heads_launch(const double* Z, int M, int K, long N, const double* Ws,
   a.cs = cs; a.cq = cq; a.ss = scale_s; a.st = scale_t; a.sq = scale_q; a.eps = eps;
   a.eps2 = eps2; a.fwd2 = forward2; a.flip = flip;
   a.v = (double*)v; a.vin = v_in ? (const double*)v_in : (const double*)v;
-  L2Q_REQUIRE(al(a.vin), L2Q_ESHAPE, "operands must be 16-byte aligned");
+  L2Q_REQUIRE(al16(a.vin), L2Q_ESHAPE, "operands must be 16-byte aligned");
   a.F = (const double*)force; a.logdet_part = (double*)ws;
   a.ld1_part = (double*)ws + (size_t)M * ncols;
   a.ke_part = (double*)ws + 2 * (size_t)M * ncols;
@@ -1294,7 +1299,7 @@ static int heads_launch(const double* Z, int M, int K, long N, const double* Ws,
   launch_zero(ws, (size_t)M * ncols * (mid ? 3 : 1) * sizeof(double), st);
   // LDS-DMA kernel whenever the K-slabs are whole (tuning heads_dma = 0 keeps the older kernel)
   const bool dma_ok = (K % BK == 0) && K >= BK && K <= (1 << 20);
-  const bool dma = tuning().heads_dma && dma_ok;
+  const bool dma = f64_use_dma(dma_ok);
 #define L2Q_HEADS(C, F, P)                                                                      \
   do {                                                                                          \
     if (dma) hipLaunchKernelGGL((fused_heads_dma_kernel<C, F, P>), grid, block, 0, st, a, swz); \

@@ -13,7 +13,7 @@
 // scale are applied in fp32 (torch promotes fp32 tensor x fp16 tensor to fp32).  The input
 // layer's two products share one accumulator here (autocast rounds xlayer(x) and vlayer(v)
 // separately before adding: one rounding fewer, <= 2^-11 relative).
-#include <type_traits>
+#include <algorithm>
 #include "half_common.hpp"
 #include "u1_math.hpp"
 #include "heads_h_common.hpp"
@@ -343,17 +343,23 @@ static int pick_config_h(int M, int N, long Kt, bool* wide) {
   return (int)(s < 1 ? 1 : s);
 }
 
-
-// gemm_f16_skinny.hip: the streaming kernel of the wide-K fp32-operand input layer (N <= 256); false -> not its case
-int gemm_h_skinny_splits(int M, int N, long raw1, long K2, int want);
-size_t gemm_h_skinny_ws_bytes(int M, int N, long K, long K2);
-template <typename HT>
-bool gemm_h_skinny_launch(const float* A, const void* W, int M, int N, long K, const float* A2,
-                          const void* W2, long K2, void* ws, size_t ws_bytes, hipStream_t st,
-                          const float* cs_mask, int cs_compl, int want, int* splits_out);
+// Which kernel runs a layer of l2q_gemm_h / l2q_gemm_h_u1x: asked by both launches and by l2q_kernel_name.  16-bit A
+// and one operand pair: the one-pass kernel for K, N <= 256 on many chains, else hipBLASLt for plain layers with every
+// dimension in the thousands, else the 256 x 256 LDS-DMA kernel.  fp32 A (`u1x`: the first operand is the virtual
+// [cos | sin] of K / 2 link angles): the streaming kernel of the wide-K input layer.  Everything else, and every layer
+// whose route declines at launch time, runs on the tile kernel here, which works out its own configuration
+// (pick_config_h) once it is known to run.  Only shape tests are asked: any sizes are answered, "no layer" with Tile.
+enum class GemmHRoute { Small, Lt, Dma, Skinny, Tile };
+static GemmHRoute pick_gemm_h(int M, int N, long K, long K2, bool a_f32, bool u1x) {
+  if (a_f32) return gemm_h_skinny_splits(M, N, u1x ? K / 2 : K, K2) ? GemmHRoute::Skinny : GemmHRoute::Tile;
+  if (K2 != 0) return GemmHRoute::Tile;
+  if (gemm_h_small_shape(M, N, K)) return GemmHRoute::Small;
+  if (gemm_h_lt_shape(M, N, K)) return GemmHRoute::Lt;
+  return gemm_h_dma_shape(M, N, K) ? GemmHRoute::Dma : GemmHRoute::Tile;
+}
 
 template <typename HT, typename AS, typename CT>
-static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, const void* A2_,
+static int gemm_h_launch(GemmHRoute route, const void* A_, const void* W_, int M, int N, long K, const void* A2_,
                          const void* W2_, long K2, EpiH epi, void* C_, void* ws, size_t ws_bytes,
                          hipStream_t st, const float* cs_mask = nullptr, int cs_compl = 0) {
   const AS* A = (const AS*)A_;
@@ -363,10 +369,9 @@ static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, c
   CT* C = (CT*)C_;
   const long Kt = K + K2;
   if constexpr (std::is_same<AS, float>::value) {
-    const int sk = tuning().gemm_h_skinny;
     int S = 0;
-    if (sk != 0 && gemm_h_skinny_launch<HT>((const float*)A_, W_, M, N, K, (const float*)A2_, W2_, K2, ws,
-                                            ws_bytes, st, cs_mask, cs_compl, sk == 1 ? 0 : sk, &S)) {
+    if (route == GemmHRoute::Skinny && gemm_h_skinny_launch(kHalfType<HT>, A, W_, M, N, K, A2, W2_, K2, ws, ws_bytes,
+                                                                 st, cs_mask, cs_compl, &S)) {
       launch_splitk_reduce_h<HT, CT>((const float*)ws, S, (long)M * N, N, epi, C, st);
       return check_launch("l2q_gemm_h");
     }
@@ -407,21 +412,21 @@ static int gemm_h_launch(const void* A_, const void* W_, int M, int N, long K, c
   return check_launch("l2q_gemm_h");
 }
 
-template <typename HT>
-static int gemm_h_dispatch(const void* A, int a_f32, const void* W, int M, int N, long K,
-                           const void* A2, const void* W2, long K2, EpiH epi, void* C, int c_f32,
-                           void* ws, size_t ws_bytes, hipStream_t st,
-                           const float* cs_mask = nullptr, int cs_compl = 0) {
-  if (a_f32) {
-    return c_f32 ? gemm_h_launch<HT, float, float>(A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes,
-                                                   st, cs_mask, cs_compl)
-                 : gemm_h_launch<HT, float, HT>(A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st,
-                                                cs_mask, cs_compl);
-  }
-  return c_f32 ? gemm_h_launch<HT, HT, float>(A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st)
-               : gemm_h_launch<HT, HT, HT>(A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st);
+static int gemm_h_dispatch(int half_type, GemmHRoute route, const void* A, int a_f32, const void* W, int M, int N,
+                           long K, const void* A2, const void* W2, long K2, EpiH epi, void* C, int c_f32, void* ws,
+                           size_t ws_bytes, hipStream_t st, const float* cs_mask = nullptr, int cs_compl = 0) {
+  int rc = L2Q_OK;
+  L2Q_WITH_HALF(half_type,
+    if (a_f32)
+      rc = c_f32 ? gemm_h_launch<HT, float, float>(route, A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st, cs_mask,
+                                                   cs_compl)
+                 : gemm_h_launch<HT, float, HT>(route, A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st, cs_mask,
+                                                cs_compl);
+    else
+      rc = c_f32 ? gemm_h_launch<HT, HT, float>(route, A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st)
+                 : gemm_h_launch<HT, HT, HT>(route, A, W, M, N, K, A2, W2, K2, epi, C, ws, ws_bytes, st));
+  return rc;
 }
-
 
 // ---------------------------------------------------------------------------------------
 // The three output heads of a U(1) LeapfrogLayer AND the sub-update that consumes them, in one
@@ -919,25 +924,6 @@ __global__ __launch_bounds__(kBlock) void nchw_to_nhwc_pad_h_kernel(const float*
   for (int c = 0; c < CP; ++c) dst[c] = c < C ? (HT)src[c * HW] : (HT)0.f;
 }
 
-// gemm_f16_small.hip: K, N <= 256 on many rows; false -> not its case
-template <typename HT>
-bool gemm_h_small_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,
-                         hipStream_t st);
-// gemm_lt.hip: hipBLASLt for plain layers with M, N, K in the thousands; false -> not taken
-size_t gemm_h_lt_ws_bytes(int M, int N, long K);
-template <typename HT>
-bool gemm_h_lt_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,
-                      void* ws, size_t ws_bytes, hipStream_t st);
-// gemm_f16_dma.hip: 256 x 256 LDS-DMA kernel when the shape fits it; false -> the kernels here
-template <typename HT>
-bool gemm_h_dma_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C,
-                       int c_is_f32, hipStream_t st);
-
-// conv_patch_f16.hip: LDS-patch kernel when the layer fits it; false -> use the gather kernel here
-template <typename HT>
-bool conv_patch_launch(const void* in, const ConvGeomH& g, const void* w, const float* bias,
-                       int cout, int act, void* out, hipStream_t st);
-
 template <typename HT, typename IT>
 static int conv_h_launch(const void* in_, ConvGeomH g, const void* w_, const float* bias, int cout,
                          int act, void* out_, hipStream_t st) {
@@ -949,8 +935,9 @@ static int conv_h_launch(const void* in_, ConvGeomH g, const void* w_, const flo
   // 16-byte channel gathers: 16-bit NHWC input, (i, j, ci) order, C % 8 == 0, aligned
   const bool vec8 = sizeof(IT) == 2 && g.clast && g.sc == 1 && g.C % 8 == 0 && g.sw % 8 == 0 &&
                     g.sh % 8 == 0 && g.sn % 8 == 0 && al16(in);
+  // LDS-patch kernel when the layer fits it (conv_patch_f16.hip)
   if (g.pool != 2 && vec8 && tuning().conv_patch &&
-      conv_patch_launch<HT>(in_, g, w_, bias, cout, act, out_, st))
+      conv_patch_launch(kHalfType<HT>, in_, g, w_, bias, cout, act, out_, st))
     return check_launch("l2q_conv_gemm_periodic_h");
 #define L2Q_CHB(KS, BNV)                                                                         \
   do {                                                                                           \
@@ -990,13 +977,7 @@ __global__ void cast_f64_f32_kernel(const double* __restrict__ in, float* __rest
   if (i < n) out[i] = accumulate ? out[i] + (float)in[i] : (float)in[i];
 }
 
-// heads_kstream_f16.hip: K-split stream kernel (tuning heads_h_stream = 2); false -> not its case
-template <typename HT>
-bool heads_h_kstream_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, int swz, float* logdet,
-                            int accumulate, hipStream_t st, bool any_length);
-
-template <typename HT>
-static int heads_h_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, float* logdet,
+static int heads_h_launch(int half_type, HeadsHArgs a, int xupd, int forward, int use_ncp, float* logdet,
                           int accumulate, void* ws, hipStream_t st) {
   const long ntile = cdiv(a.N, 64), mtile = cdiv(a.M, 128);
   const dim3 grid((unsigned)(ntile * mtile)), block(kBlock);
@@ -1006,22 +987,28 @@ static int heads_h_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, floa
   double* part = (double*)ws;
   double* tmp = part + (size_t)a.M * a.ncols_part;
   a.logdet_part = part;
-  // K-split stream kernel (writes every partial it sums: no zeroing, its own finalize)
-  if (tuning().heads_h_stream >= 2 &&
-      heads_h_kstream_launch<HT>(a, xupd, forward, use_ncp, swz, logdet, accumulate, st, tuning().heads_h_stream == 3))
+  // K-split stream kernel (heads_kstream_f16.hip; writes every partial it sums: no zeroing, its own finalize)
+  if (tuning().heads_h_stream >= 2 && heads_h_kstream_launch(half_type, a, xupd, forward, use_ncp, swz, logdet,
+                                                             accumulate, st, tuning().heads_h_stream == 3))
     return check_launch("l2q_u1_heads_update_h");
   launch_zero(part, (size_t)a.M * a.ncols_part * sizeof(double), st);
   // tile kernel (tuning heads_h_stream = 0, or a shape the K-split stream kernel does not take)
 #define L2Q_HH(X, F, C) \
   hipLaunchKernelGGL((u1_heads_update_h_kernel<HT, X, F, C, 128>), grid, block, 0, st, a, swz, nfast, stg)
-  if (!xupd) { if (forward) L2Q_HH(false, true, false); else L2Q_HH(false, false, false); }
-  else if (use_ncp) { if (forward) L2Q_HH(true, true, true); else L2Q_HH(true, false, true); }
-  else { if (forward) L2Q_HH(true, true, false); else L2Q_HH(true, false, false); }
+  L2Q_WITH_HALF(half_type,
+    if (!xupd) { if (forward) L2Q_HH(false, true, false); else L2Q_HH(false, false, false); }
+    else if (use_ncp) { if (forward) L2Q_HH(true, true, true); else L2Q_HH(true, false, true); }
+    else { if (forward) L2Q_HH(true, true, false); else L2Q_HH(true, false, false); });
 #undef L2Q_HH
   launch_finalize(part, tmp, a.M, a.ncols_part, 1, 1.0, 0.0, st);
   hipLaunchKernelGGL(cast_f64_f32_kernel, dim3((unsigned)cdiv(a.M, 64)), dim3(64), 0, st, tmp, logdet,
                      a.M, accumulate);
   return check_launch("l2q_u1_heads_update_h");
+}
+
+// l2q_kernel_name("l2q_gemm_h"): "hipblaslt" when the plain-layer route of gemm_lt.hip takes the layer, "" otherwise
+const char* gemm_h_kernel_name(int M, int N, long K) {
+  return pick_gemm_h(M, N, K, 0, false, false) == GemmHRoute::Lt && gemm_h_lt_available() ? "hipblaslt" : "";
 }
 
 }  // namespace l2q
@@ -1035,20 +1022,15 @@ size_t l2q_gemm_h_ws_bytes(int M, int N, long K, long K2) {
   bool wide = false;
   const int splits = pick_config_h(M, N, K + K2, &wide);
   size_t need = (splits == 1 && !wide) ? 0 : (size_t)(splits + 1) * M * N * sizeof(float);
-  // the streaming input-layer kernel (fp32 operands, N <= 256): up to 8 K-splits of partial sums.  The
-  // element type and the U1X form are not known here: sized for any of them.
-  if (tuning().gemm_h_skinny != 0 && N <= 256 && K + K2 >= 4096 && M >= 1024) {
-    const size_t sk = gemm_h_skinny_ws_bytes(M, N, K, K2);     // partial sums + the slab-major copy of W
-    if (sk > need) need = sk;
-  }
-  if (K2 == 0 && gemm_h_lt_shape(M, N, K) && gemm_h_lt_ws_bytes(M, N, K) > need) need = gemm_h_lt_ws_bytes(M, N, K);
+  // whichever route may take the layer (each is 0 for a shape its route never takes; the type of A is not known here)
+  need = std::max(need, gemm_h_skinny_ws_bytes(M, N, K, K2));
+  if (K2 == 0) need = std::max(need, gemm_h_lt_ws_bytes(M, N, K));
   return need;
 }
 
 int l2q_gemm_h_skinny_splits(int M, int N, long K, long K2, int u1x) {
-  const int sk = tuning().gemm_h_skinny;
-  if (sk == 0 || M <= 0 || N <= 0 || K <= 0 || K2 < 0 || (u1x && (K & 1))) return 0;
-  return gemm_h_skinny_splits(M, N, u1x ? K / 2 : K, K2, sk == 1 ? 0 : sk);
+  if (M <= 0 || N <= 0 || K <= 0 || K2 < 0 || (u1x && (K & 1))) return 0;
+  return gemm_h_skinny_splits(M, N, u1x ? K / 2 : K, K2);
 }
 
 int l2q_gemm_h(int half_type, const void* A, int a_is_f32, const void* W, int M, int N, long K,
@@ -1059,36 +1041,23 @@ int l2q_gemm_h(int half_type, const void* A, int a_is_f32, const void* W, int M,
   L2Q_REQUIRE(M > 0 && N > 0 && K > 0 && K2 >= 0, L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(K2 == 0 || (A2 && W2), L2Q_EINVAL, "second operand pair missing");
   L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
+  L2Q_REQUIRE(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
   L2Q_REQUIRE(coeff == nullptr || c_is_f32, L2Q_EINVAL, "exp(coeff) scaling needs an fp32 output");
   const EpiH epi{bias, bias2, coeff, scale, act};
   const hipStream_t st = (hipStream_t)stream;
-  // hidden layers on many chains (K, N <= 256): one pass, all N columns per workgroup (gemm_f16_small.hip)
-  if (tuning().gemm_h_small && !a_is_f32 && K2 == 0) {
-    const bool done = half_type == L2Q_HALF_F16
-                          ? gemm_h_small_launch<_Float16>(A, W, M, N, K, epi, C, c_is_f32, st)
-                          : gemm_h_small_launch<__bf16>(A, W, M, N, K, epi, C, c_is_f32, st);
-    if (done) return check_launch("l2q_gemm_h");
+  const GemmHRoute route = pick_gemm_h(M, N, K, K2, a_is_f32 != 0, false);
+  bool done = false;
+  switch (route) {
+    case GemmHRoute::Small: done = gemm_h_small_launch(half_type, A, W, M, N, K, epi, C, c_is_f32, st); break;
+    case GemmHRoute::Lt:
+      done = gemm_h_lt_launch(half_type, A, W, M, N, K, epi, C, c_is_f32, ws, ws_bytes, st);
+      if (done) break;
+      [[fallthrough]];      // hipBLASLt missing or refusing: the LDS-DMA kernel, where the shape is also its own
+    case GemmHRoute::Dma: done = gemm_h_dma_launch(half_type, A, W, M, N, K, epi, C, c_is_f32, st); break;
+    default: break;      // Skinny: inside gemm_h_launch, which has the types of its split-K reduction; Tile
   }
-  // plain layers with every dimension in the thousands: hipBLASLt (gemm_lt.hip), when it is there and takes the shape
-  if (!a_is_f32 && K2 == 0 && gemm_h_lt_shape(M, N, K)) {
-    const bool done = half_type == L2Q_HALF_F16
-                          ? gemm_h_lt_launch<_Float16>(A, W, M, N, K, epi, C, c_is_f32, ws, ws_bytes, st)
-                          : gemm_h_lt_launch<__bf16>(A, W, M, N, K, epi, C, c_is_f32, ws, ws_bytes, st);
-    if (done) return check_launch("l2q_gemm_h");
-  }
-  // big 16-bit x 16-bit layers: 256 x 256 tiles on LDS-DMA staging (gemm_f16_dma.hip)
-  if (tuning().gemm_h_dma && !a_is_f32 && K2 == 0) {
-    const bool done = half_type == L2Q_HALF_F16
-                          ? gemm_h_dma_launch<_Float16>(A, W, M, N, K, epi, C, c_is_f32, st)
-                          : gemm_h_dma_launch<__bf16>(A, W, M, N, K, epi, C, c_is_f32, st);
-    if (done) return check_launch("l2q_gemm_h");
-  }
-  if (half_type == L2Q_HALF_F16)
-    return gemm_h_dispatch<_Float16>(A, a_is_f32, W, M, N, K, A2, W2, K2, epi, C, c_is_f32, ws,
-                                     ws_bytes, st);
-  return gemm_h_dispatch<__bf16>(A, a_is_f32, W, M, N, K, A2, W2, K2, epi, C, c_is_f32, ws,
-                                 ws_bytes, st);
+  if (done) return check_launch("l2q_gemm_h");
+  return gemm_h_dispatch(half_type, route, A, a_is_f32, W, M, N, K, A2, W2, K2, epi, C, c_is_f32, ws, ws_bytes, st);
 }
 
 size_t l2q_u1_heads_update_h_ws_bytes(int M, long N) {
@@ -1106,7 +1075,7 @@ int l2q_u1_heads_update_h(int half_type, const void* Z, int M, int K, long N, co
               L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE(!x_update || mask, L2Q_EINVAL, "x-update needs the mask");
   L2Q_REQUIRE(M > 0 && K > 0 && N > 0 && N < 2000000000L, L2Q_EINVAL, "bad size");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
+  L2Q_REQUIRE(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
   L2Q_REQUIRE(K % 8 != 0 || (al16(Z) && al16(Ws) && al16(Wt) && al16(Wq)), L2Q_ESHAPE,
               "operands must be 16-byte aligned");
   L2Q_REQUIRE(ws_bytes >= l2q_u1_heads_update_h_ws_bytes(M, N), L2Q_ESHAPE, "workspace too small");
@@ -1115,10 +1084,7 @@ int l2q_u1_heads_update_h(int half_type, const void* Z, int M, int K, long N, co
   h.cs = cs; h.cq = cq; h.st = scale_t; h.eps = eps; h.a = a; h.bsrc = b; h.mask = mask;
   h.complement = complement; h.logdet_part = nullptr;
   h.M = M; h.N = (int)N; h.K = K; h.ncols_part = (int)(cdiv(N, 64) * 2);
-  const hipStream_t st = (hipStream_t)stream;
-  if (half_type == L2Q_HALF_F16)
-    return heads_h_launch<_Float16>(h, x_update, forward, use_ncp, logdet, accumulate, ws, st);
-  return heads_h_launch<__bf16>(h, x_update, forward, use_ncp, logdet, accumulate, ws, st);
+  return heads_h_launch(half_type, h, x_update, forward, use_ncp, logdet, accumulate, ws, (hipStream_t)stream);
 }
 
 int l2q_gemm_h_u1x(int half_type, const float* x, const float* mask, int complement, const void* W,
@@ -1129,80 +1095,64 @@ int l2q_gemm_h_u1x(int half_type, const float* x, const float* mask, int complem
   L2Q_REQUIRE(M > 0 && N > 0 && xdim > 0 && K2 >= 0, L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(K2 == 0 || (A2 && W2), L2Q_EINVAL, "second operand pair missing");
   L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
+  L2Q_REQUIRE(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
   const EpiH epi{bias, bias2, nullptr, 1.f, act};
+  return gemm_h_dispatch(half_type, pick_gemm_h(M, N, 2 * xdim, K2, true, true), x, 1, W, M, N, 2 * xdim, A2, W2, K2,
+                         epi, C, 0, ws, ws_bytes, (hipStream_t)stream, mask, complement);
+}
+
+// the two conv entry points: pool = 2 fuses MaxPool2d(2) and the activation (GEMM rows = 4 x pooled pixels)
+static int conv_h_entry(const char* what, int pool, int half_type, const void* in, int in_is_f32, long sn, long sc,
+                        long sh, long sw, int nb, int C, int H, int W, int k, const void* weight,
+                        int channels_last_cols, const float* bias, int cout, int act, void* out, void* stream) {
+  L2Q_REQUIRE_W(in && weight && out, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE_W(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  L2Q_REQUIRE_W(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
+  ConvGeomH g;
+  g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
+  g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
+  g.clast = channels_last_cols ? 1 : 0;
+  g.M = (long)nb * g.Ho * g.Wo;
+  if (pool == 2) {
+    g.pool = 2; g.Hp = g.Ho / 2; g.Wp = g.Wo / 2;
+    L2Q_REQUIRE_W(g.Hp > 0 && g.Wp > 0, L2Q_ESHAPE, "image smaller than the pooling window");
+    g.M = 4L * nb * g.Hp * g.Wp;
+  }
+  L2Q_REQUIRE_W(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
   const hipStream_t st = (hipStream_t)stream;
-  if (half_type == L2Q_HALF_F16)
-    return gemm_h_dispatch<_Float16>(x, 1, W, M, N, 2 * xdim, A2, W2, K2, epi, C, 0, ws, ws_bytes, st,
-                                     mask, complement);
-  return gemm_h_dispatch<__bf16>(x, 1, W, M, N, 2 * xdim, A2, W2, K2, epi, C, 0, ws, ws_bytes, st,
-                                 mask, complement);
+  int rc = L2Q_OK;
+  L2Q_WITH_HALF(half_type, rc = in_is_f32 ? conv_h_launch<HT, float>(in, g, weight, bias, cout, act, out, st)
+                                          : conv_h_launch<HT, HT>(in, g, weight, bias, cout, act, out, st));
+  return rc;
 }
 
 int l2q_conv_gemm_periodic_h(int half_type, const void* in, int in_is_f32, long sn, long sc, long sh,
                              long sw, int nb, int C, int H, int W, int k, const void* weight,
                              int channels_last_cols, const float* bias, int cout, int act,
                              void* out, void* stream) {
-  L2Q_REQUIRE(in && weight && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL,
-              "non-positive size");
-  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
-  ConvGeomH g;
-  g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
-  g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
-  g.clast = channels_last_cols ? 1 : 0;
-  g.M = (long)nb * g.Ho * g.Wo;
-  L2Q_REQUIRE(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
-  const hipStream_t st = (hipStream_t)stream;
-  if (half_type == L2Q_HALF_F16) {
-    return in_is_f32 ? conv_h_launch<_Float16, float>(in, g, weight, bias, cout, act, out, st)
-                     : conv_h_launch<_Float16, _Float16>(in, g, weight, bias, cout, act, out, st);
-  }
-  return in_is_f32 ? conv_h_launch<__bf16, float>(in, g, weight, bias, cout, act, out, st)
-                   : conv_h_launch<__bf16, __bf16>(in, g, weight, bias, cout, act, out, st);
+  return conv_h_entry(__func__, 1, half_type, in, in_is_f32, sn, sc, sh, sw, nb, C, H, W, k, weight,
+                      channels_last_cols, bias, cout, act, out, stream);
 }
 
 int l2q_conv_pool_gemm_periodic_h(int half_type, const void* in, int in_is_f32, long sn, long sc,
                                   long sh, long sw, int nb, int C, int H, int W, int k,
                                   const void* weight, int channels_last_cols, const float* bias,
                                   int cout, int act, void* out, void* stream) {
-  L2Q_REQUIRE(in && weight && out, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && k > 0 && cout > 0, L2Q_EINVAL,
-              "non-positive size");
-  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
-  ConvGeomH g;
-  g.sn = sn; g.sc = sc; g.sh = sh; g.sw = sw; g.C = C; g.H = H; g.W = W; g.k = k;
-  g.Ho = H + k - 1; g.Wo = W + k - 1; g.Kc = C * k * k;
-  g.clast = channels_last_cols ? 1 : 0;
-  g.pool = 2; g.Hp = g.Ho / 2; g.Wp = g.Wo / 2;
-  L2Q_REQUIRE(g.Hp > 0 && g.Wp > 0, L2Q_ESHAPE, "image smaller than the pooling window");
-  g.M = 4L * nb * g.Hp * g.Wp;
-  L2Q_REQUIRE(cdiv(g.M, 128) < 65536L * 16 && g.M < (1L << 31), L2Q_ESHAPE, "too many output pixels");
-  const hipStream_t st = (hipStream_t)stream;
-  if (half_type == L2Q_HALF_F16) {
-    return in_is_f32 ? conv_h_launch<_Float16, float>(in, g, weight, bias, cout, act, out, st)
-                     : conv_h_launch<_Float16, _Float16>(in, g, weight, bias, cout, act, out, st);
-  }
-  return in_is_f32 ? conv_h_launch<__bf16, float>(in, g, weight, bias, cout, act, out, st)
-                   : conv_h_launch<__bf16, __bf16>(in, g, weight, bias, cout, act, out, st);
+  return conv_h_entry(__func__, 2, half_type, in, in_is_f32, sn, sc, sh, sw, nb, C, H, W, k, weight,
+                      channels_last_cols, bias, cout, act, out, stream);
 }
 
 int l2q_nchw_to_nhwc_pad_h(int half_type, const float* in, int nb, int C, int H, int W, int cpad,
                            void* out, void* stream) {
   L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE(nb > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, L2Q_EINVAL, "bad size");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
+  L2Q_REQUIRE(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
   const long HW = (long)H * W, total = (long)nb * HW;
   const dim3 grid((unsigned)cdiv(total, kBlock)), block(kBlock);
   const hipStream_t st = (hipStream_t)stream;
-  if (half_type == L2Q_HALF_F16)
-    hipLaunchKernelGGL(nchw_to_nhwc_pad_h_kernel<_Float16>, grid, block, 0, st, in, C, HW, cpad, total,
-                       (_Float16*)out);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_pad_h_kernel<__bf16>, grid, block, 0, st, in, C, HW, cpad, total,
-                       (__bf16*)out);
+  L2Q_WITH_HALF(half_type, hipLaunchKernelGGL(nchw_to_nhwc_pad_h_kernel<HT>, grid, block, 0, st, in, C, HW, cpad,
+                                              total, (HT*)out));
   return check_launch("l2q_nchw_to_nhwc_pad_h");
 }
 
@@ -1210,18 +1160,17 @@ int l2q_maxpool_act_nhwc_h(int half_type, const void* in, int nb, int H, int W, 
                            int act, void* out, void* stream) {
   L2Q_REQUIRE(in && out, L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE(nb > 0 && H > 0 && W > 0 && C > 0 && pool > 0, L2Q_EINVAL, "non-positive size");
-  L2Q_REQUIRE(half_type == L2Q_HALF_F16 || half_type == L2Q_HALF_BF16, L2Q_EINVAL, "bad half type");
+  L2Q_REQUIRE(half_type_ok(half_type), L2Q_EINVAL, kBadHalf);
   const int Ho = H / pool, Wo = W / pool;
   L2Q_REQUIRE(Ho > 0 && Wo > 0, L2Q_ESHAPE, "pooling window larger than the image");
   const int vec = (C % 8 == 0 && al16(in) && al16(out)) ? 8 : 1;
   const long total = (long)nb * Ho * Wo * (C / vec);
   const dim3 grid((unsigned)cdiv(total, kBlock)), block(kBlock);
   const hipStream_t st = (hipStream_t)stream;
-#define L2Q_MP(HT, V)                                                                              \
+#define L2Q_MP(V)                                                                                  \
   hipLaunchKernelGGL((maxpool_act_nhwc_h_kernel<HT, V>), grid, block, 0, st, (const HT*)in, H, W, C, \
                      pool, act, Ho, Wo, total, (HT*)out)
-  if (half_type == L2Q_HALF_F16) { if (vec == 8) L2Q_MP(_Float16, 8); else L2Q_MP(_Float16, 1); }
-  else { if (vec == 8) L2Q_MP(__bf16, 8); else L2Q_MP(__bf16, 1); }
+  L2Q_WITH_HALF(half_type, if (vec == 8) L2Q_MP(8); else L2Q_MP(1));
 #undef L2Q_MP
   return check_launch("l2q_maxpool_act_nhwc_h");
 }

@@ -195,13 +195,17 @@ __global__ __launch_bounds__(64 * kHdWaves, kHdWaves / 4) void gemm_h_dma_kernel
   }
 }
 
-// true: launched.  false: the shape does not fit (the caller uses gemm_nt_h_kernel)
-template <typename HT>
-bool gemm_h_dma_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C,
-                       int c_is_f32, hipStream_t st) {
-  if (M % kHdBM || N % kHdBN || K % kHdBK || K < 4 * kHdBK) return false;
+// the shapes this kernel takes (tuning gemm_h_dma = 0: none)
+bool gemm_h_dma_shape(int M, int N, long K) {
+  if (!tuning().gemm_h_dma || M % kHdBM || N % kHdBN || K % kHdBK || K < 4 * kHdBK) return false;
   if ((long)(M / kHdBM) * (N / kHdBN) < 128) return false;  // few tiles: the split-K kernels fill the chip
-  if (!al16(A) || !al16(W) || !al16(C) || (double)kHdBM * K * 2.0 >= 4.0e9) return false;
+  return (double)kHdBM * K * 2.0 < 4.0e9;
+}
+
+// true: launched.  false: the shape does not fit (the caller uses gemm_nt_h_kernel)
+bool gemm_h_dma_launch(int half_type, const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C,
+                       int c_is_f32, hipStream_t st) {
+  if (!gemm_h_dma_shape(M, N, K) || !al16(A) || !al16(W) || !al16(C)) return false;
   const long tm = M / kHdBM, tn = N / kHdBN;
   const int patched = (tm % 8 == 0 && tn % 4 == 0) ? 1 : 0;     // (row-major tile order: 5.72 instead of 5.46 ms)
   const dim3 grid((unsigned)(tm * tn)), block(64 * kHdWaves);
@@ -216,15 +220,9 @@ bool gemm_h_dma_launch(const void* A, const void* W, int M, int N, long K, const
     hipLaunchKernelGGL((gemm_h_dma_kernel<HT, CTV>), grid, block, lds, st, (const HT*)A, (const HT*)W, M, \
                        N, K, epi, (CTV*)C, patched);                                                 \
   } while (0)
-  if (c_is_f32) L2Q_HD(float);
-  else L2Q_HD(HT);
+  L2Q_WITH_HALF(half_type, if (c_is_f32) L2Q_HD(float); else L2Q_HD(HT));
 #undef L2Q_HD
   return true;
 }
-
-template bool gemm_h_dma_launch<_Float16>(const void*, const void*, int, int, long, const EpiH&, void*, int,
-                                          hipStream_t);
-template bool gemm_h_dma_launch<__bf16>(const void*, const void*, int, int, long, const EpiH&, void*, int,
-                                        hipStream_t);
 
 }  // namespace l2q

@@ -253,10 +253,16 @@ __global__ __launch_bounds__(kSkNT, SK_OCC) void gemm_skinny_h_kernel(SkArgs a) 
   }
 }
 
+// what M, N and the total K decide of the shape test below (tuning gemm_h_skinny = 0: never)
+bool gemm_h_skinny_maybe(int M, int N, long Kt) {
+  return tuning().gemm_h_skinny != 0 && N <= kSkBN && M >= 1024 && Kt >= 4096;
+}
+
 // splits the skinny kernel would use for this shape, 0: the shape is not its case.  `raw1`: K-columns of the
-// first operand as stored (U1X: xdim).
-int gemm_h_skinny_splits(int M, int N, long raw1, long K2, int want) {
-  if (N > kSkBN || N < 64 || M < 1024 || raw1 % kSkBKA != 0 || K2 % kSkBKA != 0 || raw1 + K2 < 4096) return 0;
+// first operand as stored (U1X: xdim).  Tuning gemm_h_skinny = 2 / 4 / 8 asks for that split count or none.
+int gemm_h_skinny_splits(int M, int N, long raw1, long K2) {
+  if (!gemm_h_skinny_maybe(M, N, raw1 + K2) || N < 64 || raw1 % kSkBKA != 0 || K2 % kSkBKA != 0) return 0;
+  const int want = tuning().gemm_h_skinny == 1 ? 0 : tuning().gemm_h_skinny;
   const long s1 = raw1 / kSkBKA, s2 = K2 / kSkBKA;
   const long mt = cdiv(M, kSkBM);
   const long slots = 256L * 2 / kSkRH;                 // a full first round of workgroups (8 wavefronts per CU)
@@ -272,43 +278,39 @@ int gemm_h_skinny_splits(int M, int N, long raw1, long K2, int want) {
   return fits ? fits : smallest;
 }
 
+// Up to 8 K-splits of partial sums + the slab-major copy of W.  Sized for more shapes than the kernel takes: the caller
+// of l2q_gemm_h_ws_bytes knows neither the element type of A nor whether the first operand is the cos | sin form.
 size_t gemm_h_skinny_ws_bytes(int M, int N, long K, long K2) {
+  if (!gemm_h_skinny_maybe(M, N, K + K2)) return 0;
   return (size_t)8 * M * N * sizeof(float) + (size_t)N * (K + K2) * 2;
 }
 
 // true: launched (partials in ws; the caller runs splitk_reduce_h_kernel).  false: not this kernel's case.
-template <typename HT>
-bool gemm_h_skinny_launch(const float* A, const void* W, int M, int N, long K, const float* A2,
-                          const void* W2, long K2, void* ws, size_t ws_bytes, hipStream_t st,
-                          const float* cs_mask, int cs_compl, int want, int* splits_out) {
+bool gemm_h_skinny_launch(int half_type, const float* A, const void* W, int M, int N, long K, const float* A2,
+                          const void* W2, long K2, void* ws, size_t ws_bytes, hipStream_t st, const float* cs_mask,
+                          int cs_compl, int* splits_out) {
   const long raw1 = cs_mask ? K / 2 : K;
   if (cs_mask && (K & 1)) return false;
-  const int S = gemm_h_skinny_splits(M, N, raw1, K2, want);
+  const int S = gemm_h_skinny_splits(M, N, raw1, K2);
   if (S == 0) return false;
   if (!al16(A) || !al16(A2) || !al16(W) || !al16(W2) || !al16(cs_mask)) return false;
   const size_t part_bytes = (size_t)S * M * N * sizeof(float);
   if (!ws || part_bytes + (size_t)N * (K + K2) * 2 > ws_bytes) return false;
-  HT* Wp = (HT*)((char*)ws + part_bytes);
-  const long pieces = (K + K2) / 8 * N;
-  hipLaunchKernelGGL((pack_w_kernel<HT>), dim3((unsigned)cdiv(pieces, kBlock)), dim3(kBlock), 0, st,
-                     (const HT*)W, K, (const HT*)W2, K2, N, Wp);
+  void* Wp = (char*)ws + part_bytes;
   SkArgs a;
   a.A = A; a.A2 = A2; a.Wp = Wp; a.mask = cs_mask; a.complement = cs_compl;
   a.M = M; a.N = N; a.K = raw1; a.K2 = K2; a.splits = S; a.part = (float*)ws;
+  const long pieces = (K + K2) / 8 * N;
   const dim3 grid((unsigned)(cdiv(M, kSkBM) * S));
-  if (cs_mask)
-    hipLaunchKernelGGL((gemm_skinny_h_kernel<HT, true>), grid, dim3(kSkNT), 0, st, a);
-  else
-    hipLaunchKernelGGL((gemm_skinny_h_kernel<HT, false>), grid, dim3(kSkNT), 0, st, a);
+  L2Q_WITH_HALF(half_type,
+    hipLaunchKernelGGL((pack_w_kernel<HT>), dim3((unsigned)cdiv(pieces, kBlock)), dim3(kBlock), 0, st,
+                       (const HT*)W, K, (const HT*)W2, K2, N, (HT*)Wp);
+    if (cs_mask)
+      hipLaunchKernelGGL((gemm_skinny_h_kernel<HT, true>), grid, dim3(kSkNT), 0, st, a);
+    else
+      hipLaunchKernelGGL((gemm_skinny_h_kernel<HT, false>), grid, dim3(kSkNT), 0, st, a));
   *splits_out = S;
   return true;
 }
-
-template bool gemm_h_skinny_launch<_Float16>(const float*, const void*, int, int, long, const float*,
-                                             const void*, long, void*, size_t, hipStream_t, const float*,
-                                             int, int, int*);
-template bool gemm_h_skinny_launch<__bf16>(const float*, const void*, int, int, long, const float*,
-                                           const void*, long, void*, size_t, hipStream_t, const float*, int,
-                                           int, int*);
 
 }  // namespace l2q

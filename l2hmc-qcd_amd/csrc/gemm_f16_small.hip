@@ -121,23 +121,24 @@ __global__ __launch_bounds__(kSmNT, 2) void gemm_small_h_kernel(const HT* __rest
   }
 }
 
-// true: launched.  false: not this kernel's case
-template <typename HT>
-bool gemm_h_small_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,
-                         hipStream_t st) {
-  if (K > kSmKMax || K < 32 || K % 32 != 0 || N > 256 || N < 16 || M < 2048) return false;
-  if (!al16(A) || !al16(W) || !al16(C)) return false;
-  const dim3 grid((unsigned)cdiv(M, kSmBM)), block(kSmNT);
-  if (c_is_f32)
-    hipLaunchKernelGGL((gemm_small_h_kernel<HT, float>), grid, block, 0, st, (const HT*)A, (const HT*)W, M, N, (int)K,
-                       epi, (float*)C);
-  else
-    hipLaunchKernelGGL((gemm_small_h_kernel<HT, HT>), grid, block, 0, st, (const HT*)A, (const HT*)W, M, N, (int)K,
-                       epi, (HT*)C);
-  return true;
+// the shapes this kernel takes (tuning gemm_h_small = 0: none)
+bool gemm_h_small_shape(int M, int N, long K) {
+  return tuning().gemm_h_small && K <= kSmKMax && K >= 32 && K % 32 == 0 && N <= 256 && N >= 16 && M >= 2048;
 }
 
-template bool gemm_h_small_launch<_Float16>(const void*, const void*, int, int, long, const EpiH&, void*, int, hipStream_t);
-template bool gemm_h_small_launch<__bf16>(const void*, const void*, int, int, long, const EpiH&, void*, int, hipStream_t);
+// true: launched.  false: not this kernel's case
+bool gemm_h_small_launch(int half_type, const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C,
+                         int c_is_f32, hipStream_t st) {
+  if (!gemm_h_small_shape(M, N, K) || !al16(A) || !al16(W) || !al16(C)) return false;
+  const dim3 grid((unsigned)cdiv(M, kSmBM)), block(kSmNT);
+  L2Q_WITH_HALF(half_type,
+    if (c_is_f32)
+      hipLaunchKernelGGL((gemm_small_h_kernel<HT, float>), grid, block, 0, st, (const HT*)A, (const HT*)W, M, N,
+                         (int)K, epi, (float*)C);
+    else
+      hipLaunchKernelGGL((gemm_small_h_kernel<HT, HT>), grid, block, 0, st, (const HT*)A, (const HT*)W, M, N, (int)K,
+                         epi, (HT*)C));
+  return true;
+}
 
 }  // namespace l2q

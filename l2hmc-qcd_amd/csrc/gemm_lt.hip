@@ -15,7 +15,6 @@
 // kernels.  Handle, descriptors and the heuristic's algorithm are cached per (device, type, shape); the call
 // allocates nothing per launch: the library's workspace and the 16-bit staging of D are carved out of the
 // caller's `ws` (l2q_gemm_h_ws_bytes accounts for them).
-#include "l2q_common.hpp"
 #include "half_common.hpp"
 
 #include <dlfcn.h>
@@ -142,10 +141,8 @@ size_t gemm_h_lt_ws_bytes(int M, int N, long K) {
 }
 
 // true: the layer has been enqueued on `st`.  false: not taken (library missing, shape refused): the caller goes on.
-template <typename HT>
-bool gemm_h_lt_launch(const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C, int c_is_f32,
-                      void* ws, size_t ws_bytes, hipStream_t st) {
-  constexpr int half_type = std::is_same<HT, _Float16>::value ? L2Q_HALF_F16 : L2Q_HALF_BF16;
+bool gemm_h_lt_launch(int half_type, const void* A, const void* W, int M, int N, long K, const EpiH& epi, void* C,
+                      int c_is_f32, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!gemm_h_lt_shape(M, N, K) || epi.bias2 || epi.coeff || epi.scale != 1.0f) return false;
   if (!ws || ws_bytes < gemm_h_lt_ws_bytes(M, N, K)) return false;
   if (!al16(A) || !al16(W) || !al16(C)) return false;
@@ -202,9 +199,9 @@ bool gemm_h_lt_launch(const void* A, const void* W, int M, int N, long K, const 
   if (!p.usable) return false;
   char* wsb = reinterpret_cast<char*>(ws);
   void* lt_ws = wsb;
-  HT* d16 = reinterpret_cast<HT*>(wsb + kLtWorkspace);
+  void* d16 = wsb + kLtWorkspace;                                      // 16-bit staging of D
   const bool direct = !c_is_f32 && epi.act == L2Q_ACT_NONE;            // the library's output IS the result
-  void* dout = direct ? C : (void*)d16;
+  void* dout = direct ? C : d16;
   if (epi.bias) {
     const void* bp = epi.bias;
     if (api.desc_set(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bp, sizeof(bp)) != HIPBLAS_STATUS_SUCCESS)
@@ -217,15 +214,11 @@ bool gemm_h_lt_launch(const void* A, const void* W, int M, int N, long K, const 
   if (!direct) {
     const long n = (long)M * N;
     const dim3 grid((unsigned)cdiv(cdiv(n, 8), kBlock)), block(kBlock);
-    if (c_is_f32) hipLaunchKernelGGL((lt_act_kernel<HT, true>), grid, block, 0, st, d16, C, n, epi.act);
-    else hipLaunchKernelGGL((lt_act_kernel<HT, false>), grid, block, 0, st, d16, C, n, epi.act);
+    L2Q_WITH_HALF(half_type,
+      if (c_is_f32) hipLaunchKernelGGL((lt_act_kernel<HT, true>), grid, block, 0, st, (const HT*)d16, C, n, epi.act);
+      else hipLaunchKernelGGL((lt_act_kernel<HT, false>), grid, block, 0, st, (const HT*)d16, C, n, epi.act));
   }
   return true;
 }
-
-template bool gemm_h_lt_launch<_Float16>(const void*, const void*, int, int, long, const EpiH&, void*, int, void*,
-                                         size_t, hipStream_t);
-template bool gemm_h_lt_launch<__bf16>(const void*, const void*, int, int, long, const EpiH&, void*, int, void*,
-                                       size_t, hipStream_t);
 
 }  // namespace l2q

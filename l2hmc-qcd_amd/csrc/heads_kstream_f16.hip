@@ -305,8 +305,7 @@ __global__ __launch_bounds__(kBlock) void kstream_finalize_kernel(const double* 
 }
 
 // true: launched.  false: not this kernel's case (K != 256, ragged N, unaligned operands)
-template <typename HT>
-bool heads_h_kstream_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, int swz, float* logdet,
+bool heads_h_kstream_launch(int half_type, HeadsHArgs a, int xupd, int forward, int use_ncp, int swz, float* logdet,
                             int accumulate, hipStream_t st, bool any_length) {
   // (short streams -- fewer than ~8 steps per workgroup -- stay on the tile kernel: the stationary weights and the
   // pipeline fill are paid per workgroup)
@@ -333,16 +332,14 @@ bool heads_h_kstream_launch(HeadsHArgs a, int xupd, int forward, int use_ncp, in
     else if (a.K == 128) hipLaunchKernelGGL((u1_heads_kstream_h_kernel<HT, X, F, C, 2>), grid, block, 0, st, a, swz, rows_per_wg); \
     else hipLaunchKernelGGL((u1_heads_kstream_h_kernel<HT, X, F, C, 1>), grid, block, 0, st, a, swz, rows_per_wg);                 \
   } while (0)
-  if (!xupd) { if (forward) L2Q_KS(false, true, false); else L2Q_KS(false, false, false); }
-  else if (use_ncp) { if (forward) L2Q_KS(true, true, true); else L2Q_KS(true, false, true); }
-  else { if (forward) L2Q_KS(true, true, false); else L2Q_KS(true, false, false); }
+  L2Q_WITH_HALF(half_type,
+    if (!xupd) { if (forward) L2Q_KS(false, true, false); else L2Q_KS(false, false, false); }
+    else if (use_ncp) { if (forward) L2Q_KS(true, true, true); else L2Q_KS(true, false, true); }
+    else { if (forward) L2Q_KS(true, true, false); else L2Q_KS(true, false, false); });
 #undef L2Q_KS
   hipLaunchKernelGGL(kstream_finalize_kernel, dim3((unsigned)cdiv(a.M, kBlock / 64)), dim3(kBlock), 0, st,
                      (const double*)a.logdet_part, a.ncols_part, a.M, logdet, accumulate);
   return true;
 }
-
-template bool heads_h_kstream_launch<_Float16>(HeadsHArgs, int, int, int, int, float*, int, hipStream_t, bool);
-template bool heads_h_kstream_launch<__bf16>(HeadsHArgs, int, int, int, int, float*, int, hipStream_t, bool);
 
 }  // namespace l2q

@@ -137,8 +137,12 @@ void launch_finalize(const double* partial, double* out, int nb, long nblk, int 
 // trajectory came out NaN; profiles/r05k_graph_memset_node.txt).  No launch path of this library records a memset node.
 void launch_zero(void* p, size_t bytes, hipStream_t st);
 
-// gemm_lt.hip: the shapes the hipBLASLt route of the plain 16-bit layers takes, and whether the library loaded
-bool gemm_h_lt_shape(int M, int N, long K);
-bool gemm_h_lt_available();
+// what l2q_kernel_name (su3_kernels.hip) answers for the fp64 dense layers, from the file that launches them: gemm.hip
+// (for shapes with whole 16-wide K-slabs and aligned operands, which every SU(3) vnet has)
+const char* gemm_f64_kernel_name();
+const char* heads_f64_kernel_name();
+
+// 16-byte aligned, or absent
+inline bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace l2q

@@ -5,6 +5,7 @@
 // registers (su3_math.hpp).  Stencil neighbours are re-read through L1/L2; the 1-D grids
 // are XCD-swizzled so the blocks that share a chain's links share an XCD's L2.
 #include "su3_launch.hpp"
+#include "half_common.hpp"
 
 namespace l2q {
 
@@ -949,7 +950,6 @@ extern "C" {
 
 int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, size_t buf_bytes) {
   L2Q_REQUIRE(entry && buf && buf_bytes > 0, L2Q_EINVAL, "null pointer");
-  const Tuning& t = tuning();
   const Dims dd = strncmp(entry, "l2q_su3_", 8) ? Dims{} : make_dims(T, X, Y, Z);   // (other entries: not a lattice)
   buf[0] = 0;
   if (!strcmp(entry, "l2q_su3_plaq_reduce")) {
@@ -971,15 +971,13 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
   } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64")) {
     snprintf(buf, buf_bytes, "heads_sliced_kernel");
   } else if (!strncmp(entry, "l2q_vnet_heads_vupdate", 22)) {
-    // (for shapes with whole 16-wide K-slabs, which every SU(3) vnet has)
-    snprintf(buf, buf_bytes, "%s", t.heads_dma ? "fused_heads_dma_kernel" : "fused_heads_vupdate_kernel");
+    snprintf(buf, buf_bytes, "%s", heads_f64_kernel_name());
   } else if (!strcmp(entry, "l2q_gemm_h")) {
-    // (T, X, Y) carry (M, N, K) here: "hipblaslt" when the plain-layer route of gemm_lt.hip takes the shape
-    if (gemm_h_lt_shape(T, X, (long)Y) && gemm_h_lt_available()) snprintf(buf, buf_bytes, "hipblaslt");
+    snprintf(buf, buf_bytes, "%s", gemm_h_kernel_name(T, X, (long)Y));      // (T, X, Y) carry (M, N, K) here
   } else if (!strcmp(entry, "l2q_gemm_sliced_f64")) {
     snprintf(buf, buf_bytes, "gemm_sliced_kernel");
   } else if (!strcmp(entry, "l2q_gemm_f64")) {
-    snprintf(buf, buf_bytes, "%s", t.heads_dma ? "gemm_dma_f64_kernel" : "gemm_nt_kernel");
+    snprintf(buf, buf_bytes, "%s", gemm_f64_kernel_name());
   }
   return L2Q_OK;
 }

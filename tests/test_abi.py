@@ -108,6 +108,15 @@ def test_half_layer_kernel_plan_host_logic():
         assert q(512, 256, 8192, 8192, 0) == 0             # too few chains
         assert q(8192, 256, 1024, 1024, 0) == 0            # short K: the tile kernels
         assert q(8192, 256, 16385, 8192, 1) == 0           # odd K for the cos | sin form
+        # workspace on either side of the streaming kernel's M / N / K bounds (8 splits of partial sums + the copy of W
+        # inside them, the tile kernels' split-K partials outside) and of the hipBLASLt route's K bound
+        w = lib.l2q_gemm_h_ws_bytes
+        assert w(1024, 256, 4096, 0) == 8 * 1024 * 256 * 4 + 256 * 4096 * 2 and w(1023, 256, 4096, 0) == 9427968
+        assert w(1024, 257, 4096, 0) == 9474048 and w(1024, 256, 4095, 0) == 8388608
+        assert w(2048, 2048, 2048, 0) == (64 << 20) + 2048 * 2048 * 2 + 256 and w(2048, 2048, 2047, 0) == 0
+        # the kernel-name query answers any sizes: no kernel for a layer that is none
+        for mnk in ((0, 0, 0), (0, 0, 4096), (0, 2048, 4096), (-5, 256, 4096), (2048, 2048, 0)):
+            assert native.kernel_name('l2q_gemm_h', (*mnk, 0)) == '', mnk
         lib.l2q_set_tuning(b'gemm_h_skinny', 8)
         assert q(8192, 256, 8192, 8192, 0) == 8
         need = lib.l2q_gemm_h_ws_bytes(8192, 256, 8192, 8192)
