@@ -217,6 +217,34 @@ int l2q_su3_flow_stage(const void* x_in, const void* p_in, double c, double s, v
 int l2q_su3_flow_step(const void* x_in, void* x_out, void* ws_p, void* ws_x, double eps, int nb, int T, int X,
                       int Y, int Z, void* stream);
 
+/* ---------------------------------------------------------------- Wilson loops R x T and Polyakov loops */
+/* A line is L_mu(x, n) = U_mu(x) U_mu(x + mu) ... U_mu(x + (n-1) mu), periodic; a field of lines has the shape and the
+ * native layout xn[chain][mu][e][site] of a link field, and L(., 1) is the links.  One more link on every line:
+ *   lines_out_mu(x) = lines_in_mu(x) U_mu(x + n mu)      for all four mu, n >= 0 taken modulo the extent
+ * (n = the length of the lines in lines_in makes them one longer).  lines_out may alias lines_in: each site reads and
+ * writes only its own entry of it.  lines_out must not alias xn, which is read at another site.  Replaces a
+ * torch.roll of the unpacked links and a batched 3x3 matmul per link added.  Streaming; algorithmic traffic:
+ * 3 x 576 B per (chain, site). */
+int l2q_su3_line_extend(const void* lines_in, const void* xn, int n, void* lines_out, int nb, int T, int X, int Y,
+                        int Z, void* stream);
+/* Sums of planar loops closed from two line fields, a of length r and b of length t (r, t >= 1): for the 12 ordered
+ * pairs mu != nu, in the plaquette convention P_{mu nu}(x) = U_mu(x) U_nu(x+mu) U_mu(x+nu)^H U_nu(x)^H,
+ *   W_{mu nu}(x) = a_mu(x) b_nu(x + r mu) a_mu(x + t nu)^H b_nu(x)^H
+ *   out[c][k][0|1] = sum_x Re | Im tr W_{mu nu}(x),      k = 3 mu + (nu < mu ? nu : nu - 1)
+ * a = b = the links with r = t = 1 gives the plaquette sums: pairs mu > nu are the planes of l2q_su3_plaq_planes,
+ * pairs mu < nu their conjugates.  The shifts are taken modulo the extents, so r or t equal to or beyond an extent
+ * is legal and wraps; any lattice (extents 1 and 2 included); a and b may be the same field.  Two-stage reduction as
+ * l2q_su3_plaq_planes: ws >= nb * ceil(V/256) * 24 doubles (6 x l2q_reduce_ws_bytes(nb, V) covers it).  Replaces, per
+ * (r, t), four torch.roll and three batched 3x3 matmuls over the unpacked fields for each of the 12 pairs.
+ * Algorithmic traffic: 2 x 576 B per (chain, site) (a and b once each; the shifted operands are re-reads). */
+int l2q_su3_loop_reduce(const void* a, int r, const void* b, int t, double* out, int nb, int T, int X, int Y, int Z,
+                        void* ws, size_t ws_bytes, void* stream);
+/* Polyakov loops in direction mu (0..3): out[c][x_perp] = tr prod_{k < N_mu} U_mu(x_perp, x_mu = k), complex128, not
+ * divided by 3; the perpendicular sites are in the lattice's own order with direction mu removed ([nb][X][Y][Z] for
+ * mu = 0).  Extent 1 gives tr U.  Replaces N_mu - 1 batched matmuls over slices of the unpacked links.  Algorithmic
+ * traffic: 144 B per (chain, site) read, 16 B per (chain, perpendicular site) written. */
+int l2q_su3_polyakov(const void* xn, int mu, void* out, int nb, int T, int X, int Y, int Z, void* stream);
+
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:
  *   forward : v' = exp(eps s/2) v - (eps/2) (F exp(eps q) + t),  logdet[c] =  sum eps s/2

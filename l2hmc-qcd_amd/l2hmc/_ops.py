@@ -282,6 +282,40 @@ def su3_flow_step_n(xn: torch.Tensor, x_out: torch.Tensor, ws_p: torch.Tensor, w
     return x_out
 
 
+def su3_line_extend_n(lines: torch.Tensor, xn: torch.Tensor, n: int, lat: Sequence[int],
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out_mu(x) = lines_mu(x) U_mu(x + n mu) for all four mu (n >= 0, modulo the extent): lines of length n become
+    lines of length n + 1.  out None = a new field; out may be `lines` itself (in place), never xn."""
+    T, X, Y, Z = (int(i) for i in lat)
+    out = torch.empty_like(xn) if out is None else out
+    N.call('l2q_su3_line_extend', lines, xn, int(n), out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_loop_sums_n(a: torch.Tensor, r: int, b: torch.Tensor, t: int, lat: Sequence[int]) -> torch.Tensor:
+    """[nb, 12] complex128: sum over sites of tr W_{mu nu}, W = a_mu(x) b_nu(x + r mu) a_mu(x + t nu)^H b_nu(x)^H,
+    for the ordered pairs mu != nu at index 3 mu + (nu if nu < mu else nu - 1); a, b line fields of lengths r, t."""
+    nb = a.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    out = torch.empty((nb, 12, 2), dtype=torch.float64, device=a.device)
+    ws = N.workspace(N.reduce_ws_bytes(nb, T * X * Y * Z) * 6, a.device)
+    N.call('l2q_su3_loop_reduce', a, int(r), b, int(t), out, nb, T, X, Y, Z, ws, ws.numel())
+    return torch.view_as_complex(out)
+
+
+def su3_polyakov_n(xn: torch.Tensor, mu: int, lat: Sequence[int]) -> torch.Tensor:
+    """[nb, *perp] complex128: tr of the product of the links U_mu around direction mu, per site of the lattice
+    with direction mu removed (not divided by 3)."""
+    nb = xn.shape[0]
+    lat = [int(i) for i in lat]
+    mu = int(mu)
+    if not 0 <= mu < 4:
+        raise ValueError(f'su3_polyakov_n: mu must be 0..3, got {mu}')
+    out = torch.empty((nb, *lat[:mu], *lat[mu + 1:]), dtype=C128, device=xn.device)
+    N.call('l2q_su3_polyakov', xn, mu, out, nb, *lat)
+    return out
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

@@ -64,6 +64,27 @@ def _site_sum(w: Tensor) -> Tensor:
     return w.sum(tuple(range(2, len(w.shape)))).sum(0)
 
 
+def _log_positive(arg: Tensor) -> Tensor:
+    """ln(arg) where arg is positive and finite, NaN elsewhere"""
+    ok = (arg > 0) & torch.isfinite(arg)
+    return torch.where(ok, torch.log(torch.where(ok, arg, torch.ones_like(arg))), torch.full_like(arg, float('nan')))
+
+
+def creutz_ratios(w: Tensor) -> Tensor:
+    """chi(R, T) = -ln[W(R, T) W(R-1, T-1) / (W(R, T-1) W(R-1, T))] for R, T >= 2 from a table w[..., rmax, tmax] with
+    w[..., R-1, T-1] = W(R, T): [..., rmax-1, tmax-1], entry [R-2, T-2].  An area law W = exp(-sigma R T - m (R + T) - c)
+    gives sigma everywhere.  NaN where the argument of the logarithm is not positive; never raises."""
+    w = torch.as_tensor(w)
+    return -_log_positive(w[..., 1:, 1:] * w[..., :-1, :-1] / (w[..., 1:, :-1] * w[..., :-1, 1:]))
+
+
+def static_potential(w: Tensor) -> Tensor:
+    """V(R; T) = ln[W(R, T) / W(R, T+1)] from a table w[..., rmax, tmax]: [..., rmax, tmax-1], entry [R-1, T-1]; the
+    static potential is its plateau at large T.  NaN where the ratio is not positive; never raises."""
+    w = torch.as_tensor(w)
+    return _log_positive(w[..., :, :-1] / w[..., :, 1:])
+
+
 class LatticeSU3(Lattice):
     """4D lattice with SU(3) links: x.shape = [nb, 4, nt, nx, ny, nz, 3, 3] complex128."""
     dim = 4
@@ -188,6 +209,85 @@ class LatticeSU3(Lattice):
             out[name] = torch.stack([getattr(r, name) for r in rows])
         out['t2E'] = tt[:, None] ** 2 * out['E']
         return out
+
+    # ------------------------------------------------------------ Wilson loops R x T and Polyakov loops
+    def wilson_loop_sums_n(self, xn: Tensor, rmax: int, tmax: int) -> Tensor:
+        """[nb, rmax, tmax, 12] complex: entry [R-1, T-1, k] = sum over sites of tr W_{mu nu}(R, T), the loop with R links
+        along mu and T links along nu, k = 3 mu + (nu if nu < mu else nu - 1).  The lines along mu grow by one link
+        per R and the lines along nu by one link per T (`l2q_su3_line_extend`), in at most two fields beyond xn, which
+        is never written; one `l2q_su3_loop_reduce` per (R, T)."""
+        self._no_grad(xn, 'wilson_loop_sums_n')
+        rmax, tmax = int(rmax), int(tmax)
+        if rmax < 1 or tmax < 1:
+            raise ValueError(f'wilson_loop_sums_n: need rmax, tmax >= 1, got {rmax}, {tmax}')
+        L = self._lattice_shape
+        out = torch.empty((xn.shape[0], rmax, tmax, 12), dtype=torch.complex128, device=xn.device)
+        a, b_buf = xn, None
+        for r in range(1, rmax + 1):
+            if r > 1:       # a: lines of length r - 1 -> r (the first time into a new field, then in place)
+                a = ops.su3_line_extend_n(a, xn, r - 1, L, out=None if a is xn else a)
+            b = xn
+            for t in range(1, tmax + 1):
+                if t > 1:
+                    b_buf = torch.empty_like(xn) if b_buf is None else b_buf
+                    b = ops.su3_line_extend_n(b, xn, t - 1, L, out=b_buf)
+                out[:, r - 1, t - 1] = ops.su3_loop_sums_n(a, r, b, t, L)
+        return out
+
+    def _loop_extents(self, time_dir: Optional[int]) -> tuple[int, int]:
+        """the smallest extents that the R lines and the T lines of `wilson_loop_table` run along"""
+        L = [int(i) for i in self._lattice_shape]
+        if time_dir is None:
+            return min(L), min(L)
+        time_dir = int(time_dir)
+        if not 0 <= time_dir < 4:
+            raise ValueError(f'wilson_loop_table: time_dir must be 0..3 or None, got {time_dir}')
+        return min(n for d, n in enumerate(L) if d != time_dir), L[time_dir]
+
+    def wilson_loop_table(self, x: Tensor, rmax: int, tmax: int, time_dir: Optional[int] = 0) -> Tensor:
+        """W(R, T) [nb, rmax, tmax] real: the mean over sites and over the three pairs (mu != time_dir, nu = time_dir)
+        of Re tr W_{mu nu}(R, T) / 3; with time_dir None the mean over all 12 ordered pairs.  Loops that would wrap
+        around the lattice are refused: ValueError when rmax or tmax is below 1 or exceeds the smallest extent its
+        lines run along.  Measured on smeared links by passing `flow(x, t)`."""
+        self._no_grad(x, 'wilson_loop_table')
+        rmax, tmax = int(rmax), int(tmax)
+        rlim, tlim = self._loop_extents(time_dir)
+        if not (1 <= rmax <= rlim and 1 <= tmax <= tlim):
+            raise ValueError(f'wilson_loop_table: need 1 <= rmax <= {rlim} and 1 <= tmax <= {tlim} on lattice '
+                             f'{list(self._lattice_shape)} with time_dir = {time_dir}, got rmax = {rmax}, tmax = {tmax}')
+        s = self.wilson_loop_sums_n(self.pack(x), rmax, tmax).real
+        if time_dir is not None:
+            td = int(time_dir)
+            s = s[..., [3 * mu + (td if td < mu else td - 1) for mu in range(4) if mu != td]]
+        return s.mean(-1) / (3.0 * self.volume)
+
+    def polyakov_loops(self, x: Tensor, mu: int = 0) -> Tensor:
+        """P(x_perp) = tr prod_k U_mu(x_perp, x_mu = k) / 3, [nb, *perp] complex: the lattice with direction mu removed"""
+        self._no_grad(x, 'polyakov_loops')
+        return ops.su3_polyakov_n(self.pack(x), mu, self._lattice_shape) / 3.0
+
+    def polyakov(self, x: Tensor, mu: int = 0) -> Tensor:
+        """[nb] complex: the mean of `polyakov_loops` over the perpendicular sites (the order parameter of the centre
+        symmetry)"""
+        p = self.polyakov_loops(x, mu)
+        return p.reshape(p.shape[0], -1).mean(-1)
+
+    def polyakov_correlator(self, x: Tensor, mu: int = 0) -> Tensor:
+        """C(r) = (1 / V_perp) sum_y Re P(y) conj P(y + r), [nb, *perp] real, periodic in r; C(0) = mean |P|^2.  The sum
+        over y is a circular correlation, taken by torch.fft on the device."""
+        p = self.polyakov_loops(x, mu)
+        dims = (1, 2, 3)
+        f = torch.fft.fftn(p, dim=dims)
+        vp = p[0].numel()
+        return torch.fft.ifftn(f.real ** 2 + f.imag ** 2, dim=dims).real / vp
+
+    def polyakov_metrics(self, x: Tensor, xinit: Optional[Tensor] = None) -> dict[str, Tensor]:
+        """{'ploop': |polyakov(x, 0)|} and, with xinit, 'dploop' = | |polyakov(x, 0)| - |polyakov(xinit, 0)| | after it:
+        the entries to append to `calc_metrics` when the Polyakov loop is monitored."""
+        metrics = {'ploop': self.polyakov(x, 0).abs()}
+        if xinit is not None:
+            metrics['dploop'] = (metrics['ploop'] - self.polyakov(xinit, 0).abs()).abs()
+        return metrics
 
     # ------------------------------------------------------------ reference API
     def coeffs(self, beta: Tensor) -> dict[str, Tensor]:
