@@ -732,6 +732,17 @@ int l2q_su3_plaq_bwd(const void* xn, const double* w, void* gx, int nb, int T, i
  * out like that function's output (torch's cotangent of a complex tensor: dL/dRe + i dL/dIm).  gx += dL/dx. */
 int l2q_su3_wilson_loops_bwd(const void* xn, const void* w, void* gx, int nb, int T, int X, int Y, int Z,
                              void* stream);
+/* VJP of l2q_su3_clover_reduce: L = sum_c sum_k w[c][k] out[c][k] with out that function's raw [nb][3] output
+ * (-sum tr F F, -sum tr(F01 F23 - F02 F13 + F03 F12), sum Re tr P), w [nb][3] real on the device.  gx += dL/dx in
+ * the layout and cotangent convention of l2q_su3_plaq_bwd (native [nb][4][9][V] complex128, dL/dRe + i dL/dIm, the
+ * links as unconstrained complex 3x3 matrices).  Two gathers, no atomics: pass 1 writes -1/4 (2 w0 F + w1 Fdual) per
+ * site and plane into ws, pass 2 has one thread per link collect its 24 inserted loops and 6 staples.  A chain's
+ * result is bit-identical alone and in a batch, and from run to run.  Takes any lattice l2q_su3_clover_reduce takes.
+ * xn, gx and ws are three different buffers; ws >= nb * 54 * V doubles (432 B per (chain, site)).  Algorithmic
+ * traffic: 3168 B per (chain, site) = pass 1 576 (links) + 432 (ws written), pass 2 576 (links) + 432 (ws) + 1152
+ * (gx read and written). */
+int l2q_su3_clover_bwd(const void* xn, const double* w, void* gx, int nb, int T, int X, int Y, int Z, void* ws,
+                       size_t ws_bytes, void* stream);
 /* ---- improved gauge actions (c1 != 0: Iwasaki / DBW2 rectangles), lattice/su3/pytorch/lattice.py
  * :83-112 (coeffs, _rectangles), :180-196 (rectangle traces of _wilson_loops), :252-269 (action):
  *   S = -(1/3) [ beta (1 - 8 c1) sum_P Re tr P + beta c1 sum_R Re tr R ],  12 planar 2x1 loops R

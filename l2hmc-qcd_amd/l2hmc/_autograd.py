@@ -83,6 +83,25 @@ class SU3WilsonLoops(torch.autograd.Function):
         return ops.su3_unpack(gx, ctx.lat).reshape(ctx.shape), None
 
 
+class SU3CloverSums(torch.autograd.Function):
+    """x -> [nb, 3] raw clover sums (-sum tr F F, -sum tr(F01 F23 - F02 F13 + F03 F12), sum Re tr P):
+    `l2q_su3_clover_reduce` forward, `l2q_su3_clover_bwd` backward."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, lat: Sequence[int]):
+        xn = su3_pack_cached(x)
+        ctx.save_for_backward(xn)
+        ctx.lat, ctx.shape = tuple(int(i) for i in lat), x.shape
+        return ops.su3_clover_sums_n(xn, lat)
+
+    @staticmethod
+    def backward(ctx, g):
+        (xn,) = ctx.saved_tensors
+        gx = torch.zeros_like(xn)
+        ops.su3_clover_bwd_(gx, xn, g.contiguous(), ctx.lat)
+        return ops.su3_unpack(gx, ctx.lat).reshape(ctx.shape), None
+
+
 class U1WilsonLoops(torch.autograd.Function):
     """x [nb, 2, T, X] -> theta [nb, T, X] (lattice/u1/pytorch/lattice.py:154-159), a linear map:
     `l2q_u1_wilson_loops` forward, its adjoint `l2q_u1_wilson_loops_bwd` backward."""

@@ -1400,6 +1400,19 @@ def su3_wilson_loops_bwd_(gx: torch.Tensor, xn: torch.Tensor, w: torch.Tensor,
     return gx
 
 
+def su3_clover_bwd_(gx: torch.Tensor, xn: torch.Tensor, w: torch.Tensor,
+                    lat: Sequence[int]) -> torch.Tensor:
+    """gx += VJP of `su3_clover_sums_n` at xn for the cotangent w [nb, 3] float64 (`l2q_su3_clover_bwd`).  The
+    kernel's per-site field (54 doubles per (chain, site)) is a tensor of its own, not the shared reduction
+    workspace: at a training shape it is hundreds of MB, which the allocator should get back."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    ws = torch.empty(nb * 54 * T * X * Y * Z, dtype=torch.float64, device=xn.device)
+    N.call('l2q_su3_clover_bwd', xn, w.to(torch.float64).contiguous(), gx, nb, T, X, Y, Z, ws,
+           ws.numel() * ws.element_size())
+    return gx
+
+
 def su3_rect_sums_n(xn: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
     """[nb]: sum over sites and the 12 planar 2x1 loops of Re tr R (c1 != 0 actions)."""
     nb = xn.shape[0]

@@ -297,11 +297,21 @@ class LossConfig(BaseConfig):
     rmse_weight: float = 0.0
     plaq_weight: float = 0.0
     aux_weight: float = 0.0
+    # the charge of the charge term: 'plaq' = the reference's sinQ (sum Im tr P / 18 V), 'clover' = the clover
+    # topological charge of a 4D SU(3) lattice (LatticeSU3.clover_autograd)
+    charge_kind: str = 'plaq'
+
+    def __post_init__(self):
+        if self.charge_kind not in ('plaq', 'clover'):
+            raise ValueError(f"LossConfig.charge_kind must be 'plaq' or 'clover', got {self.charge_kind!r}")
 
     def to_str(self) -> str:
-        return '_'.join([f'qw-{self.charge_weight:2.1f}', f'pw-{self.plaq_weight:2.1f}',
-                         f'rw-{self.rmse_weight:2.1f}', f'aw-{self.aux_weight:2.1f}',
-                         f'mixed-{self.use_mixed_loss}'])
+        parts = [f'qw-{self.charge_weight:2.1f}', f'pw-{self.plaq_weight:2.1f}',
+                 f'rw-{self.rmse_weight:2.1f}', f'aw-{self.aux_weight:2.1f}',
+                 f'mixed-{self.use_mixed_loss}']
+        if self.charge_kind != 'plaq':
+            parts.append(f'qk-{self.charge_kind}')
+        return '_'.join(parts)
 
 
 @dataclass

@@ -19,7 +19,8 @@ SU(3) uses the same tape with the cotangent kernels of ``csrc/su3_train_kernels.
 ``l2q_su3_expm_mul_bwd`` (Frechet derivative of the matrix exponential), ``l2q_su3_projsu_vec8_bwd``
 (polar-projection derivative solved in a Jacobi eigenbasis), ``l2q_su3_force_bwd`` (the reference
 differentiates the force only through the ``x^H`` factor of ``TAH(dS/dx x^H)``,
-lattice/su3/pytorch/lattice.py:299-308), ``l2q_su3_plaq_bwd`` and ``l2q_v_update_bwd_c128``.
+lattice/su3/pytorch/lattice.py:299-308), ``l2q_su3_plaq_bwd`` and ``l2q_v_update_bwd_c128``; with
+``loss.charge_kind=clover`` the loss also seeds ``l2q_su3_clover_bwd`` (csrc/su3_clover_bwd.hip).
 The vnet runs on reference-ordered 8-component inputs (transposes at its boundary) so that the
 ordinary ``LeapfrogLayer.backward`` accumulates into the checkpoint-ordered parameters.
 """
@@ -670,7 +671,15 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
     if c1 != 0.0:                       # rectangle term of the improved action (potential only)
         rs_p = ops.su3_rect_sums_n(x_prop, lat).clone().requires_grad_(True)
         leaves.append(rs_p)
+    clover = getattr(loss_fn, 'charge_kind', 'plaq') == 'clover' and loss_fn.charge_weight > 0
+    q_i = q_p = None
+    if clover:                          # the charge term on the clover charge: one more [nb, 3] leaf
+        cs_p = ops.su3_clover_sums_n(x_prop, lat).clone().requires_grad_(True)
+        leaves.append(cs_p)
+        q_i = loss_fn.lattice.clover_n(xn_init).Q
     with torch.enable_grad():
+        if clover:
+            q_p = loss_fn.lattice._clover_of_sums(cs_p).Q
         h_prop = ke_p + (-beta * (1.0 - 8.0 * c1) / 3.0) * pl_p[:, :, 0].sum(1)
         if c1 != 0.0:
             h_prop = h_prop + (-beta * c1 / 3.0) * rs_p
@@ -678,7 +687,7 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
         if getattr(tape, 'swapped', False):
             dh = h_prop - tape.h_init.detach() + sld
         acc = torch.exp(torch.minimum(dh, torch.zeros_like(dh)))
-        loss = loss_fn.loss_from_sums_su3(pl_i, pl_p, d2, acc, nelem=x_prop[0].numel())
+        loss = loss_fn.loss_from_sums_su3(pl_i, pl_p, d2, acc, nelem=x_prop[0].numel(), q_init=q_i, q_prop=q_p)
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
     g_pl, g_ke, g_d2, g_sld = grads[:4]
     gx = torch.zeros_like(x_prop)
@@ -686,6 +695,8 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
         ops.su3_plaq_bwd_(gx, x_prop, g_pl, lat)
     if c1 != 0.0 and grads[4] is not None:
         ops.su3_rect_bwd_(gx, x_prop, grads[4], lat)
+    if clover and grads[-1] is not None:
+        ops.su3_clover_bwd_(gx, x_prop, grads[-1], lat)
     if g_d2 is not None:
         ops.diff_bwd_(gx, x_prop, xn_init, g_d2)
     gv = torch.zeros_like(v_prop)

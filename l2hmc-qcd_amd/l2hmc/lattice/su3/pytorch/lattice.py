@@ -130,14 +130,23 @@ class LatticeSU3(Lattice):
         return ops.su3_rect_force_add_n(xn, b * self.c1 / 3.0, f, self._lattice_shape)
 
     # ------------------------------------------------------------ Wilson flow and clover observables
-    def clover_n(self, xn: Tensor) -> Clover:
-        s = ops.su3_clover_sums_n(xn, self._lattice_shape)
+    def _clover_of_sums(self, s: Tensor) -> Clover:
         return Clover(E=s[:, 0] / self.volume, Q=s[:, 1] / (4 * np.pi ** 2),
                       Eplaq=36.0 - (2.0 / self.volume) * s[:, 2])
+
+    def clover_n(self, xn: Tensor) -> Clover:
+        return self._clover_of_sums(ops.su3_clover_sums_n(xn, self._lattice_shape))
 
     def clover(self, x: Tensor) -> Clover:
         """Clover energy density, topological charge and plaquette energy density of x (reference layout)."""
         self._no_grad(x, 'clover')
+        return self.clover_n(self.pack(x))
+
+    def clover_autograd(self, x: Tensor) -> Clover:
+        """`clover(x)`, differentiable where x requires a gradient (`l2q_su3_clover_bwd` behind it, the links as
+        unconstrained complex matrices); the same kernel and the same numbers as `clover(x)` otherwise."""
+        if AG.wants_grad(x):
+            return self._clover_of_sums(AG.SU3CloverSums.apply(x.to(DEVICE), self._lattice_shape))
         return self.clover_n(self.pack(x))
 
     def topological_charge(self, x: Tensor) -> Tensor:

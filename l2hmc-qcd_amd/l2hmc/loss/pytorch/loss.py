@@ -39,6 +39,11 @@ class LatticeLoss:
             self.g = SU3()
         else:
             raise ValueError(f'Unexpected lattice: {type(lattice)}')
+        self.charge_kind = getattr(self.config, 'charge_kind', 'plaq')
+        if self.charge_kind not in ('plaq', 'clover'):
+            raise ValueError(f"charge_kind must be 'plaq' or 'clover', got {self.charge_kind!r}")
+        if self.charge_kind == 'clover' and not isinstance(self.lattice, LatticeSU3):
+            raise ValueError("charge_kind = 'clover' needs a 4D SU(3) lattice: U(1) has no clover charge")
 
     def __call__(self, x_init: Tensor, x_prop: Tensor, acc: Tensor) -> Tensor:
         return self.calc_loss(x_init=x_init, x_prop=x_prop, acc=acc)
@@ -77,6 +82,10 @@ class LatticeLoss:
 
     def charge_loss(self, x_init: Tensor, x_prop: Tensor, acc: Tensor,
                     use_mixed_loss: Optional[bool] = None) -> Tensor:
+        if self.charge_kind == 'clover':
+            # the clover topological charge in place of sinQ (differentiable: l2q_su3_clover_bwd)
+            q1, q2 = self.lattice.clover_autograd(x_init).Q, self.lattice.clover_autograd(x_prop).Q
+            return self._mixed(acc.to(DEVICE) * (q2 - q1) ** 2, self.charge_weight, use_mixed_loss)
         q1 = self.lattice._sin_charges(self.lattice.plaq_sums(x_init))
         q2 = self.lattice._sin_charges(self.lattice.plaq_sums(x_prop))
         return self._mixed(acc.to(DEVICE) * (q2 - q1) ** 2, self.charge_weight, use_mixed_loss)
@@ -150,10 +159,12 @@ class LatticeLoss:
         return total
 
     def loss_from_sums_su3(self, planes_init: Tensor, planes_prop: Tensor, d2: Tensor, acc: Tensor,
-                           nelem: int) -> Tensor:
+                           nelem: int, q_init: Optional[Tensor] = None,
+                           q_prop: Optional[Tensor] = None) -> Tensor:
         """SU(3) training loss from per-chain reductions: planes_* [nb, 6, 2] = per-plane
         (sum Re tr P, sum Im tr P), d2 [nb] = sum |x' - x|^2.  Same value as `calc_loss`
-        (loss.py:56-148, 194-210), differentiable torch ops on small tensors only."""
+        (loss.py:56-148, 194-210), differentiable torch ops on small tensors only.  With
+        charge_kind = 'clover' the charge term takes the per-chain clover charges q_init, q_prop [nb]."""
         assert isinstance(self.lattice, LatticeSU3)
         total = torch.zeros((), dtype=acc.dtype, device=acc.device)
         if self.rmse_weight > 0:
@@ -164,8 +175,13 @@ class LatticeLoss:
             # the reference's _plaq_loss takes use_mixed_loss=None literally -> not mixed
             total = total + (-ploss / self.plaq_weight.to(acc.device)).mean()
         if self.charge_weight > 0:
-            norm = 6 * 3 * self.lattice.volume
-            q1, q2 = planes_init[:, :, 1].sum(1) / norm, planes_prop[:, :, 1].sum(1) / norm
+            if self.charge_kind == 'clover':
+                if q_init is None or q_prop is None:
+                    raise ValueError("loss_from_sums_su3: charge_kind = 'clover' needs q_init and q_prop")
+                q1, q2 = q_init, q_prop
+            else:
+                norm = 6 * 3 * self.lattice.volume
+                q1, q2 = planes_init[:, :, 1].sum(1) / norm, planes_prop[:, :, 1].sum(1) / norm
             total = total + self._mixed(acc * (q2 - q1) ** 2, self.charge_weight, None)
         return total
 

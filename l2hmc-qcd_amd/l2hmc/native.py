@@ -149,6 +149,7 @@ SIGNATURES = {
     'l2q_su3_force_bwd': (I, [P, P, D, P, I, I, I, I, I, P]),
     'l2q_su3_plaq_bwd': (I, [P, P, P, I, I, I, I, I, P]),
     'l2q_su3_wilson_loops_bwd': (I, [P, P, P, I, I, I, I, I, P]),
+    'l2q_su3_clover_bwd': (I, [P, P, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_rect_reduce': (I, [P, I, I, I, I, I, P, P, Z, P]),
     'l2q_su3_rect_force_add': (I, [P, D, P, I, I, I, I, I, P]),
     'l2q_su3_rect_bwd': (I, [P, P, P, I, I, I, I, I, P]),

@@ -64,6 +64,8 @@ def main():
     ap.add_argument('--torch-clover', action='store_true',
                     help='also time the clover sums written with torch roll / matmul and compare the outputs')
     ap.add_argument('--flow-only', action='store_true', help='only the Wilson-flow / clover rows')
+    ap.add_argument('--clover-bwd', action='store_true',
+                    help='only the clover VJP next to the clover sums and the plaquette VJP')
     ap.add_argument('--nb', type=int, default=256)
     ap.add_argument('--L', type=int, nargs=4, default=[8, 8, 8, 8])
     ap.add_argument('--gemm', action='store_true')
@@ -87,6 +89,17 @@ def main():
         print(f'{name:34s} {t*1e3:8.3f} ms  {gbs:8.1f} GB/s  ({gbs/8000*100:5.1f}% of 8 TB/s)'
               + (f'  {tf:6.2f} TFLOP/s' if flop_per_site else ''), flush=True)
 
+    if a.clover_bwd:
+        # the clover VJP: pass 1 reads the links and writes 54 reals per site (576 + 432 B, 72 products), pass 2 reads
+        # links and those (576 + 432 B) and updates gx (1152 B), 4 links x 6 loops x 8 products; the plaquette VJP
+        # reads the links and updates gx (4 links x 6 staples x 2 products)
+        gx = torch.zeros_like(xn)
+        w3 = torch.randn(nb, 3, dtype=torch.float64, device=dev)
+        w6 = torch.randn(nb, 6, 2, dtype=torch.float64, device=dev)
+        rec('su3_clover_reduce', timeit(lambda: ops.su3_clover_sums_n(xn, L)), 576, 72 * 216)
+        rec('su3_plaq_bwd', timeit(lambda: ops.su3_plaq_bwd_(gx, xn, w6, L)), 1728, 48 * 216)
+        rec('su3_clover_bwd', timeit(lambda: ops.su3_clover_bwd_(gx, xn, w3, L)), 3168, 264 * 216)
+        return
     # Wilson flow / clover observables: the clover pass reads the links once (576 B / site, 72 3x3 products); a flow
     # stage is the force kick (reads X and P, writes P) and the x-update (reads P and X, writes X): 3456 B / site
     rec('su3_clover_reduce', timeit(lambda: ops.su3_clover_sums_n(xn, L)), 576, 72 * 216)
