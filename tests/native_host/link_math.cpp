@@ -4,6 +4,9 @@
 //   frechet    : B (9 complex), G (9 complex)   -> exp(B), L_exp(B)[G]   (Cayley-Hamilton form, ships)
 //   frechet_series : the same pair from the matrix-valued Taylor recursion (kept for A/B)
 //   expm       : A (9 complex)                  -> m3_expm(A)
+//   projsu / proju / tah : X (9 complex)        -> m3_project_su / m3_project_u / m3_tah of X
+//   vec8       : X (9 complex)                  -> m3_to_vec8(m3_project_su(X))  (8 reals)
+//   mul_nn / mul_na / mul_an / mul_aa : A, B    -> op(A) op(B), a = adjoint
 #include <cstdio>
 #include <cstring>
 #include "su3_train_math.hpp"
@@ -46,6 +49,29 @@ int main() {
       if (!read_m3(a)) return 1;
       m3_expm(e, a);
       print_m3(e);
+    } else if (!strcmp(op, "projsu") || !strcmp(op, "proju") || !strcmp(op, "tah")) {
+      M3 x, r;
+      if (!read_m3(x)) return 1;
+      if (op[0] == 't') m3_tah(r, x);
+      else if (op[4] == 'u') m3_project_u(r, x);
+      else m3_project_su(r, x);
+      print_m3(r);
+    } else if (!strcmp(op, "vec8")) {
+      M3 x, r;
+      double v[8];
+      if (!read_m3(x)) return 1;
+      m3_project_su(r, x);
+      m3_to_vec8(v, r);
+      for (int i = 0; i < 8; ++i) printf("%.17g\n", v[i]);
+    } else if (!strncmp(op, "mul_", 4) && strlen(op) == 6) {
+      M3 a, b, c;
+      if (!read_m3(a) || !read_m3(b)) return 1;
+      if (!strcmp(op + 4, "nn")) m3_mul_nn(c, a, b);
+      else if (!strcmp(op + 4, "na")) m3_mul_na(c, a, b);
+      else if (!strcmp(op + 4, "an")) m3_mul_an(c, a, b);
+      else if (!strcmp(op + 4, "aa")) m3_mul_aa(c, a, b);
+      else return 2;
+      print_m3(c);
     } else {
       return 2;
     }
