@@ -743,6 +743,38 @@ int l2q_su3_wilson_loops_bwd(const void* xn, const void* w, void* gx, int nb, in
  * (gx read and written). */
 int l2q_su3_clover_bwd(const void* xn, const double* w, void* gx, int nb, int T, int X, int Y, int Z, void* ws,
                        size_t ws_bytes, void* stream);
+/* ---- reverse sweep of the Wilson flow (csrc/su3_flow_bwd.hip) */
+/* Full VJP of l2q_su3_force, F = (beta/3) TAH(U A(U)): gx += the cotangent of the links for the cotangent gf of F,
+ * with the six staples A differentiated as well (l2q_su3_force_bwd holds them constant, as the reference's HMC does;
+ * the flow's generator Z(V) = -TAH(V A(V)) needs the whole derivative).  Layout and cotangent convention of
+ * l2q_su3_force_bwd / l2q_su3_plaq_bwd (native [nb][4][9][V] complex128, dL/dRe + i dL/dIm, the links as unconstrained
+ * complex 3x3 matrices).  With K_l = (beta/3) TAH(gf_l), L = sum_l Re tr(K_l^H U_l A_l): every plaquette occurs four
+ * times, once started from each of its links with that link's K inserted, so one thread per link gathers the loops of
+ * its 6 plaquettes with 4 insertions each.  No atomics: a chain's result is bit-identical alone and in a batch, and
+ * from run to run.  Takes any lattice l2q_su3_force takes.  gx aliases neither xn nor gf.  Algorithmic traffic:
+ * 2304 B per (chain, site) = links 576 + gf 576 + gx read and written 1152. */
+int l2q_su3_force_vjp(const void* xn, const void* gf, double beta, void* gx, int nb, int T, int X, int Y, int Z,
+                      void* stream);
+/* Reverse of l2q_su3_flow_stage, P_out = P_in + c TAH(X_in A), X_out = exp(s P_out) X_in, from the stage's input
+ * links x_in and its output p_out: gx_in (overwritten) = cotangent of X_in for the cotangent gx_out of X_out; gp is
+ * read and written: the cotangent of P_out on entry (what later stages left there), of P_in on exit (P_in enters with
+ * weight 1, so it is the same field for a stage without P_in).  Two launches, mirroring the forward: l2q_su3_expm_mul_bwd
+ * (its dL/ds goes into ws and is dropped), then l2q_su3_force_vjp at beta = 3 c on gp.  gx_in and gp each alias no
+ * other argument; x_in, p_out and gx_out are only read.  ws >= l2q_su3_flow_stage_bwd_ws_bytes. */
+size_t l2q_su3_flow_stage_bwd_ws_bytes(int nb, int T, int X, int Y, int Z);
+int l2q_su3_flow_stage_bwd(const void* x_in, const void* p_out, double c, double s, const void* gx_out, void* gp,
+                           void* gx_in, int nb, int T, int X, int Y, int Z, void* ws, size_t ws_bytes,
+                           void* stream);
+/* Reverse of one l2q_su3_flow_step of size eps that started from x_in: gx_in (overwritten) = cotangent of x_in for
+ * the cotangent gx_out of the step's result.  Recomputes the three stages from x_in with the forward's kernels,
+ * keeping P1, P2, P3 apart (the forward overwrites P in place), then reverses the stages 3 -> 1 with the cotangent of
+ * P starting at zero.  x_in and gx_out are only read; neither cotangent may alias x_in; gx_in may alias gx_out (gx_out
+ * is consumed by stage 3 before gx_in is written by stage 1); ws aliases none of them.
+ * ws >= l2q_su3_flow_step_bwd_ws_bytes: seven fields of the links' size (X1, X2, P1, P2, P3, gP, one cotangent; the
+ * other cotangent reuses P3) and the stage's scratch, less than eight fields in all. */
+size_t l2q_su3_flow_step_bwd_ws_bytes(int nb, int T, int X, int Y, int Z);
+int l2q_su3_flow_step_bwd(const void* x_in, double eps, const void* gx_out, void* gx_in, int nb, int T, int X,
+                          int Y, int Z, void* ws, size_t ws_bytes, void* stream);
 /* ---- improved gauge actions (c1 != 0: Iwasaki / DBW2 rectangles), lattice/su3/pytorch/lattice.py
  * :83-112 (coeffs, _rectangles), :180-196 (rectangle traces of _wilson_loops), :252-269 (action):
  *   S = -(1/3) [ beta (1 - 8 c1) sum_P Re tr P + beta c1 sum_R Re tr R ],  12 planar 2x1 loops R

@@ -48,17 +48,6 @@ __device__ __forceinline__ void load_ah3(M3& m, const double* __restrict__ g, in
   m.re[5] = r2; m.im[5] = i2; m.re[7] = -r2; m.im[7] = i2;
 }
 
-// U^H of the link at site s
-__device__ __forceinline__ void load_link_adj(M3& m, const double2* __restrict__ f, int V, int s) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double2 d = f[(3 * j + i) * V + s];
-      m.re[3 * i + j] = d.x; m.im[3 * i + j] = -d.y;
-    }
-}
-
 // a f + b g
 __device__ __forceinline__ AH3 ah3_comb(double a, const AH3& f, double b, const AH3& g) {
   AH3 o;
@@ -113,17 +102,10 @@ __global__ __launch_bounds__(kBlock, 2) void su3_clover_g_kernel(const double2* 
 }
 
 // ------------------------------------------------------------------ pass 2: one thread per link
-// Site index that exists only once `dep` does: the loads it addresses cannot be issued before the product that made
-// dep.  Without it hipcc starts all of a loop's operands (3 links, 4 G) ahead of the first product and spills 68
-// registers; the always-taken conditional of clover_plane does not stop it here.  With it one operand is in
-// flight next to the live matrices: 210 registers, no spill.
-__device__ __forceinline__ int site_after(int site, double dep) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(site) : "v"(dep));
-#endif
-  return site;
-}
-
+// Operand loads are tied to the product before them with site_after (su3_links.hpp).  Without it hipcc starts all of
+// a loop's operands (3 links, 4 G) ahead of the first product and spills 68 registers; the always-taken conditional
+// of clover_plane does not stop it here.  With it one operand is in flight next to the live matrices: 210 registers,
+// no spill.
 // acc += sg (G1 S + A2 (G2 A3 A4 + A3 (G3 A4 + A4 G0))) + w2 S: eight products, at most four matrices live next to
 // acc.  LDA2 / LDA3 / LDA4 load the three links of the staple (adjoint where the loop walks them backwards) once
 // their second argument exists, gp is the plane of -1/4 G, c0..c3 the corners.

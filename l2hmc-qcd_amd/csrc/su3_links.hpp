@@ -19,6 +19,26 @@ __device__ __forceinline__ void load_link(M3& m, const double2* __restrict__ f, 
   }
 }
 
+// U^H of the link at site s
+__device__ __forceinline__ void load_link_adj(M3& m, const double2* __restrict__ f, int V, int s) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double2 d = f[(3 * j + i) * V + s];
+      m.re[3 * i + j] = d.x; m.im[3 * i + j] = -d.y;
+    }
+}
+
+// Site index that exists only once `dep` does: the loads it addresses cannot be issued before the product that made
+// dep (the thread-per-link gathers of su3_clover_bwd.hip and su3_flow_bwd.hip keep one operand in flight this way).
+__device__ __forceinline__ int site_after(int site, double dep) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(site) : "v"(dep));
+#endif
+  return site;
+}
+
 __device__ __forceinline__ void store_link(double2* __restrict__ f, int V, int s, const M3& m) {
 #pragma unroll
   for (int e = 0; e < 9; ++e) f[e * V + s] = make_double2(m.re[e], m.im[e]);

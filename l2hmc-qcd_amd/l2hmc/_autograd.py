@@ -102,6 +102,26 @@ class SU3CloverSums(torch.autograd.Function):
         return ops.su3_unpack(gx, ctx.lat).reshape(ctx.shape), None
 
 
+class SU3Flow(torch.autograd.Function):
+    """x -> x after `nsteps` Wilson-flow steps of size eps, reference layout in and out (the native original of the
+    result attached): `l2q_su3_flow_step` forward, `l2q_su3_flow_step_bwd` over the steps in reverse backward.
+    Checkpoint per step, recompute within the step: the forward keeps the native links entering each step (nsteps
+    fields), the backward needs 9 more (cotangent in and out, and the step's workspace of 7 and a little)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, lat: Sequence[int], nsteps: int, eps: float):
+        ctx.lat, ctx.shape, ctx.eps = tuple(int(i) for i in lat), x.shape, float(eps)
+        flowed, cps = ops.su3_flow_checkpoints_n(su3_pack_cached(x), int(nsteps), ctx.eps, ctx.lat)
+        ctx.save_for_backward(*cps)
+        return attach_native(ops.su3_unpack(flowed, ctx.lat).reshape(x.shape), flowed)
+
+    @staticmethod
+    def backward(ctx, g):
+        gn = ops.su3_pack(g.reshape(g.shape[0], -1))
+        gx = ops.su3_flow_bwd_n(ctx.saved_tensors, ctx.eps, gn, ctx.lat)
+        return ops.su3_unpack(gx, ctx.lat).reshape(ctx.shape), None, None, None
+
+
 class U1WilsonLoops(torch.autograd.Function):
     """x [nb, 2, T, X] -> theta [nb, T, X] (lattice/u1/pytorch/lattice.py:154-159), a linear map:
     `l2q_u1_wilson_loops` forward, its adjoint `l2q_u1_wilson_loops_bwd` backward."""

@@ -282,6 +282,20 @@ def su3_flow_step_n(xn: torch.Tensor, x_out: torch.Tensor, ws_p: torch.Tensor, w
     return x_out
 
 
+def su3_flow_checkpoints_n(xn: torch.Tensor, nsteps: int, eps: float, lat: Sequence[int]):
+    """`nsteps` Wilson-flow steps of size eps that keep the field entering each step: -> (flowed, checkpoints) with
+    checkpoints[k] the native links entering step k (checkpoints[0] is xn itself, which is never written) -- what
+    `su3_flow_bwd_n` reverses.  The same launches as a flow that keeps nothing, so the same bits; nsteps = 0 returns
+    (xn, [])."""
+    cps, cur = [], xn
+    if int(nsteps) > 0:
+        ws_p, ws_x = torch.empty_like(xn), torch.empty_like(xn)
+        for _ in range(int(nsteps)):
+            cps.append(cur)
+            cur = su3_flow_step_n(cur, torch.empty_like(xn), ws_p, ws_x, eps, lat)
+    return cur, cps
+
+
 def su3_line_extend_n(lines: torch.Tensor, xn: torch.Tensor, n: int, lat: Sequence[int],
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out_mu(x) = lines_mu(x) U_mu(x + n mu) for all four mu (n >= 0, modulo the extent): lines of length n become
@@ -1411,6 +1425,63 @@ def su3_clover_bwd_(gx: torch.Tensor, xn: torch.Tensor, w: torch.Tensor,
     N.call('l2q_su3_clover_bwd', xn, w.to(torch.float64).contiguous(), gx, nb, T, X, Y, Z, ws,
            ws.numel() * ws.element_size())
     return gx
+
+
+def su3_force_vjp_(gx: torch.Tensor, xn: torch.Tensor, gf: torch.Tensor, beta: float,
+                   lat: Sequence[int]) -> torch.Tensor:
+    """gx += the full VJP of `su3_force_n` at xn for the cotangent gf of the force, the staples differentiated too
+    (`l2q_su3_force_vjp`; `su3_force_bwd_` holds them constant)."""
+    T, X, Y, Z = (int(i) for i in lat)
+    N.call('l2q_su3_force_vjp', xn, gf, float(beta), gx, xn.shape[0], T, X, Y, Z)
+    return gx
+
+
+def su3_flow_stage_bwd_n(xn: torch.Tensor, p_out: torch.Tensor, c: float, s: float, gx_out: torch.Tensor,
+                         gp: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
+    """Reverse of `su3_flow_stage_n` from its input links xn and its output p_out: returns the cotangent of xn for
+    the cotangent gx_out of x_out; gp (in place) is the cotangent of p_out on entry and of pn on exit."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    gx_in = torch.empty_like(xn)
+    ws = N.workspace(int(N.load().l2q_su3_flow_stage_bwd_ws_bytes(nb, T, X, Y, Z)), xn.device)
+    N.call('l2q_su3_flow_stage_bwd', xn, p_out, float(c), float(s), gx_out, gp, gx_in, nb, T, X, Y, Z, ws,
+           ws.numel())
+    return gx_in
+
+
+def su3_flow_step_bwd_n(xn: torch.Tensor, eps: float, gx_out: torch.Tensor, lat: Sequence[int],
+                        gx_in: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Reverse of one `su3_flow_step_n` of size eps that started from xn: the cotangent of xn for the cotangent
+    gx_out of the step's result, into gx_in (a new field by default; may be gx_out itself).  ws: a uint8 tensor of
+    `l2q_su3_flow_step_bwd_ws_bytes` (seven fields and a little), its own by default: like the field of
+    `su3_clover_bwd_` it is too large for the shared reduction workspace."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    gx_in = torch.empty_like(xn) if gx_in is None else gx_in
+    if ws is None:
+        ws = torch.empty(int(N.load().l2q_su3_flow_step_bwd_ws_bytes(nb, T, X, Y, Z)), dtype=torch.uint8,
+                         device=xn.device)
+    N.call('l2q_su3_flow_step_bwd', xn, float(eps), gx_out, gx_in, nb, T, X, Y, Z, ws, ws.numel())
+    return gx_in
+
+
+def su3_flow_bwd_n(checkpoints: Sequence[torch.Tensor], eps: float, g_out: torch.Tensor,
+                   lat: Sequence[int]) -> torch.Tensor:
+    """Reverse of a Wilson flow of len(checkpoints) steps of size eps: checkpoints[k] are the native links entering
+    step k, g_out the cotangent of the flowed links (only read).  Returns the cotangent of checkpoints[0]; no
+    checkpoint returns g_out itself.  One workspace and one cotangent field serve all steps."""
+    if len(checkpoints) == 0:
+        return g_out
+    nb = g_out.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    ws = torch.empty(int(N.load().l2q_su3_flow_step_bwd_ws_bytes(nb, T, X, Y, Z)), dtype=torch.uint8,
+                     device=g_out.device)
+    g = torch.empty_like(g_out)
+    src = g_out
+    for xn in reversed(checkpoints):
+        su3_flow_step_bwd_n(xn, eps, src, lat, gx_in=g, ws=ws)
+        src = g
+    return g
 
 
 def su3_rect_sums_n(xn: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:

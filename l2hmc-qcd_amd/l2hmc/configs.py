@@ -300,10 +300,27 @@ class LossConfig(BaseConfig):
     # the charge of the charge term: 'plaq' = the reference's sinQ (sum Im tr P / 18 V), 'clover' = the clover
     # topological charge of a 4D SU(3) lattice (LatticeSU3.clover_autograd)
     charge_kind: str = 'plaq'
+    # Wilson-flow time at which the clover charge of the charge term is taken, in steps of charge_flow_eps
+    # (LatticeSU3.flow_autograd; 0 = on the unflowed links); charge_kind = 'clover' only
+    charge_flow_time: float = 0.0
+    charge_flow_eps: float = 0.01
 
     def __post_init__(self):
         if self.charge_kind not in ('plaq', 'clover'):
             raise ValueError(f"LossConfig.charge_kind must be 'plaq' or 'clover', got {self.charge_kind!r}")
+        self.charge_flow_steps()
+
+    def charge_flow_steps(self) -> int:
+        """the number of flow steps charge_flow_time asks for; ValueError where the pair is not valid"""
+        t, eps = float(self.charge_flow_time), float(self.charge_flow_eps)
+        if t < 0 or not eps > 0:
+            raise ValueError(f'LossConfig: need charge_flow_time >= 0 and charge_flow_eps > 0, got {t}, {eps}')
+        n = round(t / eps)
+        if abs(t / eps - n) > 1e-9:
+            raise ValueError(f'LossConfig: charge_flow_time / charge_flow_eps must be an integer, got {t}, {eps}')
+        if n > 0 and self.charge_kind != 'clover':
+            raise ValueError("LossConfig: charge_flow_time > 0 needs charge_kind = 'clover'")
+        return int(n)
 
     def to_str(self) -> str:
         parts = [f'qw-{self.charge_weight:2.1f}', f'pw-{self.plaq_weight:2.1f}',
@@ -311,6 +328,8 @@ class LossConfig(BaseConfig):
                  f'mixed-{self.use_mixed_loss}']
         if self.charge_kind != 'plaq':
             parts.append(f'qk-{self.charge_kind}')
+        if self.charge_flow_time > 0:
+            parts.append(f'qt-{self.charge_flow_time:g}')
         return '_'.join(parts)
 
 

@@ -20,7 +20,8 @@ SU(3) uses the same tape with the cotangent kernels of ``csrc/su3_train_kernels.
 (polar-projection derivative solved in a Jacobi eigenbasis), ``l2q_su3_force_bwd`` (the reference
 differentiates the force only through the ``x^H`` factor of ``TAH(dS/dx x^H)``,
 lattice/su3/pytorch/lattice.py:299-308), ``l2q_su3_plaq_bwd`` and ``l2q_v_update_bwd_c128``; with
-``loss.charge_kind=clover`` the loss also seeds ``l2q_su3_clover_bwd`` (csrc/su3_clover_bwd.hip).
+``loss.charge_kind=clover`` the loss also seeds ``l2q_su3_clover_bwd`` (csrc/su3_clover_bwd.hip), and with
+``loss.charge_flow_time`` > 0 the reverse sweep of the Wilson flow behind it (csrc/su3_flow_bwd.hip).
 The vnet runs on reference-ordered 8-component inputs (transposes at its boundary) so that the
 ordinary ``LeapfrogLayer.backward`` accumulates into the checkpoint-ordered parameters.
 """
@@ -673,10 +674,17 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
         leaves.append(rs_p)
     clover = getattr(loss_fn, 'charge_kind', 'plaq') == 'clover' and loss_fn.charge_weight > 0
     q_i = q_p = None
+    nflow = int(getattr(loss_fn, 'charge_flow_steps', 0)) if clover else 0
     if clover:                          # the charge term on the clover charge: one more [nb, 3] leaf
-        cs_p = ops.su3_clover_sums_n(x_prop, lat).clone().requires_grad_(True)
+        # at flow time charge_flow_time: the clover sums of the flowed proposal, the links entering each step kept
+        # for the flow's reverse sweep (no step: the proposal itself and nothing kept)
+        xf_prop, flow_cps, xf_init = x_prop, [], xn_init
+        if nflow > 0:
+            xf_prop, flow_cps = ops.su3_flow_checkpoints_n(x_prop, nflow, loss_fn.charge_flow_eps, lat)
+            xf_init = loss_fn.lattice.flow_n(xn_init, nflow, loss_fn.charge_flow_eps)
+        cs_p = ops.su3_clover_sums_n(xf_prop, lat).clone().requires_grad_(True)
         leaves.append(cs_p)
-        q_i = loss_fn.lattice.clover_n(xn_init).Q
+        q_i = loss_fn.lattice.clover_n(xf_init).Q
     with torch.enable_grad():
         if clover:
             q_p = loss_fn.lattice._clover_of_sums(cs_p).Q
@@ -690,12 +698,18 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
         loss = loss_fn.loss_from_sums_su3(pl_i, pl_p, d2, acc, nelem=x_prop[0].numel(), q_init=q_i, q_prop=q_p)
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
     g_pl, g_ke, g_d2, g_sld = grads[:4]
-    gx = torch.zeros_like(x_prop)
+    if nflow > 0 and grads[-1] is not None:
+        # the flowed field's cotangent from the clover seed, then the flow's reverse sweep: a new field, to which
+        # the other terms add
+        gf = ops.su3_clover_bwd_(torch.zeros_like(x_prop), xf_prop, grads[-1], lat)
+        gx = ops.su3_flow_bwd_n(flow_cps, loss_fn.charge_flow_eps, gf, lat)
+    else:
+        gx = torch.zeros_like(x_prop)
     if g_pl is not None:
         ops.su3_plaq_bwd_(gx, x_prop, g_pl, lat)
     if c1 != 0.0 and grads[4] is not None:
         ops.su3_rect_bwd_(gx, x_prop, grads[4], lat)
-    if clover and grads[-1] is not None:
+    if clover and nflow == 0 and grads[-1] is not None:
         ops.su3_clover_bwd_(gx, x_prop, grads[-1], lat)
     if g_d2 is not None:
         ops.diff_bwd_(gx, x_prop, xn_init, g_d2)

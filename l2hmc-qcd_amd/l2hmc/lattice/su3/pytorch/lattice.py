@@ -142,9 +142,12 @@ class LatticeSU3(Lattice):
         self._no_grad(x, 'clover')
         return self.clover_n(self.pack(x))
 
-    def clover_autograd(self, x: Tensor) -> Clover:
+    def clover_autograd(self, x: Tensor, *, flow_time: float = 0.0, eps: float = 0.01) -> Clover:
         """`clover(x)`, differentiable where x requires a gradient (`l2q_su3_clover_bwd` behind it, the links as
-        unconstrained complex matrices); the same kernel and the same numbers as `clover(x)` otherwise."""
+        unconstrained complex matrices); the same kernel and the same numbers as `clover(x)` otherwise.  With
+        `flow_time` > 0 the observables of x flowed to that time in steps of eps (`flow_autograd`)."""
+        if float(flow_time) != 0.0:
+            x = self.flow_autograd(x, flow_time, eps)
         if AG.wants_grad(x):
             return self._clover_of_sums(AG.SU3CloverSums.apply(x.to(DEVICE), self._lattice_shape))
         return self.clover_n(self.pack(x))
@@ -197,6 +200,18 @@ class LatticeSU3(Lattice):
         self._no_grad(x, 'flow')
         n = self._flow_steps(float(t), float(eps))
         return self.unpack(self.flow_n(self.pack(x), n, eps))
+
+    def flow_autograd(self, x: Tensor, t: float, eps: float = 0.01) -> Tensor:
+        """`flow(x, t, eps)`, differentiable where x requires a gradient (`AG.SU3Flow`: the reverse sweep of
+        `l2q_su3_flow_step_bwd` behind it, the links as unconstrained complex matrices; round(t / eps) + 9 fields of
+        memory); the same kernels and the same numbers as `flow` otherwise.  No step (t = 0) returns x itself."""
+        n = self._flow_steps(float(t), float(eps))
+        if n == 0:
+            return x
+        if AG.wants_grad(x):
+            return AG.SU3Flow.apply(x.to(DEVICE), self._lattice_shape, n, float(eps))
+        xn = self.flow_n(self.pack(x), n, eps)
+        return AG.attach_native(self.unpack(xn), xn)
 
     def flow_observables(self, x: Tensor, t: float, eps: float = 0.01, every: int = 1) -> dict[str, Tensor]:
         """Clover observables along the flow: 't' [n+1], 'E', 'Eplaq', 'Q', 't2E' [n+1, nb], measured every

@@ -44,6 +44,12 @@ class LatticeLoss:
             raise ValueError(f"charge_kind must be 'plaq' or 'clover', got {self.charge_kind!r}")
         if self.charge_kind == 'clover' and not isinstance(self.lattice, LatticeSU3):
             raise ValueError("charge_kind = 'clover' needs a 4D SU(3) lattice: U(1) has no clover charge")
+        # the flow time of the clover charge (0: the unflowed links), checked again where it is used
+        self.charge_flow_time = float(getattr(self.config, 'charge_flow_time', 0.0))
+        self.charge_flow_eps = float(getattr(self.config, 'charge_flow_eps', 0.01))
+        self.charge_flow_steps = LatticeSU3._flow_steps(self.charge_flow_time, self.charge_flow_eps)
+        if self.charge_flow_steps > 0 and self.charge_kind != 'clover':
+            raise ValueError("charge_flow_time > 0 needs charge_kind = 'clover'")
 
     def __call__(self, x_init: Tensor, x_prop: Tensor, acc: Tensor) -> Tensor:
         return self.calc_loss(x_init=x_init, x_prop=x_prop, acc=acc)
@@ -83,7 +89,14 @@ class LatticeLoss:
     def charge_loss(self, x_init: Tensor, x_prop: Tensor, acc: Tensor,
                     use_mixed_loss: Optional[bool] = None) -> Tensor:
         if self.charge_kind == 'clover':
-            # the clover topological charge in place of sinQ (differentiable: l2q_su3_clover_bwd)
+            # the clover topological charge in place of sinQ (differentiable: l2q_su3_clover_bwd), at flow time
+            # charge_flow_time (differentiable: l2q_su3_flow_step_bwd)
+            if self.charge_flow_steps > 0:
+                # x_init carries no gradient through the flow: no parameter depends on it, and its reverse sweep
+                # would cost what the proposal's does
+                with torch.no_grad():
+                    x_init = self.lattice.flow_autograd(x_init, self.charge_flow_time, self.charge_flow_eps)
+                x_prop = self.lattice.flow_autograd(x_prop, self.charge_flow_time, self.charge_flow_eps)
             q1, q2 = self.lattice.clover_autograd(x_init).Q, self.lattice.clover_autograd(x_prop).Q
             return self._mixed(acc.to(DEVICE) * (q2 - q1) ** 2, self.charge_weight, use_mixed_loss)
         q1 = self.lattice._sin_charges(self.lattice.plaq_sums(x_init))

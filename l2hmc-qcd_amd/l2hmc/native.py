@@ -150,6 +150,11 @@ SIGNATURES = {
     'l2q_su3_plaq_bwd': (I, [P, P, P, I, I, I, I, I, P]),
     'l2q_su3_wilson_loops_bwd': (I, [P, P, P, I, I, I, I, I, P]),
     'l2q_su3_clover_bwd': (I, [P, P, P, I, I, I, I, I, P, Z, P]),
+    'l2q_su3_force_vjp': (I, [P, P, D, P, I, I, I, I, I, P]),
+    'l2q_su3_flow_stage_bwd_ws_bytes': (Z, [I, I, I, I, I]),
+    'l2q_su3_flow_stage_bwd': (I, [P, P, D, D, P, P, P, I, I, I, I, I, P, Z, P]),
+    'l2q_su3_flow_step_bwd_ws_bytes': (Z, [I, I, I, I, I]),
+    'l2q_su3_flow_step_bwd': (I, [P, D, P, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_rect_reduce': (I, [P, I, I, I, I, I, P, P, Z, P]),
     'l2q_su3_rect_force_add': (I, [P, D, P, I, I, I, I, I, P]),
     'l2q_su3_rect_bwd': (I, [P, P, P, I, I, I, I, I, P]),

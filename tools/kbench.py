@@ -66,6 +66,8 @@ def main():
     ap.add_argument('--flow-only', action='store_true', help='only the Wilson-flow / clover rows')
     ap.add_argument('--clover-bwd', action='store_true',
                     help='only the clover VJP next to the clover sums and the plaquette VJP')
+    ap.add_argument('--flow-bwd', action='store_true',
+                    help='only the reverse sweep of the Wilson flow next to its forward and the clover VJP')
     ap.add_argument('--nb', type=int, default=256)
     ap.add_argument('--L', type=int, nargs=4, default=[8, 8, 8, 8])
     ap.add_argument('--gemm', action='store_true')
@@ -99,6 +101,24 @@ def main():
         rec('su3_clover_reduce', timeit(lambda: ops.su3_clover_sums_n(xn, L)), 576, 72 * 216)
         rec('su3_plaq_bwd', timeit(lambda: ops.su3_plaq_bwd_(gx, xn, w6, L)), 1728, 48 * 216)
         rec('su3_clover_bwd', timeit(lambda: ops.su3_clover_bwd_(gx, xn, w3, L)), 3168, 264 * 216)
+        return
+    if a.flow_bwd:
+        # the full force VJP reads the links and the force's cotangent and updates gx (576 + 576 + 1152 B): 4 links x
+        # 3 directions x (7 + 6) products.  A flow step is three stages (force kick + exponential); its reverse
+        # recomputes them (without the last exponential) and reverses each with an expm_mul_bwd and a force VJP.
+        gx, gf = torch.zeros_like(xn), torch.randn_like(xn)
+        w3 = torch.randn(nb, 3, dtype=torch.float64, device=dev)
+        rec('su3_clover_bwd', timeit(lambda: ops.su3_clover_bwd_(gx, xn, w3, L)), 3168, 264 * 216)
+        rec('su3_force_bwd (staples const)', timeit(lambda: ops.su3_force_bwd_(gx, xn, gf, 3.0, L)), 2304)
+        rec('su3_force_vjp', timeit(lambda: ops.su3_force_vjp_(gx, xn, gf, 3.0, L)), 2304, 156 * 216)
+        p2, x2, x3 = torch.empty_like(xn), torch.empty_like(xn), torch.empty_like(xn)
+        rec('su3_flow_step (3 stages)', timeit(lambda: ops.su3_flow_step_n(xn, x2, p2, x3, 0.01, L)), 2880 + 2 * 3456)
+        gp = torch.zeros_like(xn)
+        rec('su3_flow_stage_bwd', timeit(lambda: ops.su3_flow_stage_bwd_n(xn, vn, -32.0 / 17.0, 17.0 / 36.0 * 0.01, gf,
+                                                                         gp, L)), 5760)
+        del p2, x3, gp
+        ws = torch.empty(int(native.load().l2q_su3_flow_step_bwd_ws_bytes(nb, *L)), dtype=torch.uint8, device=dev)
+        rec('su3_flow_step_bwd', timeit(lambda: ops.su3_flow_step_bwd_n(xn, 0.01, gf, L, gx_in=x2, ws=ws)), 0)
         return
     # Wilson flow / clover observables: the clover pass reads the links once (576 B / site, 72 3x3 products); a flow
     # stage is the force kick (reads X and P, writes P) and the x-update (reads P and X, writes X): 3456 B / site
