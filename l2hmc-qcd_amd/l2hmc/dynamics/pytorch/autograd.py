@@ -148,7 +148,7 @@ class Transition(torch.autograd.Function):
         else:
             gv = dyn._pack(gvp) if su3 else gvp.to(rdt).reshape(v_.shape).clone()
         if gacc is not None:
-            swapped = bool(getattr(tape, 'swapped', False))
+            swapped = tape.swapped
             h0, h1 = tape.h_init.to(rdt), tape.h_prop.to(rdt)
             dh = (h1 - h0 if swapped else h0 - h1) + ctx.sld_fwd.to(rdt)
             g_dh = torch.where(dh < 0, gacc.to(rdt) * acc.to(rdt), torch.zeros_like(dh))

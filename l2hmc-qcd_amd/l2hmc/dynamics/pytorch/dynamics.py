@@ -33,6 +33,7 @@ from torch import nn
 import l2hmc.configs as cfgs
 from l2hmc import DEVICE
 from l2hmc import _ops as ops
+from l2hmc.dynamics.pytorch.trajectory import SamplerStepper, run_trajectory
 from l2hmc.group.su3.pytorch.group import SU3
 from l2hmc.group.u1.pytorch.group import U1Phase
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
@@ -256,6 +257,8 @@ class Dynamics(nn.Module):
         # train mode + grad mode: forward() records the trajectory and returns tensors with a grad_fn
         # (the reference's forward_step / loss.backward() contract); False keeps the graph-free sampler
         self.autograd_forward = True
+        # SU(3) training on native-order weight shadows (training._native_begin); 'force': even when memory is short
+        self.native_training = True
         # eval mode, small U(1) lattices: whole transitions replayed from a HIP graph (_auto_graphed)
         self.auto_graph = True
         self.auto_graph_su3 = False        # SU(3): kernel-bound, a replay is worth ~1 % (opt-in)
@@ -592,22 +595,23 @@ class Dynamics(nn.Module):
         return (self.fuse_heads and self._networks_built and self.group == 'SU3'
                 and vnet.units[-1] % 2 == 0)
 
-    def _v_inputs_n(self, vnet, xn: Tensor, beta, cache: Optional[dict]):
-        """(force, hidden activation z, kernel weights) for the fused heads kernel.  `cache`
-        (trajectory-local): the force, the vec8 network inputs and z depend only on x (and the
-        network), and x does not change between the closing v-update of one leapfrog step and
-        the opening v-update of the next (nor across the momentum flip), so they are computed
+    def _v_inputs_n(self, vnet, xn: Tensor, beta, ts: Optional[SamplerStepper] = None):
+        """(force, hidden activation z, kernel weights) for the fused heads kernel.  `ts`
+        (trajectory-local, `ts.reuse`): the force, the vec8 network inputs and z depend only on x
+        (and the network), and x does not change between the closing v-update of one leapfrog step
+        and the opening v-update of the next (nor across the momentum flip), so they are computed
         once per distinct x -- 9 instead of 16 evaluations in a merged nlf = 4 trajectory.
         Same inputs, same deterministic kernels: bitwise identical results."""
         nb = xn.shape[0]
-        hit = cache is not None and cache.get('valid', False)
-        fn = cache['F'] if hit else self._force_n(xn, beta)
-        if cache is not None and not hit:
-            pre = cache.get('xv_pre')          # vec8(x) emitted by the x-update that produced x
-            cache.clear()
-            cache.update({'valid': True, 'F': fn})
-            if pre is not None:
-                cache['xv_pre'] = pre
+        reuse = ts is not None and ts.reuse
+        if reuse and ts.valid:
+            fn = ts.F
+        else:
+            fn = self._force_n(xn, beta)
+            if reuse:                  # what was kept belongs to another x (xv_pre is of the new x already)
+                ts.valid, ts.F = True, fn
+                ts.xv = ts.fv = None
+                ts.z = {}
         if not self._can_fuse_heads(vnet):
             return fn, None, None
         p = self._perms()
@@ -619,20 +623,21 @@ class Dynamics(nn.Module):
         hs['use_sliced'] = bool(self._sliced_wanted(vnet) and ops.USE_SLICED_HEADS[0])
         if hs['use_sliced'] and 'sliced' not in hs:
             hs['sliced'] = ops.heads_sliced_build(hs)
-        zkey = ('z', id(vnet))
-        if cache is not None and zkey in cache:
-            return fn, cache[zkey], w
-        if cache is not None and 'xv' in cache:
-            xv, fv = cache['xv'], cache['fv']
+        if reuse and id(vnet) in ts.z:
+            return fn, ts.z[id(vnet)], w
+        if reuse and ts.xv is not None:
+            xv, fv = ts.xv, ts.fv
         else:
-            pre = cache.pop('xv_pre', None) if cache is not None else None
+            pre = None
+            if reuse:
+                pre, ts.xv_pre = ts.xv_pre, None     # vec8(x) emitted by the x-update that produced x
             xv = pre if pre is not None else ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
             fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
-            if cache is not None:
-                cache['xv'], cache['fv'] = xv, fv
+            if reuse:
+                ts.xv, ts.fv = xv, fv
         z = vnet.hidden_flat(xv, fv, w, sliced_exp=ops.SLICED_INPUT_EXP if self.sliced_input else None)
-        if cache is not None:
-            cache[zkey] = z
+        if reuse:
+            ts.z[id(vnet)] = z
         return fn, z, w
 
     def _sliced_wanted(self, vnet) -> bool:
@@ -662,7 +667,7 @@ class Dynamics(nn.Module):
                 and getattr(net, 'half_dtype', None) is not None)
 
     def _update_v_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool,
-                    cache: Optional[dict] = None, acc: Optional[Tensor] = None,
+                    ts: Optional[SamplerStepper] = None, acc: Optional[Tensor] = None,
                     v_src: Optional[Tensor] = None) -> Tensor:
         """v-update in place (dynamics.py:1266-1297); returns logdet [nb] (the fused U(1) kernel
         adds it into `acc` when given).  `v_src`: the momentum is read from there and only
@@ -685,7 +690,7 @@ class Dynamics(nn.Module):
             z = vnet.hidden_flat_h(x.reshape(nb, -1), fn.reshape(nb, -1), w)
             return ops.u1_heads_update_h_(z, w['h']['heads_scaled'], vnet.nw.t, vn.reshape(nb, -1),
                                           fn.reshape(nb, -1), eps, forward)
-        fn, z, w = self._v_inputs_n(vnet, xn, beta, cache)
+        fn, z, w = self._v_inputs_n(vnet, xn, beta, ts)
         if z is not None:
             # heads + momentum update in one kernel: s, t, q never reach HBM
             return ops.vnet_heads_vupdate_(z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q),
@@ -698,26 +703,25 @@ class Dynamics(nn.Module):
 
     def _update_v_pair_n(self, step0: int, forward0: bool, flip: bool, step1: int,
                          forward1: bool, xn: Tensor, vn: Tensor, beta,
-                         cache: Optional[dict] = None, mid: Optional[dict] = None) -> Tensor:
+                         ts: Optional[SamplerStepper] = None) -> Tensor:
         """The closing v-update of one leapfrog step and the opening v-update of the next (same
         x, same network => same s, t, q), optionally with the merged trajectory's v -> -v in
         between (dynamics.py:1001), from ONE evaluation of the heads.  Sum of both logdets.
-        With `mid` (per-step metrics, verbose=True): the kernel also returns the first update's
+        With `ts.late` (per-step metrics, verbose=True): the kernel also returns the first update's
         logdet and the kinetic energy of the momentum between the two updates; they are left in
-        mid['ld1'] / mid['ke'] and the return value is the SECOND update's logdet alone."""
+        ts.ld1 / ts.ke and the return value is the SECOND update's logdet alone."""
         nb = xn.shape[0]
         vnet = self._get_vnet(step1)
-        fn, z, w = self._v_inputs_n(vnet, xn, beta, cache)
+        fn, z, w = self._v_inputs_n(vnet, xn, beta, ts)
         args = (z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q), vn.reshape(nb, -1),
                 fn.reshape(nb, -1), self._eps('v', step0), forward0, flip, self._eps('v', step1),
                 forward1)
-        if mid is None:
+        if ts is None or not ts.late:
             return ops.vnet_heads_vupdate_pair_(*args)
-        ld, ld1, vn2 = ops.vnet_heads_vupdate_pair_mid_(*args)
-        mid['ld1'] = ld1
+        ld, ts.ld1, vn2 = ops.vnet_heads_vupdate_pair_mid_(*args)
         # group/su3/pytorch/group.py:125-126 as l2q_su3_kinetic_reduce evaluates it
-        mid['ke'] = 0.5 * (vn2 - 8.0 * 4.0 * self.volume)
-        return ld - ld1
+        ts.ke = 0.5 * (vn2 - 8.0 * 4.0 * self.volume)
+        return ld - ts.ld1
 
     def _can_pair_mid(self) -> bool:
         """The mid-point pair kernel (LDS-DMA heads kernel) needs whole 16-wide K-slabs."""
@@ -761,19 +765,18 @@ class Dynamics(nn.Module):
         return vn.neg_()
 
     def _lf_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool,
-              cache: Optional[dict] = None, pend: Optional[dict] = None,
-              mid: Optional[dict] = None, x_src: Optional[Tensor] = None,
-              v_src: Optional[Tensor] = None) -> Tensor:
+              ts: Optional[SamplerStepper] = None) -> Tensor:
         """One generalised leapfrog step in place; returns logdet [nb]
-        (dynamics.py:1187-1228).  `pend` (optional, trajectory-local) enables deferral of the
-        closing v-update: it is then executed together with the next step's opening v-update
-        (`_update_v_pair_n`), its logdet being returned by that next call; the caller flushes
-        a last pending update with `_flush_pending_n`.  `mid` (with `pend`, per-step metrics):
-        the deferred closing update's logdet and the kinetic energy right after it are left in
-        mid['ld1'] / mid['ke'], and the returned logdet covers THIS step's sub-updates only.
-        `x_src` (first step of a trajectory, SU(3)): the configuration is READ from x_src and the
-        x-update writes it into xn, so the trajectory never copies its input; `v_src` likewise for
-        the momentum of the step's opening v-update."""
+        (dynamics.py:1187-1228).  `ts` (optional): the state of the trajectory this step belongs
+        to (trajectory.SamplerStepper).  `ts.defer` defers the closing v-update: it is then executed
+        together with the next step's opening v-update (`_update_v_pair_n`), its logdet being
+        returned by that next call; the caller flushes a last pending update with
+        `_flush_pending_n`.  `ts.late` (with `ts.defer`, per-step metrics): the deferred closing
+        update's logdet and the kinetic energy right after it are left in ts.ld1 / ts.ke, and the
+        returned logdet covers THIS step's sub-updates only.  `ts.x_src` (first step of a
+        trajectory, SU(3)): the configuration is READ from there and the x-update writes it into
+        xn, so the trajectory never copies its input; `ts.v_src` likewise for the momentum of the
+        step's opening v-update."""
         if forward:
             st, order = step, ((False, True), (True, False))     # (complement, first)
         else:
@@ -794,7 +797,11 @@ class Dynamics(nn.Module):
                                   self.config.use_ncp, fx[first], ld)
                 ops.u1_vstep_(xn, vn, b, ev, forward, self.latvolume, fv, ld)
                 return ld
-        prev = pend.pop('p', None) if pend is not None else None
+        prev = x_src = v_src = None
+        if ts is not None:                   # taken: the pending update and the sources are this step's to use
+            prev, x_src, v_src = ts.pending, ts.x_src, ts.v_src
+            ts.pending = ts.x_src = ts.v_src = None
+        late = bool(prev is not None and ts.late)
         xr = xn if x_src is None else x_src              # where this step reads x before its x-update
         if v_src is not None and prev is not None:
             vn.copy_(v_src)
@@ -803,25 +810,25 @@ class Dynamics(nn.Module):
             st0, f0, flip = prev
             v0, v1 = self._get_vnet(st0), self._get_vnet(st)
             if v0 is v1 and self._can_fuse_heads(v1):
-                ld = self._update_v_pair_n(st0, f0, flip, st, forward, xr, vn, beta, cache, mid)
+                ld = self._update_v_pair_n(st0, f0, flip, st, forward, xr, vn, beta, ts)
             else:
-                ld = self._update_v_n(st0, xr, vn, beta, f0, cache)
-                if mid is not None:
-                    mid['ld1'], mid['ke'] = ld, self._kinetic_n(vn)
+                ld = self._update_v_n(st0, xr, vn, beta, f0, ts)
+                if late:
+                    ts.ld1, ts.ke = ld, self._kinetic_n(vn)
                 if flip:
                     self._flip_v_n(vn)
-                l1 = self._update_v_n(st, xr, vn, beta, forward, cache)
-                ld = l1 if mid is not None else ld + l1
+                l1 = self._update_v_n(st, xr, vn, beta, forward, ts)
+                ld = l1 if late else ld + l1
         else:
-            ld = self._update_v_n(st, xr, vn, beta, forward, cache, v_src=v_src)
+            ld = self._update_v_n(st, xr, vn, beta, forward, ts, v_src=v_src)
         if self.group == 'SU3' and self.fuse_x_updates:
             # both half-updates share expm(eps v): one kernel, one pass over x
             eps = self._eps('x', st)
-            if (cache is not None and self.fuse_x_vec8 and self.reuse_v_inputs
+            if (ts is not None and ts.reuse and self.fuse_x_vec8
                     and self._can_fuse_heads(self._get_vnet(st))):
                 _, xv = ops.su3_expm_mul2_vec8_n(xr, vn, eps if forward else -eps, m, not forward,
                                                  out=xn)
-                cache['xv_pre'] = xv.reshape(xn.shape[0], -1)
+                ts.xv_pre = xv.reshape(xn.shape[0], -1)
             else:
                 ops.su3_expm_mul2_n(xr, vn, eps if forward else -eps, m, not forward, out=xn)
         else:
@@ -831,19 +838,20 @@ class Dynamics(nn.Module):
                 l = self._update_x_n(st, xn, vn, m, comp, forward, first)
                 if l is not None:
                     ld = ld + l
-        if cache is not None:
-            cache['valid'] = False                     # x changed
-        if pend is not None:
-            pend['p'] = (st, forward, False)           # closing v-update deferred
-            return ld
-        return ld + self._update_v_n(st, xn, vn, beta, forward, cache)
+        if ts is not None:
+            ts.valid = False                           # x changed
+            if ts.defer:
+                ts.pending = (st, forward, False)      # closing v-update deferred
+                return ld
+        return ld + self._update_v_n(st, xn, vn, beta, forward, ts)
 
-    def _flush_pending_n(self, pend: Optional[dict], xn, vn, beta, cache) -> Optional[Tensor]:
-        prev = pend.pop('p', None) if pend is not None else None
+    def _flush_pending_n(self, ts: Optional[SamplerStepper], xn, vn, beta) -> Optional[Tensor]:
+        prev = ts.pending if ts is not None else None
         if prev is None:
             return None
+        ts.pending = None
         st0, f0, flip = prev
-        ld = self._update_v_n(st0, xn, vn, beta, f0, cache)
+        ld = self._update_v_n(st0, xn, vn, beta, f0, ts)
         if flip:
             self._flip_v_n(vn)
         return ld
@@ -1058,136 +1066,12 @@ class Dynamics(nn.Module):
 
     def _kernel_fb_n(self, xn, vn, beta):
         """Merged forward + backward trajectory (dynamics.py:956-1029)."""
-        nb = xn.shape[0]
-        # SU(3): the first leapfrog step reads the input configuration and momentum and writes
-        # x_ / v_ (x_src, v_src below): no copy of either
-        lazy_x = self.group == 'SU3' and self.config.nleapfrog > 0 and self._networks_built
-        x_ = torch.empty_like(xn) if lazy_x else xn.clone()
-        v_ = torch.empty_like(vn) if lazy_x else vn.clone()
-        sumlogdet = self._zeros_nb(nb)
-        sldf = torch.zeros_like(sumlogdet)
-        sldb = torch.zeros_like(sumlogdet)
-        history: dict = {}
-        h_init = self._hamiltonian_n(xn, vn, beta)
-        verbose = self.config.verbose
-        if verbose:
-            m = {'energy': h_init, 'logprob': h_init - sumlogdet, 'logdet': sumlogdet,
-                 'sldf': sldf, 'sldb': sldb, 'sld': sumlogdet,
-                 'xeps': self.xeps[0], 'veps': self.veps[0]}
-            self.update_history(m, history)
-        h = h_init
-        cache = {} if self.reuse_v_inputs else None
-        can_pair = (self.pair_v_updates and cache is not None and self.group == 'SU3'
-                    and self._networks_built)
-        # per-step metrics need the state between the paired updates: with verbose=True the pair
-        # kernel returns the first update's logdet and the kinetic energy after it (`mid`), and
-        # the metrics of a step are emitted once its closing update has run (one call later)
-        vpair = verbose and can_pair and self.pair_v_updates_verbose and self._can_pair_mid()
-        pend = {} if (can_pair and (not verbose or vpair)) else None
-        nlf = self.config.nleapfrog
-        deferred: Optional[dict] = None
-
-        def emit(d, ke):
-            energy = ke + d['pe']
-            if d['fwd']:
-                extras = {'sldf': sldf, 'sldb': sldb, 'sld': sumlogdet}
-            else:
-                extras = {'sldf': torch.zeros_like(sldb), 'sldb': sldb, 'sld': sumlogdet}
-            mt = {'energy': energy, 'logprob': energy - sumlogdet, 'logdet': sumlogdet}
-            mt.update(extras)
-            mt.update({'xeps': self.xeps[d['step']], 'veps': self.veps[d['step']]})
-            self.update_history(mt, history)
-            return energy
-
-        for step in range(nlf):
-            mid = {} if vpair else None
-            logdet = self._lf_n(step, x_, v_, beta, True, cache, pend, mid,
-                                x_src=xn if (lazy_x and step == 0) else None,
-                                v_src=vn if (lazy_x and step == 0) else None)
-            if vpair:
-                if deferred is not None:               # the previous step's closing update ran now
-                    sumlogdet = sumlogdet + mid['ld1']
-                    sldf = sldf + mid['ld1']
-                    emit(deferred, mid['ke'])
-                sumlogdet = sumlogdet + logdet
-                sldf = sldf + logdet
-                deferred = {'pe': self._potential_n(x_, beta), 'step': step, 'fwd': True}
-                continue
-            sumlogdet = sumlogdet + logdet
-            if verbose:
-                sldf = sldf + logdet
-                extras = {'sldf': sldf, 'sldb': sldb, 'sld': sumlogdet}
-                self.update_history(self._metrics_n(x_, v_, beta, sumlogdet, step, extras),
-                                    history)
-        if pend is not None and 'p' in pend:
-            st0, f0, _ = pend['p']
-            pend['p'] = (st0, f0, True)                # flip happens inside the paired kernel
-        else:
-            v_ = self._flip_v_n(v_)
-        for step in range(nlf):
-            mid = {} if vpair else None
-            logdet = self._lf_n(step, x_, v_, beta, False, cache, pend, mid)
-            if vpair:
-                if deferred is not None:
-                    sumlogdet = sumlogdet + mid['ld1']
-                    if deferred['fwd']:
-                        sldf = sldf + mid['ld1']
-                    else:
-                        sldb = sldb + mid['ld1']
-                    emit(deferred, mid['ke'])
-                sumlogdet = sumlogdet + logdet
-                sldb = sldb + logdet
-                deferred = {'pe': self._potential_n(x_, beta), 'step': nlf - step - 1, 'fwd': False}
-                continue
-            sumlogdet = sumlogdet + logdet
-            if verbose:
-                sldb = sldb + logdet
-                extras = {'sldf': torch.zeros_like(sldb), 'sldb': sldb, 'sld': sumlogdet}
-                mt = self._metrics_n(x_, v_, beta, sumlogdet,
-                                     self.config.nleapfrog - step - 1, extras)
-                h = mt['energy']
-                self.update_history(mt, history)
-        last = self._flush_pending_n(pend, x_, v_, beta, cache)
-        if last is not None:
-            sumlogdet = sumlogdet + last
-        if vpair and deferred is not None:
-            if last is not None:
-                if deferred['fwd']:
-                    sldf = sldf + last
-                else:
-                    sldb = sldb + last
-            h = emit(deferred, self._kinetic_n(v_))
-        if not verbose or self.config.nleapfrog == 0:
-            h = self._hamiltonian_n(x_, v_, beta)
-        acc = self._accept_prob_n(h_init, h, sumlogdet)
-        history.update({'acc': acc, 'sumlogdet': sumlogdet})
-        if verbose:
-            history = self._stack_history(history)
-        return x_, v_, history
+        return run_trajectory(self, SamplerStepper(self, beta, True), xn, vn, beta, (True, False))[:3]
 
     def _kernel_n(self, xn, vn, beta, forward: bool):
         """Single-direction kernel (dynamics.py:1031-1063), including the reference's swapped
         arguments to compute_accept_prob."""
-        nb = xn.shape[0]
-        x_, v_ = xn.clone(), vn.clone()
-        sumlogdet = self._zeros_nb(nb)
-        history: dict = {}
-        h0 = self._hamiltonian_n(xn, vn, beta)
-        if self.config.verbose:
-            self.update_history({'energy': h0, 'logprob': h0 - sumlogdet,
-                                 'logdet': sumlogdet}, history)
-        cache = {} if self.reuse_v_inputs else None
-        for step in range(self.config.nleapfrog):
-            logdet = self._lf_n(step, x_, v_, beta, forward, cache)
-            sumlogdet = sumlogdet + logdet
-            if self.config.verbose:
-                self.update_history(self._metrics_n(x_, v_, beta, sumlogdet, step), history)
-        h1 = self._hamiltonian_n(x_, v_, beta)
-        acc = self._accept_prob_n(h1, h0, sumlogdet)          # state_init=final, prop=initial
-        history.update({'acc': acc, 'sumlogdet': sumlogdet})
-        if self.config.verbose:
-            history = self._stack_history(history)
-        return x_, v_, history
+        return run_trajectory(self, SamplerStepper(self, beta, False), xn, vn, beta, (forward,))[:3]
 
     # ---- reference-shaped wrappers
     def _state_n(self, state: State):

@@ -34,6 +34,7 @@ from torch import nn
 
 from l2hmc import DEVICE
 from l2hmc import _ops as ops
+from l2hmc.dynamics.pytorch.trajectory import run_trajectory
 
 Tensor = torch.Tensor
 
@@ -385,6 +386,9 @@ class Tape:
     def __init__(self):
         self.entries: list = []
         self.eps_grads: dict = {}          # ('x'|'v', step) -> list of [nb] tensors
+        self.h_init = self.h_prop = None   # H of the initial / proposed state, as the accept probability used them
+        self.swapped = False               # single-direction kernel: acc = accept(H_prop, H_init), see trajectory_train
+        self.defer_cap = 0                 # network calls of the trajectory (arenas of the deferred weight gradients)
 
 
 def _v_step(dyn, tape: Tape, st: int, x: Tensor, v: Tensor, beta: float, forward: bool):
@@ -444,16 +448,16 @@ def _v_step_su3(dyn, tape: Tape, st: int, x: Tensor, v: Tensor, beta: float, for
     # native-order training: the network inputs of all calls of the step side by side in one arena, so that the
     # weight gradients are ONE GEMM per matrix at the end of the reverse sweep (LeapfrogLayer.defer_slot)
     slot = None
-    if vnet.native_active() and getattr(dyn, 'defer_weight_grads', True):
-        slot = vnet.defer_slot(nb, 32 * V, 32 * V, getattr(tape, 'defer_cap', 0))
+    if vnet.native_active() and dyn.defer_weight_grads:
+        slot = vnet.defer_slot(nb, 32 * V, 32 * V, tape.defer_cap)
     if slot is not None:
         xv = ops.su3_projsu_vec8_n(x, out=slot[1]).reshape(nb, -1)
         fv = ops.su3_projsu_vec8_n(F, out=slot[2]).reshape(nb, -1)
     else:
         xv = ops.su3_projsu_vec8_n(x).reshape(nb, -1)
         fv = ops.su3_projsu_vec8_n(F).reshape(nb, -1)
-    sie = ops.SLICED_INPUT_EXP if getattr(dyn, 'sliced_train_input', False) else None  # |vec8(projectSU(.))| < 4
-    if (vnet.native_active() and getattr(dyn, 'sliced_train_heads', True) and ops.USE_SLICED_HEADS[0]
+    sie = ops.SLICED_INPUT_EXP if dyn.sliced_train_input else None  # |vec8(projectSU(.))| < 4
+    if (vnet.native_active() and dyn.sliced_train_heads and ops.USE_SLICED_HEADS[0]
             and vnet.sliced_train_image() is not None):
         # the heads and this v-update in one launch on the int8 matrix cores (TAPE kernel: s, t, q are
         # stored for the reverse sweep); the image is rebuilt once per optimiser step
@@ -511,7 +515,7 @@ def _lf_train(dyn, tape: Tape, step: int, x, v, beta, forward: bool, share: Opti
     m = dyn._native_masks()[st]
     if dyn.group == 'SU3':
         v, ld = _v_step_su3(dyn, tape, st, x, v, beta, forward, share)
-        if getattr(dyn, 'fuse_x_halves_train', True):
+        if dyn.fuse_x_halves_train:
             # both masked half-updates in one kernel forward (ONE expm(eps v)) and one kernel in the reverse
             # sweep (one Frechet derivative for both: it is linear in its direction)
             eps = dyn._eps('x', st)
@@ -533,55 +537,49 @@ def _lf_train(dyn, tape: Tape, step: int, x, v, beta, forward: bool, share: Opti
     return x, v, ld + l
 
 
+class TapeStepper:
+    """trajectory.run_trajectory's stepper for training: functional steps (`_lf_train`) recorded on a Tape.
+    Nothing is deferred, so the metrics of a step are never late."""
+    late = False
+
+    def __init__(self, dyn, beta: float, merged: bool):
+        if not dyn._networks_built:
+            raise RuntimeError('training needs networks (Dynamics(network_factory=...))')
+        nlf = dyn.config.nleapfrog
+        self.dyn, self.beta, self.tape = dyn, beta, Tape()
+        self.share = {} if (dyn.group == 'SU3' and dyn.reuse_v_inputs) else None
+        # network calls of this trajectory -- arenas for the deferred weight gradients only with ONE shared vnet (the
+        # SU(3) default): separate networks see four calls each, not worth an arena per network
+        if len({id(dyn._get_vnet(s)) for s in range(nlf)}) == 1:
+            dirs = 2 if merged else 1
+            self.tape.defer_cap = dirs * nlf + 1 if self.share is not None else 2 * dirs * nlf
+        self.tape.swapped = not merged
+
+    def start(self, xn: Tensor, vn: Tensor):
+        return xn, vn
+
+    def step(self, step: int, x: Tensor, v: Tensor, forward: bool):
+        return _lf_train(self.dyn, self.tape, step, x, v, self.beta, forward, self.share)
+
+    def flip(self, v: Tensor) -> Tensor:
+        self.tape.entries.append({'kind': 'flip'})
+        return ops.scale(v, -1.0) if self.dyn.group == 'SU3' else -v
+
+    def finish(self, x: Tensor, v: Tensor):
+        return None
+
+
+def _trajectory_train(dyn, xn: Tensor, vn: Tensor, beta: float, directions: tuple):
+    stepper = TapeStepper(dyn, beta, len(directions) == 2)
+    tape = stepper.tape
+    x, v, history, tape.h_init, tape.h_prop = run_trajectory(dyn, stepper, xn, vn, beta, directions)
+    return x, v, history, tape
+
+
 def trajectory_fb_train(dyn, xn: Tensor, vn: Tensor, beta: float):
     """Merged forward + backward trajectory (dynamics.py:956-1029) recording the tape.
     Returns (x_prop, v_prop, history, tape)."""
-    if not dyn._networks_built:
-        raise RuntimeError('training needs networks (Dynamics(network_factory=...))')
-    tape = Tape()
-    nb = xn.shape[0]
-    x, v = xn, vn
-    sumlogdet = dyn._zeros_nb(nb)
-    h_init = dyn._hamiltonian_n(xn, vn, beta)
-    history: dict = {}
-    verbose = dyn.config.verbose
-    sldf = torch.zeros_like(sumlogdet)
-    sldb = torch.zeros_like(sumlogdet)
-    if verbose:
-        dyn.update_history({'energy': h_init, 'logprob': h_init - sumlogdet, 'logdet': sumlogdet,
-                            'sldf': sldf, 'sldb': sldb, 'sld': sumlogdet,
-                            'xeps': dyn.xeps[0], 'veps': dyn.veps[0]}, history)
-    nlf = dyn.config.nleapfrog
-    share = {} if (dyn.group == 'SU3' and getattr(dyn, 'reuse_v_inputs', True)) else None
-    # network calls of this trajectory -- arenas for the deferred weight gradients only with ONE shared vnet (the
-    # SU(3) default): separate networks see four calls each, not worth an arena per network
-    one_net = len({id(dyn._get_vnet(s)) for s in range(nlf)}) == 1
-    tape.defer_cap = ((2 * nlf + 1) if share is not None else 4 * nlf) if one_net else 0
-    for step in range(nlf):
-        x, v, ld = _lf_train(dyn, tape, step, x, v, beta, True, share)
-        sumlogdet = sumlogdet + ld
-        if verbose:
-            sldf = sldf + ld
-            dyn.update_history(dyn._metrics_n(x, v, beta, sumlogdet, step,
-                                              {'sldf': sldf, 'sldb': sldb, 'sld': sumlogdet}),
-                               history)
-    v = ops.scale(v, -1.0) if dyn.group == 'SU3' else -v
-    tape.entries.append({'kind': 'flip'})
-    for step in range(nlf):
-        x, v, ld = _lf_train(dyn, tape, step, x, v, beta, False, share)
-        sumlogdet = sumlogdet + ld
-        if verbose:
-            sldb = sldb + ld
-            dyn.update_history(dyn._metrics_n(x, v, beta, sumlogdet, nlf - step - 1,
-                                              {'sldf': torch.zeros_like(sldb), 'sldb': sldb,
-                                               'sld': sumlogdet}), history)
-    h_prop = dyn._hamiltonian_n(x, v, beta)
-    acc = dyn._accept_prob_n(h_init, h_prop, sumlogdet)
-    history.update({'acc': acc, 'sumlogdet': sumlogdet})
-    if verbose:
-        history = dyn._stack_history(history)
-    tape.h_init, tape.h_prop = h_init, h_prop
-    return x, v, history, tape
+    return _trajectory_train(dyn, xn, vn, beta, (True, False))
 
 
 def trajectory_train(dyn, xn: Tensor, vn: Tensor, beta: float, forward: bool):
@@ -590,34 +588,11 @@ def trajectory_train(dyn, xn: Tensor, vn: Tensor, beta: float, forward: bool):
     accept probability with the reference's SWAPPED arguments (`compute_accept_prob(state_init=
     state, state_prop=sinit)`, :1053-1057): dh = H(final) - H(start) + sumlogdet -- `tape.swapped`
     tells loss_and_seeds.  Returns (x_prop, v_prop, history, tape)."""
-    if not dyn._networks_built:
-        raise RuntimeError('training needs networks (Dynamics(network_factory=...))')
-    tape = Tape()
-    nb = xn.shape[0]
-    x, v = xn, vn
-    sumlogdet = dyn._zeros_nb(nb)
-    h_init = dyn._hamiltonian_n(xn, vn, beta)
-    history: dict = {}
-    verbose = dyn.config.verbose
-    if verbose:
-        dyn.update_history(dyn._metrics_n(x, v, beta, sumlogdet, None, None), history)
-    nlf = dyn.config.nleapfrog
-    share = {} if (dyn.group == 'SU3' and getattr(dyn, 'reuse_v_inputs', True)) else None
-    one_net = len({id(dyn._get_vnet(s)) for s in range(nlf)}) == 1
-    tape.defer_cap = ((nlf + 1) if share is not None else 2 * nlf) if one_net else 0
-    for step in range(nlf):
-        x, v, ld = _lf_train(dyn, tape, step, x, v, beta, forward, share)
-        sumlogdet = sumlogdet + ld
-        if verbose:
-            dyn.update_history(dyn._metrics_n(x, v, beta, sumlogdet, step, None), history)
-    h_fin = dyn._hamiltonian_n(x, v, beta)
-    acc = dyn._accept_prob_n(h_fin, h_init, sumlogdet)
-    history.update({'acc': acc, 'sumlogdet': sumlogdet})
-    if verbose:
-        history = dyn._stack_history(history)
-    tape.h_init, tape.h_prop = h_init, h_fin
-    tape.swapped = True
-    return x, v, history, tape
+    if dyn.config.verbose and dyn._networks_built:
+        # verbose: H(start) is evaluated twice, once for the accept step and once for the initial record; the two
+        # are the same bits, so the driver records the first and this one's result is not used
+        dyn._hamiltonian_n(xn, vn, beta)
+    return _trajectory_train(dyn, xn, vn, beta, (forward,))
 
 
 # ------------------------------------------------------------------------------ loss + seeds
@@ -640,7 +615,7 @@ def loss_and_seeds(dyn, loss_fn, xn_init: Tensor, x_prop: Tensor, v_prop: Tensor
     with torch.enable_grad():
         h_prop = ke_p + beta * (V - cos_p)
         dh = tape.h_init.detach() - h_prop + sld
-        if getattr(tape, 'swapped', False):            # single-direction kernel: see trajectory_train
+        if tape.swapped:            # single-direction kernel: see trajectory_train
             dh = h_prop - tape.h_init.detach() + sld
         acc = torch.exp(torch.minimum(dh, torch.zeros_like(dh)))
         loss = loss_fn.loss_from_sums(si[:, 0], si[:, 1], cos_p, sin_p, acc)
@@ -692,7 +667,7 @@ def _loss_and_seeds_su3(dyn, loss_fn, xn_init, x_prop, v_prop, tape, sumlogdet, 
         if c1 != 0.0:
             h_prop = h_prop + (-beta * c1 / 3.0) * rs_p
         dh = tape.h_init.detach() - h_prop + sld
-        if getattr(tape, 'swapped', False):
+        if tape.swapped:
             dh = h_prop - tape.h_init.detach() + sld
         acc = torch.exp(torch.minimum(dh, torch.zeros_like(dh)))
         loss = loss_fn.loss_from_sums_su3(pl_i, pl_p, d2, acc, nelem=x_prop[0].numel(), q_init=q_i, q_prop=q_p)
@@ -788,7 +763,7 @@ def _backward_su3(dyn, tape: Tape, gx: Tensor, gv: Tensor, gl: Tensor, beta: flo
     pend: dict = {}            # primary tape index -> cotangents deferred by the sharing v-update
     paired: dict = {}          # primary tape index -> its cotangents from the pair kernel
     flips_done: set = set()
-    fuse_pairs = getattr(dyn, 'fuse_v_pairs_bwd', True)
+    fuse_pairs = dyn.fuse_v_pairs_bwd
     for idx in range(len(tape.entries) - 1, -1, -1):
         e = tape.entries[idx]
         kind = e['kind']
@@ -955,7 +930,7 @@ def _native_begin(dyn, nb: Optional[int] = None) -> list:
     The shadows cost one gather + one scatter of the big matrices (and twice their bytes of HBM) per
     step; they are skipped only when the device is short of memory (`dyn.native_training = 'force'`
     takes them regardless)."""
-    if dyn.group != 'SU3' or not getattr(dyn, 'native_training', True):
+    if dyn.group != 'SU3' or not dyn.native_training:
         return []
     from l2hmc.network.pytorch.network import ConvStack
     p = dyn._perms()
@@ -966,7 +941,7 @@ def _native_begin(dyn, nb: Optional[int] = None) -> list:
             continue
         seen.add(id(n))
         have = bool(getattr(n, '_nat', None) and n._nat.get('w'))      # shadows of an earlier step: already paid for
-        if nb is not None and not have and getattr(dyn, 'native_training', True) != 'force':
+        if nb is not None and not have and dyn.native_training != 'force':
             # The shadows (weights + gradients: 2 x the five matrices) and what runs on them -- the sliced tape
             # heads (+ 7/8 of the head weights), the deferred weight gradients -- are taken whenever three times
             # the matrices' bytes fit in half of what the device has free.  (Rounds 2-3 compared the shadows'

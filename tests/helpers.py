@@ -618,6 +618,38 @@ def check_autograd_bridge_semantics(g, build, tol, sampler=True):
         assert xo.grad_fn is None and m['acc'].grad_fn is None
 
 
+def sampler_vs_tape(dyn, x, beta, normals, u, seed):
+    """ONE trajectory, taken by the sampler (eval mode) and by the training tape (train mode, grad on), on the
+    same injected draws, with verbose=True.  merge_directions=False: the sampler draws its direction from the
+    host generator seeded with `seed`, the tape is given the same one.  Asserts equal key sets and shapes and
+    returns {key: max|tape - sampler| / max(1, max|sampler|)} of the per-step history and the accept step."""
+    import torch
+    assert dyn.config.verbose
+    torch.manual_seed(seed)
+    forward = bool(torch.rand(1) > 0.5)          # what Dynamics.apply_transition will draw
+    hist = {}
+    for tape in (False, True):
+        dyn.train(tape)
+        dyn._inject = {'normals': normals, 'u': u, 'forward': forward}
+        torch.manual_seed(seed)
+        with torch.set_grad_enabled(tape):
+            _, m = dyn((x, torch.tensor(beta)))
+        hist[tape] = {k: v.detach().cpu().numpy() for k, v in m.items()
+                      if isinstance(v, torch.Tensor) and k != 'beta'}
+    dyn._inject = None
+    assert m['acc'].grad_fn is not None          # the second run did record the tape
+    assert hist[True].keys() == hist[False].keys(), (sorted(hist[True]), sorted(hist[False]))
+    keys = {'energy', 'logprob', 'logdet', 'sld', 'sldf', 'sldb', 'acc', 'sumlogdet'}
+    assert keys - ({'sld', 'sldf', 'sldb'} if not dyn.config.merge_directions else set()) <= hist[True].keys()
+    rel = {}
+    for k, a in hist[True].items():
+        b = hist[False][k]
+        assert a.shape == b.shape, (k, a.shape, b.shape)
+        if k in keys:
+            rel[k] = float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+    return rel
+
+
 def check_half_train_step(g, route):
     """Mixed-precision train step on a u1_train_{fp16,bf16}* fixture (the REAL reference under
     `torch.autocast(dtype)` + `GradScaler`, tests/golden/make_golden_train.py half).

@@ -1293,3 +1293,48 @@ def test_auto_graphed_su3_transitions(golden):
     dyn.auto_graph = False
     dyn((x, beta))
     assert len(dyn._graphs) == n
+
+
+@pytest.mark.parametrize('merge', [True, False], ids=['merged', 'single'])
+def test_su3_sampler_and_tape_trajectories_agree(merge):
+    """The sampler (eval mode: in-place steps, fused pair kernels -- units [16] is a whole K-slab, so verbose=True
+    takes the mid-point pair kernel and the metrics of a step arrive one call late) and the training tape
+    (functional steps, tape kernels) drive ONE trajectory loop (dynamics/pytorch/trajectory.py): on the same
+    draws their verbose histories have the same keys and shapes and agree in value.  Odd extents (wrap-around);
+    the merged sampler's first step reads its input in place; single direction: forward and backward."""
+    import l2hmc.configs as cfgs
+    from l2hmc.dynamics.pytorch.dynamics import Dynamics
+    from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
+    from l2hmc.network.pytorch.network import NetworkFactory
+    torch.set_default_dtype(torch.float64)
+    torch.manual_seed(37)
+    np.random.seed(37)
+    L, nb, nlf, beta = [3, 4, 5, 3], 3, 2, 5.8
+    V = int(np.prod(L))
+    dc = cfgs.DynamicsConfig(nchains=nb, group='SU3', latvolume=L, nleapfrog=nlf, eps=0.02, eps_hmc=0.02,
+                             verbose=True, use_split_xnets=False, use_separate_networks=False,
+                             merge_directions=merge)
+    nc = cfgs.NetworkConfig(units=[16], activation_fn='tanh', dropout_prob=0.0, use_batch_norm=False)
+    spec = cfgs.InputSpec(xshape=tuple(dc.xshape), xnet={'x': [32 * V], 'v': [32 * V]},
+                          vnet={'x': [32 * V], 'v': [32 * V]})
+    lat = LatticeSU3(nb, L)
+    dyn = Dynamics(lat.action, dc, NetworkFactory(spec, nc, cfgs.ConvolutionConfig()))
+    assert dyn._can_pair_mid() and dyn.pair_v_updates_verbose
+    g = torch.Generator().manual_seed(5)
+    with torch.no_grad():
+        for n_, p in dyn.vnet.named_parameters():
+            if n_.endswith('coeff'):
+                p.copy_(0.3 * torch.randn(p.shape, generator=g, dtype=torch.float64).to(p.device))
+    x = lat.random()
+    nrm = torch.randn(8, nb, 4, *L, generator=g, dtype=torch.float64).numpy()
+    seeds = {}                                      # direction the host generator draws -> a seed that draws it
+    for s in range(16):
+        torch.manual_seed(s)
+        seeds.setdefault(bool(torch.rand(1) > 0.5), s)
+    assert len(seeds) == 2
+    for seed in ([seeds[True]] if merge else [seeds[True], seeds[False]]):
+        rel = helpers.sampler_vs_tape(dyn, x, beta, nrm, np.full(nb, 0.5), seed)
+        print(merge, seed, rel)
+        # two kernel routes through one trajectory: the bound of test_sizes_gpu.py (the kernels round
+        # differently at 1e-16 and projectSU(force) in front of the vnet amplifies that by ~1e7 per step)
+        assert max(rel.values()) <= 1e-7, rel

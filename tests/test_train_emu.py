@@ -404,6 +404,44 @@ def test_trainer_train_step_single_direction(monkeypatch):
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='host-logic test for the CPU container')
+@pytest.mark.parametrize('merge', [True, False], ids=['merged', 'single'])
+def test_sampler_and_tape_trajectories_agree_host_logic(merge, monkeypatch, f64):
+    """The sampler (eval mode, in-place steps) and the training tape (functional steps) drive ONE trajectory
+    loop (dynamics/pytorch/trajectory.py): on the same draws their verbose histories have the same keys and
+    shapes and agree in value; single direction: forward and backward."""
+    import l2hmc.configs as cfgs
+    from l2hmc.trainers.pytorch.trainer import Trainer
+    emu_native.install(monkeypatch)
+    torch.manual_seed(3)
+    np.random.seed(3)
+    tr = Trainer(cfgs.get_config(['dynamics.group=U1', 'dynamics.latvolume=[4,4]', 'dynamics.nchains=3',
+                                  'dynamics.nleapfrog=2', f'dynamics.merge_directions={str(merge).lower()}',
+                                  'dynamics.verbose=true', 'network.units=[6]', 'conv=none',
+                                  'network.dropout_prob=0.0', 'network.use_batch_norm=false']))
+    dyn = tr.dynamics
+    assert dyn._dtype == torch.float64
+    gen = torch.Generator().manual_seed(5)
+    with torch.no_grad():                           # (fresh networks have s = q = 0: no logdet)
+        for name, p in dyn.named_parameters():
+            if name.endswith('coeff'):
+                p.copy_(0.3 * torch.randn(p.shape, generator=gen, dtype=torch.float64))
+    x = tr.lattice.random()
+    nrm = torch.randn(3, 2, 4, 4, generator=torch.Generator().manual_seed(7), dtype=torch.float64).numpy()
+    seeds = {}                                      # direction the host generator draws -> a seed that draws it
+    for s in range(16):
+        torch.manual_seed(s)
+        seeds.setdefault(bool(torch.rand(1) > 0.5), s)
+    assert len(seeds) == 2
+    for seed in ([seeds[True]] if merge else [seeds[True], seeds[False]]):
+        rel = helpers.sampler_vs_tape(dyn, x, 2.0, nrm, np.full(3, 0.5), seed)
+        print(merge, seed, rel)
+        # largest relative difference measured before the two forms shared a loop: 0.0 for every key, in all
+        # three runs (on the emulator both forms evaluate the same torch expressions); allowed: 10 x that,
+        # not below 1e-14 (room for another summation order)
+        assert max(rel.values()) <= 1e-14, rel
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='host-logic test for the CPU container')
 @pytest.mark.parametrize('name', ['u1_train_f64', 'su3_train', 'su3_train_nomerge'])
 def test_autograd_bridge_semantics_host_logic(name, golden, monkeypatch, f64):
     g = golden(name)
