@@ -245,6 +245,34 @@ int l2q_su3_loop_reduce(const void* a, int r, const void* b, int t, double* out,
  * traffic: 144 B per (chain, site) read, 16 B per (chain, perpendicular site) written. */
 int l2q_su3_polyakov(const void* xn, int mu, void* out, int nb, int T, int X, int Y, int Z, void* stream);
 
+/* ---------------------------------------------------------------- SU(3) heatbath and overrelaxation */
+/* Local updates of the Wilson action (c1 = 0), IN PLACE: both rewrite the links U_mu(x) of every chain at the sites
+ * with (t + x + y + z) & 1 == parity and only read every other link.  All four extents must be even (L2Q_ESHAPE
+ * otherwise): the staples of U_mu(x) then hold mu-links of the other parity only, so no thread of a launch reads what
+ * another one writes.  One thread per (chain, half-site h); h runs over the sites of that parity in lattice order,
+ * s = 2 h + ((parity - t - x - y) & 1).
+ * With A = A_mu(x) the sum of the six staples as in l2q_su3_force (the link's share of the action is
+ * -(beta/3) Re tr(U A)), for the SU(2) subgroups (i, j) = (0,1), (0,2), (1,2) in that order, W = U A formed anew:
+ *   r = (Re(W_ii + W_jj), Im(W_ij + W_ji), Re(W_ij - W_ji), Im(W_ii - W_jj)) / 2, k = |r|, rh = r / k  ((1,0,0,0) if
+ *   k is zero or not finite); a quaternion a is the block [[a0 + i a3, a2 + i a1], [-a2 + i a1, a0 - i a3]] at rows and
+ *   columns i, j, and U <- embed(a) U with
+ *   overrelaxation: a = conj(rh) conj(rh)  (Re tr(U A) unchanged);
+ *   heatbath (Cabibbo-Marinari with Kennedy-Pendleton sampling): alpha = 2 beta k / 3, v = 1 - u; tries t = 0..ntry-1:
+ *     delta = -(ln v1 + cos^2(2 pi v2) ln v3) / alpha, the first with v4^2 <= 1 - delta/2 gives b0 = 1 - delta;
+ *     cos(theta) = 1 - 2 v5, phi = 2 pi v6, n = sqrt(max(0, 1 - b0^2)),
+ *     b = (b0, n sin(theta) cos(phi), n sin(theta) sin(phi), n cos(theta)), a = b conj(rh).
+ *     No try accepted: the subgroup leaves U as it is and counts one failure (still exact: whether that happens
+ *     depends on the staples only).
+ * u[nb][3][4 ntry + 2][V/2] float64 uniforms in [0, 1), half-site fastest: rows 4t .. 4t+3 are u1..u4 of try t, the
+ * last two rows u5, u6; ntry in 1..16.  The kernel holds no generator.  fails (may be NULL) [nb]: the (link, subgroup)
+ * failures of each chain in this launch, by block partials in ws >= nb * ceil(V/2 / 256) doubles
+ * (l2q_reduce_ws_bytes(nb, V/2) covers it); with fails NULL, ws is not used.
+ * Algorithmic traffic per updated link: 20 x 144 B of links (18 staple links, the link read and written) plus
+ * 24 (4 ntry + 2) B of uniforms. */
+int l2q_su3_heatbath(void* xn, double beta, int mu, int parity, const double* u, int ntry, double* fails, int nb,
+                     int T, int X, int Y, int Z, void* ws, size_t ws_bytes, void* stream);
+int l2q_su3_overrelax(void* xn, int mu, int parity, int nb, int T, int X, int Y, int Z, void* stream);
+
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:
  *   forward : v' = exp(eps s/2) v - (eps/2) (F exp(eps q) + t),  logdet[c] =  sum eps s/2

@@ -330,6 +330,32 @@ def su3_polyakov_n(xn: torch.Tensor, mu: int, lat: Sequence[int]) -> torch.Tenso
     return out
 
 
+def su3_heatbath_(xn: torch.Tensor, beta: float, mu: int, parity: int, u: torch.Tensor, ntry: int,
+                  lat: Sequence[int]) -> torch.Tensor:
+    """Cabibbo-Marinari / Kennedy-Pendleton heatbath of the links U_mu at the sites of one parity, IN PLACE in the
+    native field xn, from the uniforms u[nb, 3, 4 ntry + 2, V/2] float64 (see l2q.h).  Returns [nb] float64: the
+    number of (link, subgroup) updates of each chain for which none of the ntry proposals was accepted."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    ntry = int(ntry)
+    vh = T * X * Y * Z // 2
+    if u.dtype != torch.float64 or tuple(u.shape) != (nb, 3, 4 * ntry + 2, vh):
+        raise ValueError(f'su3_heatbath_: u must be float64 [{nb}, 3, {4 * ntry + 2}, {vh}], got {u.dtype} '
+                         f'{list(u.shape)}')
+    fails = torch.empty(nb, dtype=torch.float64, device=xn.device)
+    ws = _ws(nb, max(vh, 1), xn.device)
+    N.call('l2q_su3_heatbath', xn, float(beta), int(mu), int(parity), u, ntry, fails, nb, T, X, Y, Z, ws, ws.numel())
+    return fails
+
+
+def su3_overrelax_(xn: torch.Tensor, mu: int, parity: int, lat: Sequence[int]) -> torch.Tensor:
+    """Microcanonical overrelaxation of the links U_mu at the sites of one parity, IN PLACE in the native field xn
+    (the three SU(2) subgroups of each link reflected about their staple: the Wilson action is unchanged)."""
+    T, X, Y, Z = (int(i) for i in lat)
+    N.call('l2q_su3_overrelax', xn, int(mu), int(parity), xn.shape[0], T, X, Y, Z)
+    return xn
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

@@ -313,6 +313,83 @@ class LatticeSU3(Lattice):
             metrics['dploop'] = (metrics['ploop'] - self.polyakov(xinit, 0).abs()).abs()
         return metrics
 
+    # ------------------------------------------------------------ heatbath and overrelaxation sweeps
+    def _local_update_checks(self, xn: Tensor, what: str, nsweeps: int, nover: int = 0) -> None:
+        if isinstance(xn, torch.Tensor) and xn.requires_grad:
+            raise ValueError(f'LatticeSU3.{what}: no autograd through a local update')
+        if any(int(n) % 2 for n in self._lattice_shape):
+            raise ValueError(f'LatticeSU3.{what}: the checkerboard needs even extents, got {list(self._lattice_shape)}')
+        if self.c1 != 0:
+            raise ValueError(f'LatticeSU3.{what}: only the Wilson action (c1 = 0), got c1 = {self.c1}')
+        if int(nsweeps) < 0 or int(nover) < 0:
+            raise ValueError(f'LatticeSU3.{what}: sweep counts must be >= 0, got {nsweeps}, {nover}')
+
+    def _heatbath_checks(self, x: Tensor, beta, nsweeps: int, nover: int, ntry: int) -> None:
+        self._local_update_checks(x, 'heatbath', nsweeps, nover)
+        b = _beta(beta)
+        if not (b > 0 and np.isfinite(b)):
+            raise ValueError(f'LatticeSU3.heatbath: beta must be positive and finite, got {b}')
+        if not 1 <= int(ntry) <= 16:
+            raise ValueError(f'LatticeSU3.heatbath: ntry must be 1..16, got {ntry}')
+
+    def _overrelax_sweeps_(self, xn: Tensor, nsweeps: int) -> None:
+        for _ in range(nsweeps):
+            for mu in range(4):
+                for parity in (0, 1):
+                    ops.su3_overrelax_(xn, mu, parity, self._lattice_shape)
+
+    def heatbath_n(self, xn: Tensor, beta, nsweeps: int = 1, nover: int = 0, ntry: int = 4,
+                   generator: Optional[torch.Generator] = None, reunitarize: bool = True) -> tuple[Tensor, dict]:
+        """`nsweeps` Cabibbo-Marinari heatbath sweeps of the Wilson action at `beta` on a native field, each followed by
+        `nover` overrelaxation sweeps; returns (a new field, info); xn is never written.  A sweep is
+        `for mu in 0..3: for parity in 0, 1:` one launch each (`l2q_su3_heatbath` / `l2q_su3_overrelax`).  Every
+        heatbath launch draws `torch.rand((nb, 3, 4 * ntry + 2, V // 2), dtype=float64)`, in that order: on the device
+        with generator None, on the host with a CPU torch.Generator (the parity mode: the same numbers on any machine).
+        `ntry` (1..16) Kennedy-Pendleton proposals per SU(2) subgroup; a subgroup for which none is accepted is left as
+        it is (still exact) and counted: info['fail_frac'] [nb] = failures / (3 * 4 V * nsweeps).  `reunitarize` projects
+        the field on SU(3) once after each full sweep (the drift is rounding only, but accumulates)."""
+        self._heatbath_checks(xn, beta, nsweeps, nover, ntry)
+        b = _beta(beta)
+        nsweeps, nover, ntry = int(nsweeps), int(nover), int(ntry)
+        L = self._lattice_shape
+        xn = xn.detach().clone()
+        nb = xn.shape[0]
+        shape = (nb, 3, 4 * ntry + 2, self.volume // 2)
+        fails = torch.zeros(nb, dtype=torch.float64, device=xn.device)
+        for _ in range(nsweeps):
+            for mu in range(4):
+                for parity in (0, 1):
+                    if generator is None:
+                        u = torch.rand(shape, dtype=torch.float64, device=xn.device)
+                    else:
+                        u = torch.rand(shape, dtype=torch.float64, generator=generator).to(xn.device)
+                    fails += ops.su3_heatbath_(xn, b, mu, parity, u, ntry, L)
+            self._overrelax_sweeps_(xn, nover)
+            if reunitarize:
+                xn = ops.su3_project_su_n(xn)
+        return xn, {'fail_frac': fails / (3.0 * 4.0 * self.volume * max(nsweeps, 1))}
+
+    def heatbath(self, x: Tensor, beta, nsweeps: int = 1, nover: int = 0, ntry: int = 4,
+                 generator: Optional[torch.Generator] = None, reunitarize: bool = True) -> tuple[Tensor, dict]:
+        """`heatbath_n` in the reference layout: (x_new, info); x is never written."""
+        self._heatbath_checks(x, beta, nsweeps, nover, ntry)
+        xn, info = self.heatbath_n(self.pack(x), beta, nsweeps, nover, ntry, generator, reunitarize)
+        return AG.attach_native(self.unpack(xn), xn), info
+
+    def overrelax_n(self, xn: Tensor, nsweeps: int = 1) -> Tensor:
+        """`nsweeps` microcanonical overrelaxation sweeps (the heatbath's launch order) on a native field: a new field
+        with the same Wilson action; xn is never written."""
+        nsweeps = int(nsweeps)
+        self._local_update_checks(xn, 'overrelax', nsweeps)
+        xn = xn.detach().clone()
+        self._overrelax_sweeps_(xn, nsweeps)
+        return xn
+
+    def overrelax(self, x: Tensor, nsweeps: int = 1) -> Tensor:
+        self._local_update_checks(x, 'overrelax', nsweeps)
+        xn = self.overrelax_n(self.pack(x), nsweeps)
+        return AG.attach_native(self.unpack(xn), xn)
+
     # ------------------------------------------------------------ reference API
     def coeffs(self, beta: Tensor) -> dict[str, Tensor]:
         return {'plaq': beta * (1.0 - 8.0 * self.c1), 'rect': beta * self.c1}

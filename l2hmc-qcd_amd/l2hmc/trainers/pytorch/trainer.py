@@ -472,6 +472,15 @@ class Trainer:
                     break
         return x
 
+    def thermalize(self, beta: float, x: Optional[Tensor] = None, nsweeps: int = 50, nover: int = 3) -> Tensor:
+        """SU(3): `nsweeps` heatbath sweeps at `beta`, each followed by `nover` overrelaxation sweeps
+        (`LatticeSU3.heatbath`), from x or a hot start: the local-update way to equilibrium beside `warmup`'s HMC."""
+        if not isinstance(self.lattice, LatticeSU3):
+            raise NotImplementedError('Trainer.thermalize: heatbath sweeps exist for SU(3) only')
+        x = self.lattice.random() if x is None else x
+        beta = float(beta.item()) if isinstance(beta, torch.Tensor) else float(beta)
+        return self.lattice.heatbath(self._prep(x), beta, nsweeps=nsweeps, nover=nover)[0]
+
     def eval(self, beta: Optional[float] = None, x: Optional[Tensor] = None,
              job_type: str = 'eval', nsteps: Optional[int] = None, eps: Optional[float] = None,
              nleapfrog: Optional[int] = None, dynamic_step_size: Optional[bool] = None) -> dict:
