@@ -168,6 +168,13 @@ int l2q_su3_expm_mul2(const void* xn, const void* vn, double eps, const float* m
 int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const float* mask_n,
                            int complement_first, void* out, double* vec, int nb, long V,
                            void* stream);
+/* l2q_su3_expm_mul2_vec8 / l2q_su3_projsu_vec8 that write the DIGITS of those values instead (the activation
+ * digit image of l2q_gemm_digits_f64 below: row = chain, K = 32 V; image: l2q_gemm_digits_bytes(nb, 32 V) bytes,
+ * 16-byte aligned; every value must satisfy |v| < 2^a_exp, else the next sliced layer's output is NaN).  Serve
+ * V % 64 == 0 (and whole chains: nfields % 4 == 0), L2Q_EINVAL otherwise. */
+int l2q_su3_expm_mul2_digits(const void* xn, const void* vn, double eps, const float* mask_n, int complement_first,
+                             void* out, void* image, int a_exp, int nb, long V, void* stream);
+int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, long V, void* stream);
 /* projectSU on every link (group/su3/pytorch/utils.py:341-346); out may alias in. */
 int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* stream);
 /* su3_to_vec(projectSU(.)) -> vec[nfields][8][V] double (group.py:138-147); the vnet
@@ -332,6 +339,19 @@ int l2q_gemm_sliced_f64(const double* A, const void* image, long K, int a_exp, c
                         const void* image2, long K2, int a2_exp, int M, int N, const double* bias,
                         const double* bias2, const double* coeff, double scale, int act, double* C, void* ws,
                         size_t ws_bytes, void* stream);
+/* l2q_gemm_sliced_f64 with the activations given as digit images too (csrc/gemm_digits.hip, csrc/digits.hpp:
+ * [M][K / 64][7][64] bytes, l2q_gemm_digits_bytes(M, K) of them, 16-byte aligned), written by
+ * l2q_gemm_digits_slice from fp64 A [M][K] or by the kernels that produce the activations
+ * (l2q_su3_projsu_digits, l2q_su3_expm_mul2_digits): the digits are made once instead of once per column tile.
+ * Same digits, sums and reduce as l2q_gemm_sliced_f64: the same bits.  A value outside (-2^a_exp, 2^a_exp) or a
+ * NaN seen by a producer turns the output of the next sliced layer launched on the device into NaN.  Workspace:
+ * l2q_gemm_sliced_ws_bytes. */
+size_t l2q_gemm_digits_bytes(long M, long K);
+int l2q_gemm_digits_slice(const double* A, long M, long K, int a_exp, void* image, size_t image_bytes, void* stream);
+int l2q_gemm_digits_f64(const void* A, const void* image, long K, int a_exp, const void* A2, const void* image2,
+                        long K2, int a2_exp, int M, int N, const double* bias, const double* bias2,
+                        const double* coeff, double scale, int act, double* C, void* ws, size_t ws_bytes,
+                        void* stream);
 /* The three output heads of a LeapfrogLayer AND the generalised momentum update in one kernel
  * (network.py:547-551 + dynamics.py:1266-1297): for chain m, entry n
  *   s = cs[n] tanh(Z.Ws[n] + bs[n]);  t = scale_t (Z.Wt[n] + bt[n]);  q = cq[n] tanh(Z.Wq[n] + bq[n])

@@ -594,6 +594,16 @@ static long gs_pick_klen(int M, int N, long K, long K2) {
   return klen;
 }
 
+// what gemm_digits.hip (the same layer on activation digit images, digits.hpp) shares with this file: with the same
+// k-grouping, the same flag and the same reduce kernel its output has the bits of l2q_gemm_sliced_f64's
+long gs_klen(int M, int N, long K, long K2) { return gs_pick_klen(M, N, K, K2); }
+int* gs_flag() { return gs_flag_ptr(); }
+void gs_launch_reduce(const double* part, int groups, long MN, int N, const double* bias, const double* bias2,
+                      const double* coeff, double scale, int act, int* flag, double* C, hipStream_t st) {
+  hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)cdiv(MN, 256)), dim3(256), 0, st, part, groups, MN, N, bias, bias2,
+                     coeff, scale, act, flag, C);
+}
+
 }  // namespace l2q
 
 using namespace l2q;

@@ -5,6 +5,7 @@
 // registers (su3_math.hpp).  Stencil neighbours are re-read through L1/L2; the 1-D grids
 // are XCD-swizzled so the blocks that share a chain's links share an XCD's L2.
 #include "su3_launch.hpp"
+#include "digits.hpp"
 #include "half_common.hpp"
 
 namespace l2q {
@@ -644,17 +645,29 @@ __global__ __launch_bounds__(4 * kFS / LPT, (kFS == 64 || LPT == 2) ? 1 : 2) voi
 #ifndef XU_OCC
 #define XU_OCC 3        // wavefronts per SIMD the x-update is compiled for (A/B builds override)
 #endif
-template <bool TWO, bool VEC8>
-__global__ __launch_bounds__(kBlock, XU_OCC) void su3_expm_mul_kernel(const double2* xn,
-                                                              const double2* __restrict__ vn,
-                                                              double eps,
-                                                              const float* __restrict__ mask,
-                                                              int complement, double2* out,
-                                                              double* __restrict__ out_vec,
-                                                              int V, long nblk, int lo) {
-  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;     // f = chain*4 + mu
-  const int s = (int)blk * kBlock + threadIdx.x;
-  if (s >= V) return;
+// The eight vec8 values of link (f, s) -> their digits in the activation image of the int8-sliced input layer
+// (digits.hpp; row = chain, k = ((mu 8 + a) V + s), V % 64 == 0: the 64 sites of a wavefront are one slab of the
+// row).  Called by whole wavefronts.  Returns nonzero for a
+// value outside (-lim, lim) or a NaN.
+__device__ __forceinline__ int su3_vec8_to_digits(const double (&w)[8], char* img, long f, int s, int V, double dsc,
+                                                  double dlim) {
+  const int lane = threadIdx.x & 63;
+  char* slab = img + ((f >> 2) * (V >> 1) + (f & 3) * 8L * (V >> 6) + (s >> 6)) * GD_SLAB;
+  int bad = 0;
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    unsigned dl, dh;
+    bad |= gd_digits(w[a], dsc, dlim, dl, dh);
+    gd_store_slab(slab + a * (long)(V >> 6) * GD_SLAB, lane, dl, dh);
+  }
+  return bad;
+}
+// VEC: 0 links only, 1 + vec8 as fp64 (out_vec), 2 + vec8 as digits (out_vec is the image; V % 64 == 0)
+template <bool TWO, int VEC>
+__device__ __forceinline__ void su3_expm_mul_body(const double2* xn, const double2* __restrict__ vn, double eps,
+                                                  const float* __restrict__ mask, int complement, double2* out,
+                                                  void* __restrict__ out_vec, int V, long f, int s, int lo,
+                                                  double dsc, double dlim, int* flag) {
   const int mu = (int)(f & 3);
   // The three stages below sit in run-time conditionals that are always taken (`lo` = 0 is a kernel
   // ARGUMENT): hipcc then allocates each stage on its own instead of scheduling the exponential, the
@@ -727,16 +740,45 @@ __global__ __launch_bounds__(kBlock, XU_OCC) void su3_expm_mul_kernel(const doub
   }
   M3& r = x;
   store_link(out + f * 9L * V, V, s, r);
-  if constexpr (VEC8) {
+  if constexpr (VEC != 0) {
     if (s >= lo) {
       M3 p;
       m3_project_su(p, r);
       double w[8];
       m3_to_vec8(w, p);
+      if constexpr (VEC == 1) {
 #pragma unroll
-      for (int a = 0; a < 8; ++a) out_vec[(f * 8 + a) * (long)V + s] = w[a];
+        for (int a = 0; a < 8; ++a) static_cast<double*>(out_vec)[(f * 8 + a) * (long)V + s] = w[a];
+      } else {
+        if (su3_vec8_to_digits(w, static_cast<char*>(out_vec), f, s, V, dsc, dlim)) atomicOr(flag, 1);
+      }
     }
   }
+}
+template <bool TWO, bool VEC8>
+__global__ __launch_bounds__(kBlock, XU_OCC) void su3_expm_mul_kernel(const double2* xn,
+                                                              const double2* __restrict__ vn,
+                                                              double eps,
+                                                              const float* __restrict__ mask,
+                                                              int complement, double2* out,
+                                                              double* __restrict__ out_vec,
+                                                              int V, long nblk, int lo) {
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;     // f = chain*4 + mu
+  const int s = (int)blk * kBlock + threadIdx.x;
+  if (s >= V) return;
+  su3_expm_mul_body<TWO, VEC8 ? 1 : 0>(xn, vn, eps, mask, complement, out, out_vec, V, f, s, lo, 0.0, 0.0, nullptr);
+}
+// the two half-updates + the digits of su3_to_vec(projectSU(x')) instead of its fp64 values
+__global__ __launch_bounds__(kBlock, XU_OCC) void su3_expm_mul_digits_kernel(const double2* xn,
+                                                                     const double2* __restrict__ vn, double eps,
+                                                                     const float* __restrict__ mask, int complement,
+                                                                     double2* out, char* __restrict__ image, int V,
+                                                                     long nblk, int lo, double dsc, double dlim,
+                                                                     int* flag) {
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int s = (int)blk * kBlock + threadIdx.x;
+  if (s >= V) return;                                           // (V % 64 == 0: whole wavefronts)
+  su3_expm_mul_body<true, 2>(xn, vn, eps, mask, complement, out, image, V, f, s, lo, dsc, dlim, flag);
 }
 
 // MODE 0: projectSU -> links;  1: projectSU -> vec8;  2: projectTAH -> links;  3: projectU
@@ -765,6 +807,19 @@ __global__ __launch_bounds__(kBlock) void su3_project_kernel(const double2* in,
   } else {
     store_link(out_links + f * 9L * V, V, s, r);
   }
+}
+// projectSU -> the digits of vec8 (V % 64 == 0: whole wavefronts)
+__global__ __launch_bounds__(kBlock) void su3_project_digits_kernel(const double2* in, char* __restrict__ image, int V,
+                                                                    long nblk, double dsc, double dlim, int* flag) {
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int s = (int)blk * kBlock + threadIdx.x;
+  if (s >= V) return;
+  M3 x, r;
+  load_link(x, in + f * 9L * V, V, s);
+  m3_project_su(r, x);
+  double v[8];
+  m3_to_vec8(v, r);
+  if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
 }
 
 // out = op(a) * op(b) per link, op = identity or adjoint   (SU3.mul, group.py:56-69)
@@ -976,6 +1031,14 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
     snprintf(buf, buf_bytes, "%s", gemm_h_kernel_name(T, X, (long)Y));      // (T, X, Y) carry (M, N, K) here
   } else if (!strcmp(entry, "l2q_gemm_sliced_f64")) {
     snprintf(buf, buf_bytes, "gemm_sliced_kernel");
+  } else if (!strcmp(entry, "l2q_gemm_digits_f64")) {
+    snprintf(buf, buf_bytes, "gemm_digits_kernel");
+  } else if (!strcmp(entry, "l2q_gemm_digits_slice")) {
+    snprintf(buf, buf_bytes, "gd_slice_kernel");
+  } else if (!strcmp(entry, "l2q_su3_expm_mul2_digits")) {
+    snprintf(buf, buf_bytes, "su3_expm_mul_digits_kernel");
+  } else if (!strcmp(entry, "l2q_su3_projsu_digits")) {
+    snprintf(buf, buf_bytes, "su3_project_digits_kernel");
   } else if (!strcmp(entry, "l2q_gemm_f64")) {
     snprintf(buf, buf_bytes, "%s", gemm_f64_kernel_name());
   }
@@ -1123,6 +1186,36 @@ int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const flo
                      0, (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n,
                      complement_first, (double2*)out, vec, (int)V, nblk, 0);
   return check_launch("l2q_su3_expm_mul2_vec8");
+}
+
+int l2q_su3_expm_mul2_digits(const void* xn, const void* vn, double eps, const float* mask_n, int complement_first,
+                             void* out, void* image, int a_exp, int nb, long V, void* stream) {
+  L2Q_REQUIRE(xn && vn && out && mask_n && image, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_field_ok(nb, V) && V % 64 == 0, L2Q_EINVAL, "the digit image serves V % 64 == 0");
+  L2Q_REQUIRE(a_exp > -900 && a_exp < 900, L2Q_EINVAL, "bad operand exponent");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, L2Q_ESHAPE, "the image must be 16-byte aligned");
+  int* flag = gs_flag();
+  L2Q_REQUIRE(flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
+  const long nblk = cdiv(V, kBlock);
+  hipLaunchKernelGGL(su3_expm_mul_digits_kernel, dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n, complement_first,
+                     (double2*)out, (char*)image, (int)V, nblk, 0, ldexp(1.0, GD_BITS - a_exp), ldexp(1.0, a_exp), flag);
+  return check_launch("l2q_su3_expm_mul2_digits");
+}
+
+int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, long V, void* stream) {
+  L2Q_REQUIRE(in && image, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_field_ok(nfields, V) && V % 64 == 0 && nfields % 4 == 0, L2Q_EINVAL,
+              "the digit image serves whole chains (4 fields each) with V % 64 == 0");
+  L2Q_REQUIRE(a_exp > -900 && a_exp < 900, L2Q_EINVAL, "bad operand exponent");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, L2Q_ESHAPE, "the image must be 16-byte aligned");
+  int* flag = gs_flag();
+  L2Q_REQUIRE(flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
+  const long nblk = cdiv(V, kBlock);
+  hipLaunchKernelGGL(su3_project_digits_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const double2*)in, (char*)image, (int)V, nblk, ldexp(1.0, GD_BITS - a_exp), ldexp(1.0, a_exp),
+                     flag);
+  return check_launch("l2q_su3_projsu_digits");
 }
 
 int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* stream) {

@@ -492,6 +492,80 @@ def gemm_sliced(a: torch.Tensor, image: torch.Tensor, n: int, bias: Optional[tor
     return out
 
 
+# activation digit images (csrc/digits.hpp, csrc/gemm_digits.hip): [True] = the sampler's x-update and projection
+# write the vnet inputs as int8 digits and the sliced input layer takes both operands as images
+USE_DIGIT_INPUTS = [True]
+
+
+class DigitImage:
+    """The digits of an fp64 operand [m, k] with every |entry| < 2^exp: `buf` uint8 [m, k / 64, 7, 64]."""
+    __slots__ = ('buf', 'shape', 'exp')
+
+    def __init__(self, buf: torch.Tensor, m: int, k: int, exp: int):
+        self.buf, self.shape, self.exp = buf, (m, k), exp
+
+
+def digits_ok(nb: int, V: int) -> bool:
+    """Lattices whose vnet inputs [nb, 32 V] the producers can write as digit images."""
+    return nb > 0 and V > 0 and V % 64 == 0
+
+
+def _digit_buf(m: int, k: int, device) -> torch.Tensor:
+    return torch.empty((m, k // 64, 7, 64), dtype=torch.uint8, device=device)
+
+
+def gemm_digits_slice(a: torch.Tensor, a_exp: int = SLICED_INPUT_EXP) -> Optional[DigitImage]:
+    """Digit image of fp64 a [m, k]; None when k % 64 != 0 (or not fp64)."""
+    m, k = a.shape
+    if a.dtype != torch.float64 or k % 64 or m <= 0:
+        return None
+    buf = _digit_buf(m, k, a.device)
+    N.call('l2q_gemm_digits_slice', a.contiguous(), m, k, int(a_exp), buf, buf.numel())
+    return DigitImage(buf, m, k, int(a_exp))
+
+
+def su3_projsu_digits_n(xn: torch.Tensor, a_exp: int = SLICED_INPUT_EXP) -> Optional[DigitImage]:
+    """su3_projsu_vec8_n(xn).reshape(nb, -1) as a digit image ([nb, 4, 9, V] links); None when the lattice does
+    not qualify (digits_ok)."""
+    nb, V = xn.shape[0], xn.shape[-1]
+    if xn.dim() != 4 or xn.shape[1] != 4 or not digits_ok(nb, V):
+        return None
+    buf = _digit_buf(nb, 32 * V, xn.device)
+    N.call('l2q_su3_projsu_digits', xn, buf, int(a_exp), nb * 4, V)
+    return DigitImage(buf, nb, 32 * V, int(a_exp))
+
+
+def su3_expm_mul2_digits_n(xn: torch.Tensor, vn: torch.Tensor, eps: float, mask_n: torch.Tensor,
+                           complement_first: bool, out: Optional[torch.Tensor] = None,
+                           a_exp: int = SLICED_INPUT_EXP):
+    """su3_expm_mul2_vec8_n with the vec8 of x' as a digit image: (x', image); None when the lattice does not
+    qualify (nothing is launched)."""
+    nb, _, _, V = xn.shape
+    if not digits_ok(nb, V):
+        return None
+    out = torch.empty_like(xn) if out is None else out
+    buf = _digit_buf(nb, 32 * V, xn.device)
+    N.call('l2q_su3_expm_mul2_digits', xn, vn, float(eps), mask_n, int(complement_first), out, buf, int(a_exp),
+           nb, V)
+    return out, DigitImage(buf, nb, 32 * V, int(a_exp))
+
+
+def gemm_digits(a: DigitImage, image: torch.Tensor, n: int, bias: Optional[torch.Tensor] = None, *,
+                a2: Optional[DigitImage] = None, image2: Optional[torch.Tensor] = None,
+                bias2: Optional[torch.Tensor] = None, coeff: Optional[torch.Tensor] = None,
+                scale: float = 1.0, act: Optional[str] = None) -> torch.Tensor:
+    """gemm_sliced with the activations given as digit images: the same bits."""
+    m, k = a.shape
+    k2 = 0 if a2 is None else a2.shape[1]
+    if not gemm_sliced_ok(m, n, k, k2) or (a2 is not None and (image2 is None or a2.shape[0] != m)):
+        raise N.L2QError(f'gemm_digits: a{a.shape} n {n} k2 {k2}')
+    out = torch.empty((m, n), dtype=torch.float64, device=a.buf.device)
+    ws = N.workspace(int(N.load().l2q_gemm_sliced_ws_bytes(m, n, k, k2)), a.buf.device)
+    N.call('l2q_gemm_digits_f64', a.buf, image, k, a.exp, None if a2 is None else a2.buf, image2, k2,
+           0 if a2 is None else a2.exp, m, n, bias, bias2, coeff, float(scale), N.ACT[act], out, ws, ws.numel())
+    return out
+
+
 def gemm_ex(a: torch.Tensor, w: torch.Tensor, a_trans: bool = False, w_trans: bool = False,
             out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """C (+)= Aop @ Wop^T without transposed copies (include/l2q.h: l2q_gemm_ex).  a: [m, k], or

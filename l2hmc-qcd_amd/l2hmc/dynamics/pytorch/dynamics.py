@@ -595,6 +595,21 @@ class Dynamics(nn.Module):
         return (self.fuse_heads and self._networks_built and self.group == 'SU3'
                 and vnet.units[-1] % 2 == 0)
 
+    def _digit_inputs(self, vnet, nb: int, V: int) -> bool:
+        """The vnet inputs travel as int8 digit images (csrc/digits.hpp) from the kernels that make them -- the
+        projection, the x-update -- to the sliced input layer: the sampler only (the tape keeps fp64 activations),
+        with every knob of the sliced input layer on, on lattices the producers serve, and once the digit
+        images of the layer's weights exist (the fp64-activation layer builds them at its first call)."""
+        if (self.training or not self.sliced_input or not ops.USE_SLICED_INPUT[0] or not ops.USE_DIGIT_INPUTS[0]
+                or not ops.digits_ok(nb, V) or not self._can_fuse_heads(vnet)):
+            return False
+        if getattr(vnet, 'half_dtype', None) is not None:
+            return False
+        p = self._perms()
+        w = vnet.kernel_weights(p['in'], p['out'])
+        return (w.get('input_img') is not None and w['wx'].dtype == torch.float64
+                and ops.gemm_sliced_pays(nb, w['wx'].shape[0], 32 * V, 32 * V))
+
     def _v_inputs_n(self, vnet, xn: Tensor, beta, ts: Optional[SamplerStepper] = None):
         """(force, hidden activation z, kernel weights) for the fused heads kernel.  `ts`
         (trajectory-local, `ts.reuse`): the force, the vec8 network inputs and z depend only on x
@@ -627,12 +642,22 @@ class Dynamics(nn.Module):
             return fn, ts.z[id(vnet)], w
         if reuse and ts.xv is not None:
             xv, fv = ts.xv, ts.fv
+            if isinstance(xv, ops.DigitImage) and not self._digit_inputs(vnet, nb, xn.shape[-1]):
+                # kept for another network of this x; this one takes fp64 activations
+                xv = ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
+                fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
         else:
             pre = None
             if reuse:
                 pre, ts.xv_pre = ts.xv_pre, None     # vec8(x) emitted by the x-update that produced x
-            xv = pre if pre is not None else ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
-            fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
+            if self._digit_inputs(vnet, nb, xn.shape[-1]):
+                xv = pre if isinstance(pre, ops.DigitImage) else ops.su3_projsu_digits_n(xn)
+                fv = ops.su3_projsu_digits_n(fn)
+            else:
+                if isinstance(pre, ops.DigitImage):      # (a knob changed since the x-update: x itself is at hand)
+                    pre = None
+                xv = pre if pre is not None else ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
+                fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
             if reuse:
                 ts.xv, ts.fv = xv, fv
         z = vnet.hidden_flat(xv, fv, w, sliced_exp=ops.SLICED_INPUT_EXP if self.sliced_input else None)
@@ -826,9 +851,13 @@ class Dynamics(nn.Module):
             eps = self._eps('x', st)
             if (ts is not None and ts.reuse and self.fuse_x_vec8
                     and self._can_fuse_heads(self._get_vnet(st))):
-                _, xv = ops.su3_expm_mul2_vec8_n(xr, vn, eps if forward else -eps, m, not forward,
-                                                 out=xn)
-                ts.xv_pre = xv.reshape(xn.shape[0], -1)
+                if self._digit_inputs(self._get_vnet(st), xn.shape[0], xn.shape[-1]):
+                    _, ts.xv_pre = ops.su3_expm_mul2_digits_n(xr, vn, eps if forward else -eps, m, not forward,
+                                                              out=xn)
+                else:
+                    _, xv = ops.su3_expm_mul2_vec8_n(xr, vn, eps if forward else -eps, m, not forward,
+                                                     out=xn)
+                    ts.xv_pre = xv.reshape(xn.shape[0], -1)
             else:
                 ops.su3_expm_mul2_n(xr, vn, eps if forward else -eps, m, not forward, out=xn)
         else:
@@ -1540,7 +1569,8 @@ class GraphedTransition:
         masks = tuple(id(m) for m in d.masks)
         flags = (d.fuse_heads, d.fuse_x_updates, d.reuse_v_inputs, d.pair_v_updates,
                  d.fuse_u1_steps, d.fuse_half_heads, d.merge_hmc_kicks, d.sliced_heads,
-                 ops.USE_SLICED_HEADS[0], d.sliced_input, ops.USE_SLICED_INPUT[0], d.pair_v_updates_verbose,
+                 ops.USE_SLICED_HEADS[0], d.sliced_input, ops.USE_SLICED_INPUT[0], ops.USE_DIGIT_INPUTS[0],
+                 d.pair_v_updates_verbose,
                  getattr(d, 'fuse_x_vec8', None), d.net_precision, d.config.verbose, d.training)
         return (ops.PARAM_GENERATION[0], params, masks, flags)
 

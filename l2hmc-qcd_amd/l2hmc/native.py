@@ -47,6 +47,8 @@ SIGNATURES = {
     'l2q_su3_expm_mul': (I, [P, P, D, P, I, P, I, L, P]),
     'l2q_su3_expm_mul2': (I, [P, P, D, P, I, P, I, L, P]),
     'l2q_su3_expm_mul2_vec8': (I, [P, P, D, P, I, P, P, I, L, P]),
+    'l2q_su3_expm_mul2_digits': (I, [P, P, D, P, I, P, P, I, I, L, P]),
+    'l2q_su3_projsu_digits': (I, [P, P, I, L, L, P]),
     'l2q_su3_project_su': (I, [P, P, L, L, P]),
     'l2q_su3_projsu_vec8': (I, [P, P, L, L, P]),
     'l2q_su3_project_tah': (I, [P, P, L, L, P]),
@@ -74,6 +76,9 @@ SIGNATURES = {
     'l2q_gemm_sliced_build': (I, [P, I, L, P, Z, P, P]),
     'l2q_gemm_sliced_ws_bytes': (Z, [I, I, L, L]),
     'l2q_gemm_sliced_f64': (I, [P, P, L, I, P, P, L, I, I, I, P, P, P, D, I, P, P, Z, P]),
+    'l2q_gemm_digits_bytes': (Z, [L, L]),
+    'l2q_gemm_digits_slice': (I, [P, L, L, I, P, Z, P]),
+    'l2q_gemm_digits_f64': (I, [P, P, L, I, P, P, L, I, I, I, P, P, P, D, I, P, P, Z, P]),
     'l2q_vnet_heads_vupdate_f64': (I, [P, I, I, L, P, P, P, D, P, P, D, P, P, P, D, P, P, I, D, I, P, P, Z, P]),
     'l2q_vnet_heads_vupdate_to_f64': (I, [P, I, I, L, P, P, P, D, P, P, D, P, P, P, D, P, P, P, I, D, I, P, P, Z, P]),
     'l2q_vnet_heads_vupdate_pair_f64': (I, [P, I, I, L, P, P, P, D, P, P, D, P, P, P, D, P, P, I, D, I, I, D, I, P, P, Z, P]),

@@ -685,7 +685,14 @@ class LeapfrogLayer(nn.Module):
         if getattr(self, 'half_dtype', None) is not None:
             raise NotImplementedError('hidden_flat feeds the fp64 fused heads kernel (SU(3))')
         z = None
-        if sliced_exp is not None and ops.USE_SLICED_INPUT[0] and x.dtype == torch.float64 and \
+        if isinstance(x, ops.DigitImage):
+            # both inputs as digit images (csrc/gemm_digits.hip), written by the kernels that made them; the
+            # caller has seen the weight images in `w` (Dynamics._digit_inputs)
+            if not isinstance(v, ops.DigitImage) or w.get('input_img') is None:
+                raise ValueError('hidden_flat: digit operands need each other and the weight images')
+            z = ops.gemm_digits(x, w['input_img'][0], w['wx'].shape[0], w['bx'], a2=v, image2=w['input_img'][1],
+                                bias2=w['bv'], act=self.act)
+        elif sliced_exp is not None and ops.USE_SLICED_INPUT[0] and x.dtype == torch.float64 and \
                 ops.gemm_sliced_pays(x.shape[0], w['wx'].shape[0], x.shape[1], v.shape[1]):
             if 'input_img' not in w:
                 # the images take 7/8 of the weights' bytes again (2 x 235 MB per vnet at cfg-4, 2 x 3.8 GB
