@@ -140,6 +140,17 @@ int l2q_diff_norm2_reduce(const double* a, const double* b, int nb, long n, doub
  * Algorithmic traffic: 1152 B per (chain, site). */
 int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, int Y, int Z,
                   void* stream);
+/* l2q_su3_force that also returns the plaquette sum of the x it was taken at: plaq[c] = sum over sites and the 6
+ * planes of Re tr P (out[c][0] of l2q_su3_plaq_reduce, equal to rounding: another summation order; action =
+ * -(beta/3) plaq[c]).  The thread-per-link kernel holds W = U A per link when it stores F, and sum_links Re tr W =
+ * 4 sum_plaq Re tr P: it forms the real diagonal of W (which F does not need) and reduces it -- per thread over its
+ * sweep, once over the workgroup, one partial per workgroup at a fixed index, then the fixed-order sum of
+ * l2q_su3_plaq_reduce's second stage: no atomics, the same bits every run.  F is bit-identical to l2q_su3_force.  On
+ * lattices (or under force_tile settings) that kernel does not serve, the ordinary force and the plaquette reduction
+ * run one after the other.  ws: l2q_su3_force_action_ws_bytes(...) bytes. */
+size_t l2q_su3_force_action_ws_bytes(int nb, int T, int X, int Y, int Z);
+int l2q_su3_force_action(const void* xn, double beta, void* fn, double* plaq, int nb, int T, int X, int Y, int Z,
+                         void* ws, size_t ws_bytes, void* stream);
 /* fused plain-HMC half-kick: v += coef * F(x)   (dynamics/pytorch/dynamics.py:903-911,
  * coef = -eps/2); F is never materialised. */
 int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int nb, int T,
@@ -193,6 +204,11 @@ int l2q_su3_kinetic_reduce(const void* vn, int nb, long V, double* out, void* ws
 /* momenta from 8 standard-normal fields normals[8][nfields*V] in the reference's draw order
  * r3, r8, r01, r02, r12, i01, i02, i12 (group/su3/pytorch/utils.py:171-195). */
 int l2q_su3_assemble_tah(const double* normals, void* vn, long nfields, long V, void* stream);
+/* The same for whole chains (4 nb fields) with norm2[c] = sum over the chain's 36 V entries of |p|^2, summed
+ * from the values as stored (fixed order; l2q_su3_kinetic_reduce of vn is 0.5 * (norm2[c] - 32 V) to rounding).
+ * ws >= nb * 4 * ceil(V/256) doubles. */
+int l2q_su3_assemble_tah_norm2(const double* normals, void* vn, int nb, long V, double* norm2, void* ws,
+                               size_t ws_bytes, void* stream);
 /* max over links of |x^H x - 1|_F^2 + |det x - 1|^2 and its mean, per chain
  * (checkSU, utils.py:376-391): out[c][0] = sqrt(mean/20), out[c][1] = sqrt(max/20). */
 int l2q_su3_check_su(const void* xn, int nb, long V, double* out, void* ws, size_t ws_bytes,
@@ -409,7 +425,9 @@ size_t l2q_vnet_heads_ws_bytes(int M, long N);
  * point (mean |w| below 2^-6 of the largest): keep the fp64 kernel then.  The call synchronises the
  * stream.  l2q_vnet_heads_vupdate_sliced_f64 is the four fp64 entry points in one: v_in NULL = in
  * place; pair = 0 ignores flip_between / eps2 / forward2; logdet1 / vnorm2_mid non-NULL (pair only) =
- * the mid-point outputs.  Results agree with the fp64 kernels to fp64 rounding (not bit for bit).
+ * the mid-point outputs; pair = 0 with logdet1 NULL and vnorm2_mid non-NULL: vnorm2_mid [M] = sum |v_out|^2 of
+ * the momentum the single update writes (v and logdet are the same bits with or without the request).
+ * Results agree with the fp64 kernels to fp64 rounding (not bit for bit).
  * The per-call operand Z gets the same conditioning test as the weights, as a DIAGNOSTIC: rows whose
  * mean |z| is below 2^-6 of their largest entry (possible with an unbounded activation; never with
  * tanh) are counted per device -- their products are exact to 2^-54 K max|z| max|w| rather than to

@@ -97,6 +97,8 @@ struct HeadsArgs {
   double* tape_s = nullptr;
   double* tape_t = nullptr;
   double* tape_q = nullptr;
+  // single-update kernels of heads_sliced.hip: also accumulate sum |v_out|^2 into ke_part (a run-time request)
+  int want_ke = 0;
 };
 
 }  // namespace l2q

@@ -558,6 +558,7 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
         }
         if (!PAIR) {
           if (ok) ld[r] += lj;
+          if (!TAPE && ok && a.want_ke) ke[r] += fma(vr, vr, vi * vi);
         } else {
           if (MID) { if (ok) { ld1[r] += lj; ke[r] += fma(vr, vr, vi * vi); } }
           if (a.flip) { vr = -vr; vi = -vi; }
@@ -682,18 +683,18 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     double x = ld[r], x1 = ld1[r], xk = ke[r];
+    const bool vn2 = !PAIR && !TAPE && a.want_ke;      // sum |v_out|^2 of the single update, on request
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) {
       x += __shfl_xor(x, off, 64);
-      if (MID) { x1 += __shfl_xor(x1, off, 64); xk += __shfl_xor(xk, off, 64); }
+      if (MID) x1 += __shfl_xor(x1, off, 64);
+      if (MID || vn2) xk += __shfl_xor(xk, off, 64);
     }
     const long m = mrow + r;
     if ((lane & 15) == 0 && m < a.M) {
       a.logdet_part[m * a.ncols_part + cw] = x;
-      if (MID) {
-        a.ld1_part[m * a.ncols_part + cw] = x1;
-        a.ke_part[m * a.ncols_part + cw] = xk;
-      }
+      if (MID) a.ld1_part[m * a.ncols_part + cw] = x1;
+      if (MID || vn2) a.ke_part[m * a.ncols_part + cw] = xk;
     }
   }
 }
@@ -747,6 +748,9 @@ static int sliced_launch(const char* who, double* tape_s, double* tape_t, double
   a.v = (double*)v; a.vin = (const double*)vin; a.F = (const double*)force;
   a.logdet_part = part; a.ld1_part = part + (size_t)M * ncw; a.ke_part = part + 2 * (size_t)M * ncw;
   a.M = M; a.N = (int)N; a.K = K; a.ncols_part = ncw;
+  // a single update asked for vnorm2_mid (no mid-point exists): sum |v_out|^2 of the momentum it writes
+  const bool vn2 = !pair && !mid && !tape_s && vnorm2_mid != nullptr;
+  a.want_ke = vn2 ? 1 : 0;
   SlicedArgs o;
   o.Zs = zs; o.zscale = zscale; o.Wsl = (const char*)sliced;
   o.wscale = (const double*)((const char*)sliced + sliced_scale_off(N));
@@ -801,6 +805,7 @@ static int sliced_launch(const char* who, double* tape_s, double* tape_t, double
     launch_finalize(a.ld1_part, logdet1, M, ncw, 1, 1.0, 0.0, st);
     launch_finalize(a.ke_part, vnorm2_mid, M, ncw, 1, 1.0, 0.0, st);
   }
+  if (vn2) launch_finalize(a.ke_part, vnorm2_mid, M, ncw, 1, 1.0, 0.0, st);
   return check_launch(who);
 }
 

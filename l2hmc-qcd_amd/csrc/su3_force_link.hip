@@ -78,8 +78,13 @@ __host__ __device__ constexpr int lk_other(int mu, int j) { return j + (j >= mu 
 // MODE 2 (training, the VJP of the force with the staple sum held constant like the reference's
 //   autograd.grad(action) without create_graph, lattice/su3/pytorch/lattice.py:299-308):
 //   out += coef * TAH(vin) A^H  with vin = g_F, out = g_x  (the same staple sweep, another epilogue)
+// MODE 3: MODE 0 that also forms the real diagonal of W = U A and returns the thread's sum of Re tr W over its
+//   sweep (sum over links of Re tr(U_mu A_mu) = 4 * sum over plaquettes of Re tr P: the Wilson action of the x
+//   the force was taken at).  The other modes return 0.
 template <int MODE, int MU, int INM>
-__device__ __forceinline__ void force_link_sweep(const LkCtx& c) {
+__device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
+  constexpr bool ACTION = MODE == 3;
+  double esum = 0.0;
   constexpr bool IN_MU = lk_in<INM>(MU);
   const Dims& d = c.d;
   const int T = d.T, V16 = c.V16, Vs16 = c.Vs16;
@@ -277,13 +282,14 @@ __device__ __forceinline__ void force_link_sweep(const LkCtx& c) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             // the real parts of the diagonal cancel in (W - W^H) / 2: not formed (18 of the 108 FMAs)
-            if (L2Q_LK_FULL_DIAG || i != j) { sr = fma(ur.re[k], acc.re[3 * k + j], sr); sr = fma(-ur.im[k], acc.im[3 * k + j], sr); }
+            if (L2Q_LK_FULL_DIAG || ACTION || i != j) { sr = fma(ur.re[k], acc.re[3 * k + j], sr); sr = fma(-ur.im[k], acc.im[3 * k + j], sr); }
             si = fma(ur.re[k], acc.im[3 * k + j], si); si = fma(ur.im[k], acc.re[3 * k + j], si);
           }
           ua.re[3 * i + j] = sr; ua.im[3 * i + j] = si;
         }
       }
       const int so = MU * 9 * V16 + gcur;
+      if (ACTION) esum += (ua.re[0] + ua.re[4]) + ua.re[8];
       const double tri = (ua.im[0] + ua.im[4] + ua.im[8]) / 3.0;     // the trace term is imaginary
 #pragma unroll
       for (int i = 0; i < 3; ++i)
@@ -326,15 +332,18 @@ __device__ __forceinline__ void force_link_sweep(const LkCtx& c) {
     cur ^= 1;
     if (!(L2Q_LK_EXP & 8)) __syncthreads();           // next slice in place
   }
+  return esum;
 }
 
 #ifndef L2Q_LK_OCC
 #define L2Q_LK_OCC 2
 #endif
+// One workgroup's sweep; returns the thread's action sum (MODE 3) and, in `w`, the workgroup's place in the
+// chain-major order (chain, t-chunk, spatial tile) that the partial sums are stored in.
 template <int MODE, int INM>
-__global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
-    const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz, double coef,
-    const double2* vin, double2* out, int lo, int stagger) {
+__device__ __forceinline__ double force_link_block(const double2* __restrict__ xn, const Dims& d, int nsb, int tsplit,
+                                                   int swz, double coef, const double2* vin, double2* out, int lo,
+                                                   int stagger, long& w) {
   // The two workgroups co-resident on a CU start together, do identical work and would stay in
   // lock-step: both at their slice barriers / halo loads at the same time, both wanting the fp64
   // pipe at the same time.  Delaying the second resident set ONCE (tuning force_stagger, units of
@@ -342,7 +351,7 @@ __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
   if (stagger > 0 && blockIdx.x >= 256 && blockIdx.x < 512) {
     for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(32);
   }
-  const long w = xcd_swizzle(blockIdx.x, gridDim.x, swz);
+  w = xcd_swizzle(blockIdx.x, gridDim.x, swz);
   const int per_chain = nsb * tsplit;
   const long c = w / per_chain;
   const int rr = (int)(w % per_chain);
@@ -361,7 +370,7 @@ __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
   const int chain_bytes = 36 * k.V16;
   k.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xn + c * 36L * V), 0, chain_bytes, 0x00020000);
   k.ro = __builtin_amdgcn_make_buffer_rsrc((void*)(out + c * 36L * V), 0, chain_bytes, 0x00020000);
-  k.rv = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE != 0 ? vin : out) + c * 36L * V), 0, chain_bytes, 0x00020000);
+  k.rv = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE == 1 || MODE == 2 ? vin : out) + c * 36L * V), 0, chain_bytes, 0x00020000);
   k.sp = sb * kRS + k.lt;
   {
     int q = k.sp;
@@ -372,11 +381,33 @@ __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
   k.coef = coef;
   k.lo = lo;
   switch (wv) {
-    case 0: force_link_sweep<MODE, 0, INM>(k); break;
-    case 1: force_link_sweep<MODE, 1, INM>(k); break;
-    case 2: force_link_sweep<MODE, 2, INM>(k); break;
-    default: force_link_sweep<MODE, 3, INM>(k); break;
+    case 0: return force_link_sweep<MODE, 0, INM>(k);
+    case 1: return force_link_sweep<MODE, 1, INM>(k);
+    case 2: return force_link_sweep<MODE, 2, INM>(k);
+    default: return force_link_sweep<MODE, 3, INM>(k);
   }
+}
+
+template <int MODE, int INM>
+__global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
+    const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz, double coef,
+    const double2* vin, double2* out, int lo, int stagger) {
+  long w;
+  (void)force_link_block<MODE, INM>(xn, d, nsb, tsplit, swz, coef, vin, out, lo, stagger, w);
+}
+
+// The plain force that also leaves part[w] = this workgroup's sum over its links of Re tr(U A): one reduction over
+// the block after its sweep, one store at a fixed index, no atomics (l2q_su3_force_action sums the partials in a
+// fixed order).  A workgroup belongs to one chain, so the partials of a chain are contiguous.
+template <int INM>
+__global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_action_kernel(
+    const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz, double coef, double2* out, int lo,
+    int stagger, double* __restrict__ part) {
+  long w;
+  const double e = force_link_block<3, INM>(xn, d, nsb, tsplit, swz, coef, out, out, lo, stagger, w);
+  // (the sweep ends at a workgroup barrier: nobody reads the tile's LDS any more)
+  const double r = block_sum(e, reinterpret_cast<double*>(fr_lds));
+  if (threadIdx.x == 0) part[w] = r;
 }
 
 template <int MODE, int INM>
@@ -418,13 +449,45 @@ void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const
   }
 }
 
+// >= ~2 resident rounds of 2 x 256 workgroups
+static int force_link_tsplit(const Dims& d, int nb) {
+  return t_chunks((long)nb * (d.X * d.Y * d.Z / kRS), d.T, 1024, tuning().force_tsplit);
+}
+
+long force_link_action_parts(const Dims& d, int nb) { return (long)(d.X * d.Y * d.Z / kRS) * force_link_tsplit(d, nb); }
+
+template <int INM>
+static void launch_link_action(const double2* xn, Dims d, int nb, int nsb, int tsplit, double coef, double2* out,
+                               double* part, hipStream_t st) {
+  static PerDeviceOnce attr_once;
+  if (attr_once.first()) {
+    (void)hipFuncSetAttribute((const void*)su3_force_link_action_kernel<INM>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLkLds);
+  }
+  hipLaunchKernelGGL((su3_force_link_action_kernel<INM>), dim3((unsigned)((long)nb * nsb * tsplit)),
+                     dim3(kLkThreads), kLkLds, st, xn, d, nsb, tsplit, tuning().xcd_swizzle, coef, out, 1,
+                     tuning().force_stagger, part);
+}
+
+// part: nb * force_link_action_parts(d, nb) doubles
+void launch_force_link_action(const double2* xn, Dims d, int nb, double coef, double2* out, double* part,
+                              hipStream_t st) {
+  const int nsb = d.X * d.Y * d.Z / kRS;
+  const int tsplit = force_link_tsplit(d, nb);
+  switch (force_link_inmask(d)) {
+    case 7: launch_link_action<7>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
+    case 6: launch_link_action<6>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
+    case 4: launch_link_action<4>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
+    default: launch_link_action<0>(xn, d, nb, nsb, tsplit, coef, out, part, st);
+  }
+}
+
 void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st,
                        const double2* vin) {
   if (vin == nullptr) vin = out;
   const int Vs = d.X * d.Y * d.Z;
   const int nsb = Vs / kRS;
-  // >= ~2 resident rounds of 2 x 256 workgroups
-  const int tsplit = t_chunks((long)nb * nsb, d.T, 1024, tuning().force_tsplit);
+  const int tsplit = force_link_tsplit(d, nb);
 #define L2Q_LK_CASE(M)                                                                    \
   case M:                                                                                 \
     if (kick) launch_link_variant<1, M>(xn, d, nb, nsb, tsplit, coef, vin, out, st);           \

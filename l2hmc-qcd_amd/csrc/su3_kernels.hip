@@ -839,12 +839,9 @@ __global__ __launch_bounds__(kBlock) void su3_mul_kernel(const double2* a, const
   store_link(out + f * 9L * V, V, s, r);
 }
 
-__global__ __launch_bounds__(kBlock) void su3_assemble_tah_kernel(const double* __restrict__ nrm,
-                                                                  double2* __restrict__ vn, long V,
-                                                                  long nblk, long nlinks) {
-  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
-  const long s = blk * kBlock + threadIdx.x;
-  if (s >= V) return;
+// the momentum of link (field f, site s); returns the sum of |entry|^2 over its nine entries as stored
+__device__ __forceinline__ double assemble_tah_link(const double* __restrict__ nrm, double2* __restrict__ vn,
+                                                    long V, long nlinks, long f, long s) {
   const long l = f * V + s;
   const double h = 0.70710678118654757;          // sqrt(1/2)
   const double r3 = h * nrm[0 * nlinks + l];
@@ -853,15 +850,46 @@ __global__ __launch_bounds__(kBlock) void su3_assemble_tah_kernel(const double* 
   const double r12 = h * nrm[4 * nlinks + l], i01 = h * nrm[5 * nlinks + l];
   const double i02 = h * nrm[6 * nlinks + l], i12 = h * nrm[7 * nlinks + l];
   double2* o = vn + f * 9 * V;
-  o[0 * V + s] = make_double2(0.0, r8 + r3);
-  o[1 * V + s] = make_double2(r01, i01);
-  o[2 * V + s] = make_double2(r02, i02);
-  o[3 * V + s] = make_double2(-r01, i01);
-  o[4 * V + s] = make_double2(0.0, r8 - r3);
-  o[5 * V + s] = make_double2(r12, i12);
-  o[6 * V + s] = make_double2(-r02, i02);
-  o[7 * V + s] = make_double2(-r12, i12);
-  o[8 * V + s] = make_double2(0.0, -2.0 * r8);
+  const double2 m[9] = {make_double2(0.0, r8 + r3), make_double2(r01, i01),      make_double2(r02, i02),
+                        make_double2(-r01, i01),    make_double2(0.0, r8 - r3),  make_double2(r12, i12),
+                        make_double2(-r02, i02),    make_double2(-r12, i12),     make_double2(0.0, -2.0 * r8)};
+  double acc = 0.0;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    o[e * V + s] = m[e];
+    acc = fma(m[e].x, m[e].x, acc);
+    acc = fma(m[e].y, m[e].y, acc);
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(kBlock) void su3_assemble_tah_kernel(const double* __restrict__ nrm,
+                                                                  double2* __restrict__ vn, long V,
+                                                                  long nblk, long nlinks) {
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const long s = blk * kBlock + threadIdx.x;
+  if (s >= V) return;
+  (void)assemble_tah_link(nrm, vn, V, nlinks, f, s);
+}
+
+// the same with partial[f][blk] = the block's sum of |entry|^2: the four fields of a chain are adjacent, so a
+// chain's partials are contiguous (l2q_su3_assemble_tah_norm2 sums them in a fixed order)
+__global__ __launch_bounds__(kBlock) void su3_assemble_tah_norm2_kernel(const double* __restrict__ nrm,
+                                                                        double2* __restrict__ vn, long V,
+                                                                        long nblk, long nlinks,
+                                                                        double* __restrict__ partial) {
+  __shared__ double lds[4];
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const long s = blk * kBlock + threadIdx.x;
+  const double acc = s < V ? assemble_tah_link(nrm, vn, V, nlinks, f, s) : 0.0;
+  const double r = block_sum(acc, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// out[c] = sums[c][0]: the real part of the (Re, Im) pairs l2q_su3_plaq_reduce writes
+__global__ void su3_plaq_re_kernel(const double* __restrict__ sums, double* __restrict__ out, int nb) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < nb) out[c] = sums[2 * c];
 }
 
 // per-chain sum over all 36 V complex entries of |p|^2; the -8 per link and the 1/2 are
@@ -1015,6 +1043,15 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
     force_kernel_name<false>(dd, buf, buf_bytes);
   } else if (!strcmp(entry, "l2q_su3_force_kick")) {
     force_kernel_name<true>(dd, buf, buf_bytes);
+  } else if (!strcmp(entry, "l2q_su3_force_action")) {
+    if (pick_force(dd, false) == ForceKernel::Link) {
+      snprintf(buf, buf_bytes, "su3_force_link_action_kernel<%d>", force_link_inmask(dd));
+    } else {                          // the ordinary force, then the plaquette reduction
+      char force[128], plaq[128];
+      force_kernel_name<false>(dd, force, sizeof(force));
+      (void)l2q_kernel_name("l2q_su3_plaq_reduce", T, X, Y, Z, plaq, sizeof(plaq));
+      snprintf(buf, buf_bytes, "%s + %s", force, plaq);
+    }
   } else if (!strcmp(entry, "l2q_su3_clover_reduce")) {
     snprintf(buf, buf_bytes, "%s", clover_slice_applicable(dd) ? "su3_clover_slice_kernel" : "su3_clover_kernel");
   } else if (!strcmp(entry, "l2q_su3_flow_stage")) {
@@ -1126,6 +1163,38 @@ int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, i
   const Dims d = make_dims(T, X, Y, Z);
   launch_force<false>((const double2*)xn, d, nb, beta / 3.0, (double2*)fn, (hipStream_t)stream);
   return check_launch("l2q_su3_force");
+}
+
+size_t l2q_su3_force_action_ws_bytes(int nb, int T, int X, int Y, int Z) {
+  if (!su3_dims_ok(nb, T, X, Y, Z)) return 0;
+  // the link kernel's one partial per workgroup (at most V / 64 per chain), or, on the other route, the
+  // plaquette reduction's (Re, Im) result in the first 256-byte multiple and its own workspace behind it
+  return (((size_t)nb * 2 * sizeof(double) + 255) & ~(size_t)255) + l2q_reduce_ws_bytes(nb, 36L * T * X * Y * Z);
+}
+
+int l2q_su3_force_action(const void* xn, double beta, void* fn, double* plaq, int nb, int T, int X, int Y, int Z,
+                         void* ws, size_t ws_bytes, void* stream) {
+  L2Q_REQUIRE(xn && fn && plaq && ws, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(xn != fn, L2Q_EINVAL, "force output must not alias the gauge field");
+  L2Q_REQUIRE(ws_bytes >= l2q_su3_force_action_ws_bytes(nb, T, X, Y, Z), L2Q_ESHAPE, "workspace too small");
+  const Dims d = make_dims(T, X, Y, Z);
+  hipStream_t st = (hipStream_t)stream;
+  if (pick_force(d, false) == ForceKernel::Link) {
+    // sum over links of Re tr(U A) counts every plaquette once per link of it
+    const long parts = force_link_action_parts(d, nb);
+    launch_force_link_action((const double2*)xn, d, nb, beta / 3.0, (double2*)fn, (double*)ws, st);
+    launch_finalize((const double*)ws, plaq, nb, parts, 1, 0.25, 0.0, st);
+    return check_launch("l2q_su3_force_action");
+  }
+  // lattices (and force_tile settings) the link kernel does not serve: the two passes
+  launch_force<false>((const double2*)xn, d, nb, beta / 3.0, (double2*)fn, st);
+  const size_t head = ((size_t)nb * 2 * sizeof(double) + 255) & ~(size_t)255;
+  const int rc = l2q_su3_plaq_reduce(xn, nb, T, X, Y, Z, (double*)ws, (char*)ws + head, ws_bytes - head, stream);
+  if (rc != L2Q_OK) return rc;
+  hipLaunchKernelGGL(su3_plaq_re_kernel, dim3((unsigned)cdiv(nb, kBlock)), dim3(kBlock), 0, st, (const double*)ws,
+                     plaq, nb);
+  return check_launch("l2q_su3_force_action");
 }
 
 int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int nb, int T, int X,
@@ -1290,6 +1359,19 @@ int l2q_su3_assemble_tah(const double* normals, void* vn, long nfields, long V, 
   hipLaunchKernelGGL(su3_assemble_tah_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, normals, (double2*)vn, V, nblk, nfields * V);
   return check_launch("l2q_su3_assemble_tah");
+}
+
+int l2q_su3_assemble_tah_norm2(const double* normals, void* vn, int nb, long V, double* norm2, void* ws,
+                               size_t ws_bytes, void* stream) {
+  L2Q_REQUIRE(normals && vn && norm2 && ws, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_field_ok(nb, V), L2Q_EINVAL, "bad size");
+  const long nblk = cdiv(V, kBlock);
+  L2Q_REQUIRE(ws_bytes >= (size_t)nb * 4 * nblk * sizeof(double), L2Q_ESHAPE, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(su3_assemble_tah_norm2_kernel, dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock), 0, st, normals,
+                     (double2*)vn, V, nblk, nb * 4L * V, (double*)ws);
+  launch_finalize((const double*)ws, norm2, nb, 4 * nblk, 1, 1.0, 0.0, st);
+  return check_launch("l2q_su3_assemble_tah_norm2");
 }
 
 int l2q_su3_check_su(const void* xn, int nb, long V, double* out, void* ws, size_t ws_bytes,

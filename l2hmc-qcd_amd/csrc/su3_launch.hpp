@@ -31,6 +31,10 @@ void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef
                        const double2* vin = nullptr);
 void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const double2* gf, double2* gx,
                            hipStream_t st);
+// the plain force that also stores one partial sum of Re tr(U A) per workgroup: part[nb][force_link_action_parts]
+long force_link_action_parts(const Dims& d, int nb);
+void launch_force_link_action(const double2* xn, Dims d, int nb, double coef, double2* out, double* part,
+                              hipStream_t st);
 // su3_force_plaq.hip: plaquettes shared between their four links (plain force only)
 bool force_plaq_applicable(const Dims& d);
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);

@@ -140,6 +140,24 @@ def su3_force_n(xn: torch.Tensor, beta: float, lat: Sequence[int]) -> torch.Tens
     return f
 
 
+# The Hamiltonian's terms from the kernels that already hold them (l2q_su3_force_action, l2q_su3_assemble_tah_norm2,
+# the sum |v_out|^2 request of the sliced heads kernel) instead of separate passes over the fields: [True] = the
+# sampler asks for them where it can (dynamics.py: `Dynamics._kernel_energies`), [False] = the separate passes.
+USE_KERNEL_ENERGIES = [True]
+
+
+def su3_force_action_n(xn: torch.Tensor, beta: float, lat: Sequence[int]):
+    """(F, plaq): su3_force_n and, from the same launch, plaq [nb] = sum Re tr P = su3_plaq_sums_n(xn)[:, 0] to
+    rounding (include/l2q.h: l2q_su3_force_action)."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    f = torch.empty_like(xn)
+    plaq = torch.empty(nb, dtype=torch.float64, device=xn.device)
+    ws = N.workspace(int(N.load().l2q_su3_force_action_ws_bytes(nb, T, X, Y, Z)), xn.device)
+    N.call('l2q_su3_force_action', xn, float(beta), f, plaq, nb, T, X, Y, Z, ws, ws.numel())
+    return f, plaq
+
+
 def su3_force_kick_n(xn: torch.Tensor, beta: float, coef: float, vn: torch.Tensor,
                      lat: Sequence[int], v_src: Optional[torch.Tensor] = None) -> torch.Tensor:
     """vn += coef * F(xn) in place; with v_src: vn = v_src + coef * F(xn) (vn only written)."""
@@ -242,6 +260,17 @@ def su3_assemble_tah_n(normals: torch.Tensor) -> torch.Tensor:
     out = torch.empty((*lead, 9, V), dtype=C128, device=normals.device)
     N.call('l2q_su3_assemble_tah', normals.contiguous(), out, nf, V)
     return out
+
+
+def su3_assemble_tah_norm2_n(normals: torch.Tensor):
+    """normals [8, nb, 4, V] float64 -> (vn [nb, 4, 9, V], norm2 [nb] = sum |vn|^2 per chain, from the same launch)."""
+    _, nb, four, V = normals.shape
+    assert four == 4
+    out = torch.empty((nb, 4, 9, V), dtype=C128, device=normals.device)
+    n2 = torch.empty(nb, dtype=torch.float64, device=normals.device)
+    ws = _ws(nb, 4 * V, normals.device)
+    N.call('l2q_su3_assemble_tah_norm2', normals.contiguous(), out, nb, V, n2, ws, ws.numel())
+    return out, n2
 
 
 def su3_check_su_n(xn: torch.Tensor) -> torch.Tensor:
@@ -837,19 +866,22 @@ def heads_sliced_zflag(reset: bool = True) -> int:
 
 
 def _sliced_call(z, heads, scales, v, force, eps1, forward1, pair, flip, eps2, forward2, v_src=None,
-                 mid=False):
+                 mid=False, norm2=False):
+    """out[0] = logdet; mid (pair): out[1] = the first update's logdet, out[2] = sum |v_mid|^2;
+    norm2 (single update): out[2] = sum |v_out|^2"""
     m, k = z.shape
     _, bs, cs = heads['s']
     _, bt, _ = heads['t']
     wq, bq, cq = heads['q']
     n = wq.shape[0]
-    out = torch.empty((3 if mid else 1, m), dtype=torch.float64, device=z.device)
+    assert not (norm2 and (pair or mid))
+    out = torch.empty((3 if mid or norm2 else 1, m), dtype=torch.float64, device=z.device)
     nbytes = int(N.load().l2q_vnet_heads_sliced_ws_bytes(m, n))
     ws = N.workspace(nbytes, z.device)
     N.call('l2q_vnet_heads_vupdate_sliced_f64', z, m, k, n, heads['sliced'], bs, cs, float(scales[0]), bt,
            float(scales[1]), bq, cq, float(scales[2]), v_src, v, force, int(v.is_complex()), float(eps1),
            int(forward1), int(pair), int(flip), float(eps2), int(forward2), out[0],
-           out[1] if mid else None, out[2] if mid else None, ws, ws.numel())
+           out[1] if mid else None, out[2] if mid or norm2 else None, ws, ws.numel())
     return out
 
 
@@ -862,8 +894,10 @@ def _use_sliced(z, heads) -> bool:
 
 def vnet_heads_vupdate_(z: torch.Tensor, heads: dict, scales, v: torch.Tensor,
                         force: torch.Tensor, eps: float, forward: bool,
-                        v_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        v_src: Optional[torch.Tensor] = None, norm2: Optional[list] = None) -> torch.Tensor:
     """Fused (s, t, q) heads + generalised momentum update, v in place; returns logdet [nb].
+    norm2: a list that receives sum |v_out|^2 [nb] when the kernel that runs can emit it (the int8-sliced one);
+    left empty otherwise.
     heads: {'s': (W, b, colscale|None), 't': (W, b, None), 'q': (W, b, colscale|None)};
     scales = (nw.s, nw.t, nw.q) used where no per-column scale is given.
     v_src: read the momentum from there instead (v is then only written)."""
@@ -875,7 +909,11 @@ def vnet_heads_vupdate_(z: torch.Tensor, heads: dict, scales, v: torch.Tensor,
     if _use_sliced(z, heads):
         if v_src is not None:
             assert v_src.shape == v.shape and v_src.dtype == v.dtype and v_src.is_contiguous()
-        return _sliced_call(z, heads, scales, v, force, eps, forward, False, False, 0.0, False, v_src)[0]
+        out = _sliced_call(z, heads, scales, v, force, eps, forward, False, False, 0.0, False, v_src,
+                           norm2=norm2 is not None)
+        if norm2 is not None:
+            norm2.append(out[2])
+        return out[0]
     logdet = torch.empty(m, dtype=torch.float64, device=z.device)
     nbytes = int(N.load().l2q_vnet_heads_ws_bytes(m, n))
     ws = N.workspace(nbytes, z.device)

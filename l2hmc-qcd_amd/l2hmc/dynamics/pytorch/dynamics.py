@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import logging
 import os
+import weakref
 from dataclasses import dataclass
 from math import pi as PI
 from pathlib import Path
@@ -231,6 +232,7 @@ class Dynamics(nn.Module):
         self.fuse_half_heads = True
         self.merge_hmc_kicks = True  # plain HMC, non-verbose: adjacent half-kicks share one force pass
         self._inject: Optional[dict] = None
+        self._mom_norm2 = None       # (weak reference to the last momenta drawn, their sum |v|^2 per chain)
         self._eps_cache: dict = {}
         self._masks_native: Optional[list] = None
         self._perm: dict = {}
@@ -521,8 +523,26 @@ class Dynamics(nn.Module):
         s = ops.u1_plaq_sums(xn, self.latvolume)
         return _beta(beta) * (self.volume - s[:, 0])
 
+    def _potential_from_plaq(self, plaq: Tensor, beta) -> Tensor:
+        """`_potential_n` (c1 = 0) from sum Re tr P as a force kernel returned it (ops.su3_force_action_n)"""
+        return (-_beta(beta) / 3.0) * plaq
+
+    def _kinetic_from_norm2(self, n2: Tensor) -> Tensor:
+        """group/su3/pytorch/group.py:125-126 from sum |v|^2, as l2q_su3_kinetic_reduce evaluates it"""
+        return 0.5 * (n2 - 8.0 * 4.0 * self.volume)
+
     def _kinetic_n(self, vn: Tensor) -> Tensor:
+        kept, self._mom_norm2 = self._mom_norm2, None
+        if kept is not None and kept[0]() is vn:       # the momenta `_momentum_n` just made, untouched since
+            return self._kinetic_from_norm2(kept[1])
         return ops.su3_kinetic_n(vn) if self.group == 'SU3' else ops.u1_kinetic(vn)
+
+    def _kernel_energies(self, xn: Tensor) -> bool:
+        """The sampler takes the Hamiltonian's terms from the kernels that hold them (ops.USE_KERNEL_ENERGIES):
+        SU(3) on the device with the plain Wilson action, outside training.  (Injected momenta: `_momentum_n`
+        keeps no sum for them, their kinetic energy is the separate pass.)"""
+        return bool(ops.USE_KERNEL_ENERGIES[0] and self.group == 'SU3' and xn.is_cuda
+                    and self.potential_c1 == 0.0 and not self.training)
 
     def _hamiltonian_n(self, xn: Tensor, vn: Tensor, beta) -> Tensor:
         return self._kinetic_n(vn) + self._potential_n(xn, beta)
@@ -540,7 +560,13 @@ class Dynamics(nn.Module):
                                    for _ in range(8)]).to(DEVICE)
             else:
                 nrm = torch.randn((8, *shape), dtype=torch.float64, device=DEVICE)
-            return ops.su3_assemble_tah_n(nrm.reshape(8, nb, 4, self.volume))
+            nrm = nrm.reshape(8, nb, 4, self.volume)
+            if ops.USE_KERNEL_ENERGIES[0] and inj is None and not self.training and nrm.is_cuda:
+                # sum |v|^2 while the matrices are in registers: the opening kinetic energy (`_kinetic_n`)
+                vn, n2 = ops.su3_assemble_tah_norm2_n(nrm)
+                self._mom_norm2 = (weakref.ref(vn), n2)
+                return vn
+            return ops.su3_assemble_tah_n(nrm)
         shape = (nb, 2, *self.latvolume)
         if inj is not None:
             v = torch.as_tensor(inj).to(DEVICE)
@@ -622,7 +648,13 @@ class Dynamics(nn.Module):
         if reuse and ts.valid:
             fn = ts.F
         else:
-            fn = self._force_n(xn, beta)
+            if reuse and ts.want_pe:
+                # the potential of this x is consumed: it comes out of the force launch
+                fn, ts.plaq = ops.su3_force_action_n(xn, _beta(beta), self.latvolume)
+            else:
+                fn = self._force_n(xn, beta)
+                if reuse:
+                    ts.plaq = None
             if reuse:                  # what was kept belongs to another x (xv_pre is of the new x already)
                 ts.valid, ts.F = True, fn
                 ts.xv = ts.fv = None
@@ -693,9 +725,10 @@ class Dynamics(nn.Module):
 
     def _update_v_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool,
                     ts: Optional[SamplerStepper] = None, acc: Optional[Tensor] = None,
-                    v_src: Optional[Tensor] = None) -> Tensor:
+                    v_src: Optional[Tensor] = None, norm2: Optional[list] = None) -> Tensor:
         """v-update in place (dynamics.py:1266-1297); returns logdet [nb] (the fused U(1) kernel
-        adds it into `acc` when given).  `v_src`: the momentum is read from there and only
+        adds it into `acc` when given).  `norm2`: a list that receives sum |v'|^2 [nb] of the updated momentum
+        when the kernel that runs emits it (ops.vnet_heads_vupdate_), and stays empty otherwise.  `v_src`: the momentum is read from there and only
         written to vn (the heads kernel does that itself; the other paths copy first)."""
         eps = self._eps('v', step)
         nb = xn.shape[0]
@@ -720,7 +753,7 @@ class Dynamics(nn.Module):
             # heads + momentum update in one kernel: s, t, q never reach HBM
             return ops.vnet_heads_vupdate_(z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q),
                                            vn.reshape(nb, -1), fn.reshape(nb, -1), eps, forward,
-                                           None if v_src is None else v_src.reshape(nb, -1))
+                                           None if v_src is None else v_src.reshape(nb, -1), norm2=norm2)
         if v_src is not None:
             vn.copy_(v_src)
         s, t, q = self._vnet_n(step, xn, fn)
@@ -745,7 +778,7 @@ class Dynamics(nn.Module):
             return ops.vnet_heads_vupdate_pair_(*args)
         ld, ts.ld1, vn2 = ops.vnet_heads_vupdate_pair_mid_(*args)
         # group/su3/pytorch/group.py:125-126 as l2q_su3_kinetic_reduce evaluates it
-        ts.ke = 0.5 * (vn2 - 8.0 * 4.0 * self.volume)
+        ts.ke = self._kinetic_from_norm2(vn2)
         return ld - ts.ld1
 
     def _can_pair_mid(self) -> bool:
@@ -826,6 +859,8 @@ class Dynamics(nn.Module):
         if ts is not None:                   # taken: the pending update and the sources are this step's to use
             prev, x_src, v_src = ts.pending, ts.x_src, ts.v_src
             ts.pending = ts.x_src = ts.v_src = None
+            # per-step metrics: the potential of every x a step produced is consumed (not the trajectory's input's)
+            ts.want_pe = bool(ts.energies and ts.late and prev is not None)
         late = bool(prev is not None and ts.late)
         xr = xn if x_src is None else x_src              # where this step reads x before its x-update
         if v_src is not None and prev is not None:
@@ -880,7 +915,13 @@ class Dynamics(nn.Module):
             return None
         ts.pending = None
         st0, f0, flip = prev
-        ld = self._update_v_n(st0, xn, vn, beta, f0, ts)
+        # the trajectory's last update: the force launch leaves the potential of the final x in ts.plaq and
+        # the heads kernel the final momentum's sum |v|^2 (the sign flip does not change it)
+        n2 = [] if ts.energies else None
+        ts.want_pe = ts.energies
+        ld = self._update_v_n(st0, xn, vn, beta, f0, ts, norm2=n2)
+        ts.want_pe = False
+        ts.ke_out = self._kinetic_from_norm2(n2[0]) if n2 else None
         if flip:
             self._flip_v_n(vn)
         return ld
@@ -1570,7 +1611,7 @@ class GraphedTransition:
         flags = (d.fuse_heads, d.fuse_x_updates, d.reuse_v_inputs, d.pair_v_updates,
                  d.fuse_u1_steps, d.fuse_half_heads, d.merge_hmc_kicks, d.sliced_heads,
                  ops.USE_SLICED_HEADS[0], d.sliced_input, ops.USE_SLICED_INPUT[0], ops.USE_DIGIT_INPUTS[0],
-                 d.pair_v_updates_verbose,
+                 ops.USE_KERNEL_ENERGIES[0], d.pair_v_updates_verbose,
                  getattr(d, 'fuse_x_vec8', None), d.net_precision, d.config.verbose, d.training)
         return (ops.PARAM_GENERATION[0], params, masks, flags)
 

@@ -17,6 +17,8 @@ import torch
 
 Tensor = torch.Tensor
 
+_WITH_FORCE = object()        # a potential energy that the next force launch delivers (SamplerStepper.energies)
+
 
 class SamplerStepper:
     """In-place steps of the sampler and everything that is local to ONE of its trajectories:
@@ -28,10 +30,15 @@ class SamplerStepper:
     late     ... under verbose=True: the mid-point pair kernel leaves the deferred update's logdet and the
              kinetic energy right after it in `ld1` / `ke`, so a step's metrics are complete one call late
     x_src, v_src   SU(3): the first step READS the trajectory's input from there and writes x / v, so the
-             input is never copied"""
+             input is never copied
+    energies ... with `defer`, where `Dynamics._kernel_energies` allows: the Hamiltonian's terms come out of the
+             kernels that hold them.  `plaq` (beside `F`): sum Re tr P of the x the force was taken at, from the
+             force launches whose potential is consumed (`want_pe`: the closing one; `late`: every one but the first);
+             `ke_out`: the kinetic energy of the momentum the closing update wrote (None: that kernel does not
+             emit it)"""
     __slots__ = ('dyn', 'beta', 'reuse', 'defer', 'late', 'lazy', 'x_src', 'v_src',
                  'valid', 'F', 'xv_pre', 'xv', 'fv', 'z',
-                 'pending', 'ld1', 'ke')
+                 'pending', 'ld1', 'ke', 'energies', 'want_pe', 'plaq', 'ke_out')
 
     def __init__(self, dyn, beta, merged: bool):
         verbose = dyn.config.verbose
@@ -48,8 +55,11 @@ class SamplerStepper:
         self.z = {}
         self.pending = self.ld1 = self.ke = None
         self.lazy = bool(merged and su3 and dyn.config.nleapfrog > 0)
+        self.energies = self.want_pe = False
+        self.plaq = self.ke_out = None
 
     def start(self, xn: Tensor, vn: Tensor):
+        self.energies = bool(self.defer and self.lazy and self.dyn._kernel_energies(xn))
         if not self.lazy:
             return xn.clone(), vn.clone()
         self.x_src, self.v_src = xn, vn
@@ -67,6 +77,16 @@ class SamplerStepper:
     def finish(self, x: Tensor, v: Tensor):
         return self.dyn._flush_pending_n(self, x, v, self.beta)
 
+    def potential(self, x: Tensor) -> Tensor:
+        """of the x the last force was taken at (`energies`); the separate pass where no launch emitted it"""
+        if self.plaq is None:
+            return self.dyn._potential_n(x, self.beta)
+        return self.dyn._potential_from_plaq(self.plaq, self.beta)
+
+    def kinetic_out(self, v: Tensor) -> Tensor:
+        """of the momentum `finish` left (`energies`)"""
+        return self.dyn._kinetic_n(v) if self.ke_out is None else self.ke_out
+
 
 def run_trajectory(dyn, stepper, xn: Tensor, vn: Tensor, beta, directions: tuple):
     """`directions` = (True, False): the merged forward + backward trajectory (dynamics.py:956-1029);
@@ -75,6 +95,9 @@ def run_trajectory(dyn, stepper, xn: Tensor, vn: Tensor, beta, directions: tuple
     merged = len(directions) == 2
     verbose, nlf = dyn.config.verbose, dyn.config.nleapfrog
     x, v = stepper.start(xn, vn)
+    # SamplerStepper.energies: the potential of a step's x comes out of the force launch on it -- the next call's
+    # (or `finish`'s) -- and the closing kinetic energy out of `finish`; the opening potential stays a pass
+    energies = getattr(stepper, 'energies', False)
     # (every sum below is out of place: the history holds the earlier tensors)
     sumlogdet = dyn._zeros_nb(xn.shape[0])
     sldf = sldb = torch.zeros_like(sumlogdet) if merged else None
@@ -110,6 +133,8 @@ def run_trajectory(dyn, stepper, xn: Tensor, vn: Tensor, beta, directions: tuple
             if late_pe is not None:                    # the previous step's closing update ran now
                 sumlogdet = sumlogdet + stepper.ld1
                 add_sld(late_fwd, stepper.ld1)
+                if late_pe is _WITH_FORCE:             # ... on the force of that step's x (x_prev, no longer held)
+                    late_pe = dyn._potential_from_plaq(stepper.plaq, beta)
                 h = record(stepper.ke + late_pe, late_idx, late_fwd)
             sumlogdet = sumlogdet + logdet
             if not verbose:
@@ -118,7 +143,8 @@ def run_trajectory(dyn, stepper, xn: Tensor, vn: Tensor, beta, directions: tuple
                 add_sld(forward, logdet)
             idx = step if (forward or not merged) else nlf - step - 1
             if stepper.late:
-                late_pe, late_idx, late_fwd = dyn._potential_n(x, beta), idx, forward
+                late_pe = _WITH_FORCE if energies else dyn._potential_n(x, beta)
+                late_idx, late_fwd = idx, forward
             else:
                 h = record(dyn._hamiltonian_n(x, v, beta), idx, forward)
     last = stepper.finish(x, v)
@@ -127,9 +153,12 @@ def run_trajectory(dyn, stepper, xn: Tensor, vn: Tensor, beta, directions: tuple
     if late_pe is not None:
         if last is not None:
             add_sld(late_fwd, last)
-        h = record(dyn._kinetic_n(v) + late_pe, late_idx, late_fwd)
+        if late_pe is _WITH_FORCE:
+            h = record(stepper.kinetic_out(v) + stepper.potential(x), late_idx, late_fwd)
+        else:
+            h = record(dyn._kinetic_n(v) + late_pe, late_idx, late_fwd)
     if not verbose or nlf == 0:                        # (verbose: the last record's energy is H of the final state)
-        h = dyn._hamiltonian_n(x, v, beta)
+        h = stepper.kinetic_out(v) + stepper.potential(x) if energies else dyn._hamiltonian_n(x, v, beta)
     h_pair = (h_init, h) if merged else (h, h_init)        # single direction: the reference's swapped call
     acc = dyn._accept_prob_n(*h_pair, sumlogdet)
     history.update({'acc': acc, 'sumlogdet': sumlogdet})

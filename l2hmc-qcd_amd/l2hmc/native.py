@@ -43,6 +43,8 @@ SIGNATURES = {
     'l2q_diff_norm2_reduce': (I, [P, P, I, L, P, P, Z, P]),
     'l2q_su3_force': (I, [P, D, P, I, I, I, I, I, P]),
     'l2q_su3_force_kick': (I, [P, D, D, P, I, I, I, I, I, P]),
+    'l2q_su3_force_action_ws_bytes': (Z, [I, I, I, I, I]),
+    'l2q_su3_force_action': (I, [P, D, P, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_force_kick_to': (I, [P, D, D, P, P, I, I, I, I, I, P]),
     'l2q_su3_expm_mul': (I, [P, P, D, P, I, P, I, L, P]),
     'l2q_su3_expm_mul2': (I, [P, P, D, P, I, P, I, L, P]),
@@ -56,6 +58,7 @@ SIGNATURES = {
     'l2q_su3_mul': (I, [P, P, I, I, P, L, L, P]),
     'l2q_su3_kinetic_reduce': (I, [P, I, L, P, P, Z, P]),
     'l2q_su3_assemble_tah': (I, [P, P, L, L, P]),
+    'l2q_su3_assemble_tah_norm2': (I, [P, P, I, L, P, P, Z, P]),
     'l2q_su3_check_su': (I, [P, I, L, P, P, Z, P]),
     'l2q_su3_clover_reduce': (I, [P, I, I, I, I, I, P, P, Z, P]),
     'l2q_su3_flow_stage': (I, [P, P, D, D, P, P, I, I, I, I, I, P]),
