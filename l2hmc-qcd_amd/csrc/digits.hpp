@@ -1,7 +1,8 @@
 // digits.hpp -- the activation digit image of the int8-sliced input layer (gemm_digits.hip) and the code its
 // producers (su3_kernels.hip, gemm_digits.hip) write it with.
 //
-// Code: exactly gemm_sliced.hip's (gs_slice16_impl): a value v with |v| < 2^e is X = rint(v 2^(54 - e)), recoded in
+// Code: the one of the whole sliced input layer (gd_digits below is its scalar definition, gs_slice16_impl of
+// gemm_sliced.hip the staged four-wide form): a value v with |v| < 2^e is X = rint(v 2^(54 - e)), recoded in
 // balanced base 256, X = sum_s d_s 256^(6-s), d_s in [-128, 127] -- the same magic-number sums, hence the same bytes
 // as the on-the-fly slicer of gemm_sliced_kernel.
 //
@@ -16,27 +17,24 @@
 
 namespace l2q {
 
-constexpr int GD_NS = 7;                        // digits per value
-constexpr int GD_BITS = 54;                     // fixed-point bits below the operand's exponent
-constexpr int GD_SLAB = GD_NS * 64;             // bytes of one row's 64-k slab
+constexpr int GS_NS = 7;                        // int8 digits per value
+constexpr int GS_BITS = 54;                     // fixed-point bits below the operand's exponent
+constexpr double GS_MAGIC24 = 113336795588871485128704.0;   // 1.5 * 2^76: a sum with it has ulp 2^24
+constexpr double GS_MAGIC = 6755399441055744.0;             // 1.5 * 2^52: ulp 1
+constexpr int GD_SLAB = GS_NS * 64;             // bytes of one row's 64-k slab
 
-// shared with gemm_sliced.hip (defined there): k per workgroup, the "operand out of range" flag of the device
-// (raised by whoever slices, read and cleared by the reduce kernel) and the reduce kernel's launch
-long gs_klen(int M, int N, long K, long K2);
+// the "operand out of range" flag of the device (gemm_sliced.hip): raised by whoever slices, read and cleared by the
+// layer's reduce kernel
 int* gs_flag();
-void gs_launch_reduce(const double* part, int groups, long MN, int N, const double* bias, const double* bias2,
-                      const double* coeff, double scale, int act, int* flag, double* C, hipStream_t st);
 
 #ifdef __HIPCC__
 // digits of one value: lo = digits 6, 5, 4 in bytes 0, 1, 2 (byte 3: not a digit), hi = digits 3, 2, 1, 0 in bytes
 // 0..3; returns true for |x| >= lim or a NaN.  sc = 2^(54 - e), lim = 2^e.
 __device__ __forceinline__ bool gd_digits(double x, double sc, double lim, unsigned& lo, unsigned& hi) {
-  constexpr double M24 = 113336795588871485128704.0;          // 1.5 * 2^76
-  constexpr double M0 = 6755399441055744.0;                   // 1.5 * 2^52
-  const double t1 = fma(x, sc, M24);                          // low mantissa dword: H = rint(x sc 2^-24)
-  double r = M24 - t1;                                        // -H 2^24 exactly
+  const double t1 = fma(x, sc, GS_MAGIC24);                   // low mantissa dword: H = rint(x sc 2^-24)
+  double r = GS_MAGIC24 - t1;                                 // -H 2^24 exactly
   r = fma(x, sc, r);                                          // x sc - H 2^24, exact, |r| <= 2^23
-  const double t2 = r + M0;                                   // low mantissa dword: L = rint(r)
+  const double t2 = r + GS_MAGIC;                             // low mantissa dword: L = rint(r)
   const int Lb = (int)(unsigned)__double_as_longlong(t2) + 0x00808080;   // bit 24: the carry into H
   lo = (unsigned)Lb ^ 0x00808080u;
   hi = ((unsigned)__double_as_longlong(t1) + (unsigned)(Lb >> 24) + 0x80808080u) ^ 0x80808080u;

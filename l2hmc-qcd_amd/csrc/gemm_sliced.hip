@@ -32,8 +32,10 @@
 // ahead, asm loads with explicit vmcnt), sliced and written to LDS by the helpers; two activation + three
 // weight stages of 28 KB, one barrier per slab.  A matrix wavefront issues 28 ds_read_b128 (asm, explicit
 // lgkmcnt) and 112 MFMAs per slab, the last 12 of them after the next barrier (they cover the barrier and
-// the first LDS reads).  A workgroup owns (tile, k-range group); partial sums [group][M][N] are added in a
-// fixed order by the reduce kernel, which applies bias / activation / ScaledTanh scale.
+// the first LDS reads): that loop, the argument block and the launcher are sliced_core.hpp's, shared with the
+// kernel that takes the activations as digit images (gemm_digits.hip).  A workgroup owns (tile, k-range group);
+// partial sums [group][M][N] are added in a fixed order by the reduce kernel, which applies bias / activation /
+// ScaledTanh scale.
 //
 // Measured (cfg-4: M = N = 256, K = 2 x 131 072; tools/time_gemm_sliced.py, -DL2Q_GS_EXP=64 prints the shader
 // clock and the barrier waits): 0.486 ms against 0.63 ms for the fp64 MFMA layer on the same box = 71
@@ -43,23 +45,17 @@
 // ~260 VALU instructions run at ~10 clocks each beside a busy matrix pipe:
 // tools/microbench/mfma_valu_overlap.hip, "convert"), the loads and LDS-DMA ~550 more, whoever issues them.
 #include "heads_common.hpp"
+#include "sliced_core.hpp"
 
 namespace l2q {
 
-typedef int gs_v4i __attribute__((ext_vector_type(4)));
-typedef unsigned gs_v4u __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* gs_lds_ptr_t;
-
+// timing experiments (tools/ab_build.sh ... -DL2Q_GS_EXP=bits; wrong results): 1 the helpers store the raw
+// loaded bits instead of digits (no slicing arithmetic), 2 one MFMA per digit pair instead of four,
+// 4 no weight LDS-DMA after the prologue, 8 no activation loads after the prologue, 64 print the shader
+// clock measured over the kernel
 #ifndef L2Q_GS_EXP
 #define L2Q_GS_EXP 0
 #endif
-constexpr int GS_NS = 7;                       // int8 digits per value
-constexpr int GS_BITS = 54;                    // fixed-point bits below the operand's exponent
-constexpr int GS_FRAG = 1024;                  // one MFMA operand fragment: 64 lanes x 16 bytes
-constexpr int GS_T = 64;                       // output tile (rows = columns)
-constexpr int GS_OPER = 4 * GS_NS * GS_FRAG;   // one operand of a stage: 4 row tiles x 7 digits = 28 KB
-constexpr int GS_RANGE = 16384;                // k per int32 accumulation
-constexpr double GS_MAGIC = 6755399441055744.0;   // 1.5 * 2^52
 
 // 16 values -> 7 digit planes of 16 bytes (plane s: byte j = digit s of x[j]); returns nonzero when a
 // value is outside (-lim, lim) or not a number.  X = rint(x sc) (|X| <= 2^54) = H 2^24 + L in two exact
@@ -69,13 +65,12 @@ constexpr double GS_MAGIC = 6755399441055744.0;   // 1.5 * 2^52
 // digit + 128 -- done on L (3 bytes, its carry goes into H) and on H (4 bytes); XOR 0x80 makes them int8.
 // ~10 instructions per value.  hook(j) runs after value j is converted (the GEMM's helpers issue their
 // memory instructions there, spread through the arithmetic; called for j = 3, 7, 11, 15); get(j) supplies
-// value j when its turn comes.
+// value j when its turn comes.  (The staged four-wide form of gd_digits, digits.hpp: the same sums, the same bytes.)
 struct GsNoHook { __device__ __forceinline__ void operator()(int) const {} };
 template <bool PIN, class Get, class Hook>
 __device__ __forceinline__ int gs_slice16_impl(Get get, double sc, double lim, gs_v4u (&out)[GS_NS], Hook hook) {
   unsigned lo[16], hi[16];               // lo: digits 6, 5, 4 in bytes 0, 1, 2; hi: digits 3, 2, 1, 0 in bytes 0..3
   unsigned long long bad = 0;            // wavefront mask (scalar registers): |x| >= lim or NaN
-  constexpr double M24 = 113336795588871485128704.0;          // 1.5 * 2^76
   // four values at a time, stage by stage: four independent dependency chains side by side (written value by
   // value the compiler emits each chain serially and every instruction waits for the one before it)
 #pragma unroll
@@ -98,9 +93,9 @@ __device__ __forceinline__ int gs_slice16_impl(Get get, double sc, double lim, g
     continue;
 #endif
 #pragma unroll
-    for (int i = 0; i < 4; ++i) t1[i] = fma(xj[i], sc, M24);
+    for (int i = 0; i < 4; ++i) t1[i] = fma(xj[i], sc, GS_MAGIC24);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = M24 - t1[i];             // -H 2^24 exactly
+    for (int i = 0; i < 4; ++i) r[i] = GS_MAGIC24 - t1[i];            // -H 2^24 exactly
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = fma(xj[i], sc, r[i]);
 #pragma unroll
@@ -210,42 +205,6 @@ __global__ __launch_bounds__(256) void gs_build_kernel(const double* __restrict_
   if (ks == 0 && g == 0) wsc[n] = ldexp(1.0, e - 2 * GS_BITS + 48);   // 256^6 2^-(54 - e_w) 2^-54; x 2^e_a at run time
 }
 
-// timing experiments (tools/ab_build.sh ... -DL2Q_GS_EXP=bits; wrong results): 1 the helpers store the raw
-// loaded bits instead of digits (no slicing arithmetic), 2 one MFMA per digit pair instead of four,
-// 4 no weight LDS-DMA after the prologue, 8 no activation loads after the prologue, 64 print the shader
-// clock measured over the kernel
-
-struct GsArgs {
-  const double* A[2];       // activations [M][K]
-  const char* img[2];       // digit images of the weights
-  const double* wsc[2];     // [N] column scales
-  long K[2];
-  double sc[2], lim[2], post[2];   // 2^(50 - e_a), 2^e_a, 2^e_a
-  int groups0;              // k-range groups of operand 0 (the rest belong to operand 1)
-  long klen;                // k per group (a multiple of 64)
-  int M, N;
-  double* part;             // [groups][M][N]
-  int* flag;
-};
-
-// compile-time loop and LDS read / wait with literal operands (asm wants immediates)
-template <int I> using gs_c = std::integral_constant<int, I>;
-template <int I, int N, class F>
-__device__ __forceinline__ void gs_for(F f) {
-  if constexpr (I < N) {
-    f(gs_c<I>());
-    gs_for<I + 1, N>(f);
-  }
-}
-template <int OFF>
-__device__ __forceinline__ void gs_dsr(gs_v4i& d, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-template <int N>
-__device__ __forceinline__ void gs_wait(gs_v4i& a0, gs_v4i& a1, gs_v4i& b0, gs_v4i& b1) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1) : "n"(N));
-}
-
 // (matrix wavefronts: at B(p) the pieces of slab p, issued in period p - 2, must have landed; the seven of
 // period p - 1 may still be in flight)
 __device__ __forceinline__ void gs_barrier() { asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -253,27 +212,11 @@ __device__ __forceinline__ void gs_barrier() { asm volatile("s_waitcnt vmcnt(7) 
 __global__ __launch_bounds__(512, 1) void gemm_sliced_kernel(GsArgs a, int swz) {
   // two stages of activation digits (written by the helpers one slab ahead), three of weight digits (LDS-DMA
   // by the matrix wavefronts, two slabs ahead: a piece has more than a period to land)
-  __shared__ __attribute__((aligned(1024))) char lds[5 * GS_OPER];           // 140 KB
+  __shared__ __attribute__((aligned(1024))) char lds[GS_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tn_count = a.N / GS_T;
-  const int tiles = (a.M / GS_T) * tn_count;
-  const long w = xcd_swizzle(blockIdx.x, gridDim.x, swz);
-  const int grp = (int)(w / tiles), tile = (int)(w % tiles);
-  const int tm = tile / tn_count, tn = tile % tn_count;
-  const int op = grp < a.groups0 ? 0 : 1;
-  const int gl = op ? grp - a.groups0 : grp;
-  const long K = a.K[op];
-  const long kbeg = (long)gl * a.klen;
-  const long kend = kbeg + a.klen < K ? kbeg + a.klen : K;
-  const int nslab = (int)((kend - kbeg) / 64);
-  const int NT = a.N / 16;
-
-  const char* bsrc = a.img[op] + ((kbeg / 64) * NT + tn * 4) * (long)(GS_NS * GS_FRAG) + lane * 16;
-  const long bstep = (long)NT * (GS_NS * GS_FRAG);               // next k-slab of the image
-  // experiment 64: shader clock over the kernel (s_memtime counts core clocks, s_memrealtime 100 MHz)
-  unsigned long long t0c = 0, t0r = 0, twait = 0, twait2 = 0;
-  if (L2Q_GS_EXP & 64) { t0c = __builtin_amdgcn_s_memtime(); t0r = __builtin_amdgcn_s_memrealtime(); }
+  const GsTile t = gs_tile(a, swz);
+  const int nslab = t.nslab;
   if (wave < 4) {
     // ================================================================ matrix wavefronts
     const int wm = wave >> 1, wn = wave & 1;
@@ -283,15 +226,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sliced_kernel(GsArgs a, int swz) 
     // the MFMA stream is the critical path: the arbiter should serve it first and fit the helper's conversion
     // arithmetic (same SIMD) into the gaps
     __builtin_amdgcn_s_setprio(L2Q_GS_PRIO);
-    gs_v4i acc[4][GS_NS];
-    double racc[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int g = 0; g < GS_NS; ++g) acc[t][g] = (gs_v4i){0, 0, 0, 0};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) racc[t][r] = 0.0;
-    }
+    GsClock<(L2Q_GS_EXP & 64) != 0> clk;
     // The activation fragments are XOR-swizzled in LDS: piece (row r, k-chunk g) of a fragment sits in slot
     // 16 g + (r ^ 2 g) instead of 16 g + r.  A helper's ds_write_b128 (8 consecutive lanes = 2 rows x 4 chunks)
     // then covers all 32 banks once instead of hitting four of them 4 times (PMC before: half of the LDS-active
@@ -299,11 +234,12 @@ __global__ __launch_bounds__(512, 1) void gemm_sliced_kernel(GsArgs a, int swz) 
     // conflict-free (both checked by enumeration over the bank model of MI355X_MICROARCH.md).
     const char* abase = lds + (2 * wm) * (GS_NS * GS_FRAG) + ((lane & 48) | ((lane & 15) ^ ((lane >> 4) * 2))) * 16;
     const char* bbase = lds + 2 * GS_OPER + (2 * wn) * (GS_NS * GS_FRAG) + lane * 16;
-    int p3 = 0;                                                // p % 3
     // The weight digits come in by LDS-DMA, issued by the MATRIX wavefronts (the helpers are the longer path:
     // a memory instruction costs the issuing wavefront 60-180 clocks, and these wavefronts otherwise wait
     // ~1400 clocks per slab at the barrier): wavefront w moves fragments w, w + 4, ..., w + 24 of a slab, one
     // after each MFMA group of row 0, two slabs ahead (three stages: a piece has more than a period to land).
+    const char* bsrc = gs_wsrc(a, t, lane);
+    const long bstep = gs_wstep(t);
     auto dma_b = [&](int q, int f) {
       if (L2Q_GS_EXP & 4) return;
       const int qc = q < nslab ? q : nslab - 1;                 // past the end: the last slab again, into a free stage
@@ -317,127 +253,23 @@ __global__ __launch_bounds__(512, 1) void gemm_sliced_kernel(GsArgs a, int swz) 
 #pragma unroll
     for (int f = 0; f < GS_NS; ++f) dma_b(1, f);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    gs_v4i bf[2][GS_NS], af[2][2], afd[2][2];
-    bool pending = false;                                      // rows 5, 6 of the previous slab not issued yet
-    for (int p = 0; p < nslab; ++p) {
-      unsigned long long tb = 0;
-      if (L2Q_GS_EXP & 64) tb = __builtin_amdgcn_s_memtime();
-      gs_barrier();                                            // B(p): the stages of slab p are complete
-      if (L2Q_GS_EXP & 64) twait += __builtin_amdgcn_s_memtime() - tb;
-      const int soa = (p & 1) * GS_OPER, sob = p3 * GS_OPER;
-      p3 = p3 == 2 ? 0 : p3 + 1;
-      // Reads and MFMAs in an explicit order, the reads as asm with explicit lgkmcnt waits (LDS returns in
-      // order): left to the compiler, all 18 reads of the first row are hoisted and waited for with
-      // lgkmcnt(0) -- ~600 clocks of LDS time with four wavefronts reading -- before the first MFMA.  Row 0
-      // starts on four reads and pulls the other weight fragments in two groups ahead; the activation
-      // fragments of row s + 1 are read while row s runs.  A fragment is only touched through its wait.
-      const unsigned aaddr = (unsigned)(unsigned long)(gs_lds_ptr_t)(abase + soa);
-      const unsigned baddr = (unsigned)(unsigned long)(gs_lds_ptr_t)(bbase + sob);
-      auto rd_a = [&](auto sc, gs_v4i (&dst)[2]) {
-        constexpr int S = decltype(sc)::value;
-        gs_dsr<S * GS_FRAG>(dst[0], aaddr);
-        gs_dsr<(GS_NS + S) * GS_FRAG>(dst[1], aaddr);
-      };
-      auto rd_b = [&](auto tc) {
-        constexpr int T = decltype(tc)::value;
-        gs_dsr<T * GS_FRAG>(bf[0][T], baddr);
-        gs_dsr<(GS_NS + T) * GS_FRAG>(bf[1][T], baddr);
-      };
-      auto mm = [&](const gs_v4i (&a2)[2], int s, int t) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (!(L2Q_GS_EXP & 2) || (i == 0 && j == 0))
-              acc[2 * i + j][s + t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a2[i], bf[j][t], acc[2 * i + j][s + t], 0, 0, 0);
-      };
-      // The last two rows of a slab (12 MFMAs, fragments kept in afd and in the weight fragments 0 and 1) are
-      // issued after the NEXT barrier, behind the first reads of the next slab: they cover the barrier and the
-      // LDS latency, during which the matrix pipe would idle.  Row 0 runs t = 6 ... 0 so that its first weight
-      // fragments go into registers the old slab no longer needs.
-      auto tail = [&]() {
-        mm(afd[0], 5, 0);
-        mm(afd[0], 5, 1);
-        mm(afd[1], 6, 0);
-      };
-      rd_a(gs_c<0>(), af[0]);
-      rd_b(gs_c<6>());
-      rd_b(gs_c<5>());
-      rd_b(gs_c<4>());
-      if (pending) {
-        gs_wait<8>(afd[0][0], afd[0][1], afd[1][0], afd[1][1]);   // (complete since the barrier; orders the MFMAs)
-        tail();
-      }
-      rd_b(gs_c<3>());
-      gs_for<0, GS_NS>([&](auto uc) {                       // row 0: 7 groups of 4 MFMAs
-        constexpr int T = GS_NS - 1 - decltype(uc)::value;
-        // outstanding behind the fragments of group T: three more pairs (two for T = 1, one for T = 0)
-        gs_wait<(T >= 2 ? 6 : T == 1 ? 4 : 2)>(af[0][0], af[0][1], bf[0][T], bf[1][T]);
-        mm(af[0], 0, T);
-        dma_b(p + 2, GS_NS - 1 - T);
-        if constexpr (T >= 4) rd_b(gs_c<T - 4>());
-        if constexpr (T == 3) rd_a(gs_c<1>(), af[1]);
-      });
-      gs_for<1, 5>([&](auto sc) {                           // rows 1..4: 24, 20, 16, 12 MFMAs
-        constexpr int S = decltype(sc)::value;
-        gs_wait<0>(af[S & 1][0], af[S & 1][1], bf[0][0], bf[1][0]);
-        if constexpr (S < 4) rd_a(gs_c<S + 1>(), af[(S + 1) & 1]);
-        if constexpr (S == 4) {
-          rd_a(gs_c<5>(), afd[0]);
-          rd_a(gs_c<6>(), afd[1]);
-        }
-#pragma unroll
-        for (int t = 0; S + t < GS_NS; ++t) mm(af[S & 1], S, t);
-      });
-      pending = true;
-      if (((p + 1) & (GS_RANGE / 64 - 1)) == 0 || p + 1 == nslab) {
-        // end of an int32 range: the last rows now, then sum_g 256^(6-g) S_g in fp64, accumulate, clear
-        gs_wait<0>(afd[0][0], afd[0][1], afd[1][0], afd[1][1]);
-        tail();
-        pending = false;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            double x = (double)acc[t][0][r];
-#pragma unroll
-            for (int g = 1; g < GS_NS; ++g) x = fma(x, 256.0, (double)acc[t][g][r]);
-            racc[t][r] += x;
-          }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int g = 0; g < GS_NS; ++g) acc[t][g] = (gs_v4i){0, 0, 0, 0};
-      }
-    }
-    if ((L2Q_GS_EXP & 64) && wave == 0 && lane == 0 && (blockIdx.x & 63) == 0) {
-      const unsigned long long c = __builtin_amdgcn_s_memtime() - t0c, r = __builtin_amdgcn_s_memrealtime() - t0r;
-      printf("block %d: %llu core clocks, %llu x 10 ns -> %.0f MHz, %.0f clocks per slab; matrix wavefront 0 at the barrier %.0f per slab\n",
-             (int)blockIdx.x, c, r, (double)c / ((double)r * 0.01), (double)c / nslab, (double)twait / nslab);
-    }
+    double racc[4][4];
+    gs_slab_loop<L2Q_GS_EXP>(abase, bbase, nslab, racc, [&]() { clk.timed(gs_barrier); },
+                             [&](int p, int f) { dma_b(p + 2, f); });
+    clk.print(wave, lane, nslab);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (no DMA may outlive the workgroup's LDS)
-    // C/D layout of v_mfma_i32_16x16x64_i8: col = lane & 15, row = 4 (lane >> 4) + reg
-    double* part = a.part + (long)grp * a.M * a.N;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int n = tn * GS_T + (2 * wn + j) * 16 + (lane & 15);
-        const double cs = a.wsc[op][n] * a.post[op];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = tm * GS_T + (2 * wm + i) * 16 + 4 * (lane >> 4) + r;
-          part[(long)m * a.N + n] = racc[2 * i + j][r] * cs;
-        }
-      }
+    gs_store_part(a, t, wm, wn, lane, racc);
     return;
   }
 
   // ================================================================== helper wavefronts
   const int h = wave - 4;                                       // row tile of the A operand
+  const int op = t.op, tm = t.tm;
+  const long K = t.K, kbeg = t.kbeg;
+  unsigned long long twait = 0, twait2 = 0;                     // (experiment 64)
   const double sc = a.sc[op], lim = a.lim[op];
   const int hr = lane >> 2, hg = lane & 3;                      // row of the tile / k-group this thread slices
-  const double* arow = a.A[op] + (long)(tm * GS_T + h * 16 + hr) * K + kbeg;
+  const double* arow = (const double*)a.A[op] + (long)(tm * GS_T + h * 16 + hr) * K + kbeg;
   int bad = 0;
   // The activation loads are written as asm: the compiler's own wait placement for register loads that cross
   // the loop edge is a vmcnt(0) at the top of every period (seen in the ISA), which would expose the latency
@@ -576,14 +408,16 @@ __global__ __launch_bounds__(256) void gs_reduce_kernel(const double* __restrict
   }
 }
 
-static inline size_t gs_image_bytes(int N, long K) {
-  return (size_t)(K / 64) * (size_t)(N / 16) * GS_NS * GS_FRAG;
-}
 static inline size_t gs_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// a weight image: the digits [K / 64][N / 16][7][fragment], then (256-byte aligned each) the column scales and the
+// build's row exponents and flag
+static inline size_t gs_image_bytes(int N, long K) {
+  return gs_align((size_t)(K / 64) * (size_t)(N / 16) * GS_NS * GS_FRAG);
+}
 
 // k per group: about 256 workgroups in all (one round of one per CU), at least 4096 k (64 slabs: the
 // prologue and the partial-sum traffic stay small), at most 64 int32 ranges
-static long gs_pick_klen(int M, int N, long K, long K2) {
+static long gs_klen(int M, int N, long K, long K2) {
   const long tiles = (long)(M / GS_T) * (N / GS_T);
 #ifndef L2Q_GS_TARGET
 #define L2Q_GS_TARGET 256      // (A/B at cfg-4, same box: 256 -> 0.450 ms, 512 -> 0.454-0.464, 1024 -> 0.471-0.476)
@@ -594,14 +428,49 @@ static long gs_pick_klen(int M, int N, long K, long K2) {
   return klen;
 }
 
-// what gemm_digits.hip (the same layer on activation digit images, digits.hpp) shares with this file: with the same
-// k-grouping, the same flag and the same reduce kernel its output has the bits of l2q_gemm_sliced_f64's
-long gs_klen(int M, int N, long K, long K2) { return gs_pick_klen(M, N, K, K2); }
 int* gs_flag() { return gs_flag_ptr(); }
-void gs_launch_reduce(const double* part, int groups, long MN, int N, const double* bias, const double* bias2,
-                      const double* coeff, double scale, int act, int* flag, double* C, hipStream_t st) {
-  hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)cdiv(MN, 256)), dim3(256), 0, st, part, groups, MN, N, bias, bias2,
-                     coeff, scale, act, flag, C);
+
+int gs_launch(const char* what, gs_kernel_t kernel, const char* align_msg, const void* A, const void* image, long K,
+              int a_exp, const void* A2, const void* image2, long K2, int a2_exp, int M, int N, const double* bias,
+              const double* bias2, const double* coeff, double scale, int act, double* C, void* ws, size_t ws_bytes,
+              void* stream) {
+  L2Q_REQUIRE_W(A && image && C && ws, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE_W(K2 == 0 || (A2 && image2), L2Q_EINVAL, "second operand pair missing");
+  L2Q_REQUIRE_W(M > 0 && N > 0 && K > 0 && K2 >= 0, L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE_W(M % GS_T == 0 && N % GS_T == 0 && K % 64 == 0 && K2 % 64 == 0, L2Q_ESHAPE,
+                "the sliced layer serves M, N % 64 == 0 and K, K2 % 64 == 0");
+  L2Q_REQUIRE_W(a_exp > -900 && a_exp < 900 && a2_exp > -900 && a2_exp < 900, L2Q_EINVAL, "bad operand exponent");
+  L2Q_REQUIRE_W(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
+  L2Q_REQUIRE_W(ws_bytes >= l2q_gemm_sliced_ws_bytes(M, N, K, K2), L2Q_ESHAPE, "workspace too small");
+  auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
+  L2Q_REQUIRE_W(al(A, 15) && (!A2 || al(A2, 15)) && al(image, 255) && (!image2 || al(image2, 255)) && al(ws, 255),
+                L2Q_ESHAPE, align_msg);
+  hipStream_t st = (hipStream_t)stream;
+  GsArgs a;
+  const long klen = gs_klen(M, N, K, K2);
+  const int g0 = (int)cdiv(K, klen), g1 = K2 > 0 ? (int)cdiv(K2, klen) : 0;
+  a.A[0] = A; a.A[1] = A2;
+  a.img[0] = (const char*)image; a.img[1] = (const char*)image2;
+  a.wsc[0] = (const double*)((const char*)image + gs_image_bytes(N, K));
+  a.wsc[1] = K2 > 0 ? (const double*)((const char*)image2 + gs_image_bytes(N, K2)) : nullptr;
+  a.K[0] = K; a.K[1] = K2;
+  const int ex[2] = {a_exp, a2_exp};
+  for (int o = 0; o < 2; ++o) {
+    a.sc[o] = ldexp(1.0, GS_BITS - ex[o]);
+    a.lim[o] = ldexp(1.0, ex[o]);
+    a.post[o] = ldexp(1.0, ex[o]);
+  }
+  a.groups0 = g0; a.klen = klen; a.M = M; a.N = N;
+  const int groups = g0 + g1;
+  a.part = (double*)ws;
+  a.flag = gs_flag_ptr();
+  L2Q_REQUIRE_W(a.flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
+  const int tiles = (M / GS_T) * (N / GS_T);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(groups * tiles)), dim3(512), 0, st, a, tuning().xcd_swizzle);
+  const long MN = (long)M * N;
+  hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)cdiv(MN, 256)), dim3(256), 0, st, (const double*)ws, groups, MN,
+                     N, bias, bias2, coeff, scale, act, a.flag, C);
+  return check_launch(what);
 }
 
 }  // namespace l2q
@@ -612,7 +481,7 @@ extern "C" {
 
 size_t l2q_gemm_sliced_bytes(int N, long K) {
   if (N <= 0 || K <= 0 || N % GS_T != 0 || K % 64 != 0) return 0;
-  return gs_align(gs_image_bytes(N, K)) + gs_align((size_t)N * sizeof(double)) + gs_align((size_t)N * sizeof(int)) + 256;
+  return gs_image_bytes(N, K) + gs_align((size_t)N * sizeof(double)) + gs_align((size_t)N * sizeof(int)) + 256;
 }
 
 int l2q_gemm_sliced_build(const double* W, int N, long K, void* image, size_t image_bytes, int* usable,
@@ -625,7 +494,7 @@ int l2q_gemm_sliced_build(const double* W, int N, long K, void* image, size_t im
               L2Q_ESHAPE, "W must be 16-byte aligned, the image 256-byte");
   hipStream_t st = (hipStream_t)stream;
   char* buf = (char*)image;
-  double* wsc = (double*)(buf + gs_align(gs_image_bytes(N, K)));
+  double* wsc = (double*)(buf + gs_image_bytes(N, K));
   int* exps = (int*)((char*)wsc + gs_align((size_t)N * sizeof(double)));
   int* flag = (int*)((char*)exps + gs_align((size_t)N * sizeof(int)));
   (void)hipMemsetAsync(flag, 0, sizeof(int), st);
@@ -644,7 +513,7 @@ int l2q_gemm_sliced_build(const double* W, int N, long K, void* image, size_t im
 
 size_t l2q_gemm_sliced_ws_bytes(int M, int N, long K, long K2) {
   if (M <= 0 || N <= 0 || K <= 0 || K2 < 0) return 0;
-  const long klen = gs_pick_klen(M, N, K, K2);
+  const long klen = gs_klen(M, N, K, K2);
   const long groups = cdiv(K, klen) + (K2 > 0 ? cdiv(K2, klen) : 0);
   return (size_t)groups * M * N * sizeof(double) + 512;
 }
@@ -653,43 +522,9 @@ int l2q_gemm_sliced_f64(const double* A, const void* image, long K, int a_exp, c
                         const void* image2, long K2, int a2_exp, int M, int N, const double* bias,
                         const double* bias2, const double* coeff, double scale, int act, double* C, void* ws,
                         size_t ws_bytes, void* stream) {
-  L2Q_REQUIRE(A && image && C && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(K2 == 0 || (A2 && image2), L2Q_EINVAL, "second operand pair missing");
-  L2Q_REQUIRE(M > 0 && N > 0 && K > 0 && K2 >= 0, L2Q_EINVAL, "non-positive size");
-  L2Q_REQUIRE(M % GS_T == 0 && N % GS_T == 0 && K % 64 == 0 && K2 % 64 == 0, L2Q_ESHAPE,
-              "the sliced layer serves M, N % 64 == 0 and K, K2 % 64 == 0");
-  L2Q_REQUIRE(a_exp > -900 && a_exp < 900 && a2_exp > -900 && a2_exp < 900, L2Q_EINVAL, "bad operand exponent");
-  L2Q_REQUIRE(act >= L2Q_ACT_NONE && act <= L2Q_ACT_SWISH, L2Q_EINVAL, "bad activation");
-  L2Q_REQUIRE(ws_bytes >= l2q_gemm_sliced_ws_bytes(M, N, K, K2), L2Q_ESHAPE, "workspace too small");
-  auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-  L2Q_REQUIRE(al(A, 15) && (!A2 || al(A2, 15)) && al(image, 255) && (!image2 || al(image2, 255)) && al(ws, 255),
-              L2Q_ESHAPE, "operands must be 16-byte aligned (images and workspace 256-byte)");
-  hipStream_t st = (hipStream_t)stream;
-  GsArgs a;
-  const long klen = gs_pick_klen(M, N, K, K2);
-  const int g0 = (int)cdiv(K, klen), g1 = K2 > 0 ? (int)cdiv(K2, klen) : 0;
-  a.A[0] = A; a.A[1] = A2;
-  a.img[0] = (const char*)image; a.img[1] = (const char*)image2;
-  a.wsc[0] = (const double*)((const char*)image + gs_align(gs_image_bytes(N, K)));
-  a.wsc[1] = K2 > 0 ? (const double*)((const char*)image2 + gs_align(gs_image_bytes(N, K2))) : nullptr;
-  a.K[0] = K; a.K[1] = K2;
-  const int ex[2] = {a_exp, a2_exp};
-  for (int o = 0; o < 2; ++o) {
-    a.sc[o] = ldexp(1.0, GS_BITS - ex[o]);
-    a.lim[o] = ldexp(1.0, ex[o]);
-    a.post[o] = ldexp(1.0, ex[o]);
-  }
-  a.groups0 = g0; a.klen = klen; a.M = M; a.N = N;
-  const int groups = g0 + g1;
-  a.part = (double*)ws;
-  a.flag = gs_flag_ptr();
-  L2Q_REQUIRE(a.flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
-  const int tiles = (M / GS_T) * (N / GS_T);
-  hipLaunchKernelGGL(gemm_sliced_kernel, dim3((unsigned)(groups * tiles)), dim3(512), 0, st, a, tuning().xcd_swizzle);
-  const long MN = (long)M * N;
-  hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)cdiv(MN, 256)), dim3(256), 0, st, (const double*)ws, groups, MN,
-                     N, bias, bias2, coeff, scale, act, a.flag, C);
-  return check_launch("l2q_gemm_sliced_f64");
+  return gs_launch("l2q_gemm_sliced_f64", gemm_sliced_kernel,
+                   "operands must be 16-byte aligned (images and workspace 256-byte)", A, image, K, a_exp, A2, image2, K2,
+                   a2_exp, M, N, bias, bias2, coeff, scale, act, C, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1268,7 +1268,7 @@ int l2q_su3_expm_mul2_digits(const void* xn, const void* vn, double eps, const f
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_expm_mul_digits_kernel, dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock), 0,
                      (hipStream_t)stream, (const double2*)xn, (const double2*)vn, eps, mask_n, complement_first,
-                     (double2*)out, (char*)image, (int)V, nblk, 0, ldexp(1.0, GD_BITS - a_exp), ldexp(1.0, a_exp), flag);
+                     (double2*)out, (char*)image, (int)V, nblk, 0, ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp), flag);
   return check_launch("l2q_su3_expm_mul2_digits");
 }
 
@@ -1282,7 +1282,7 @@ int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, 
   L2Q_REQUIRE(flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
   const long nblk = cdiv(V, kBlock);
   hipLaunchKernelGGL(su3_project_digits_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const double2*)in, (char*)image, (int)V, nblk, ldexp(1.0, GD_BITS - a_exp), ldexp(1.0, a_exp),
+                     (const double2*)in, (char*)image, (int)V, nblk, ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp),
                      flag);
   return check_launch("l2q_su3_projsu_digits");
 }

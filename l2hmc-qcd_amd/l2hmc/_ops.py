@@ -503,6 +503,26 @@ def gemm_sliced_build(w: torch.Tensor):
     return buf if usable.value else None
 
 
+def _sliced_out_ws(name: str, ok: bool, m: int, n: int, k: int, k2: int, device, what: str):
+    """(output, workspace) of a sliced input-layer call; refuses shapes csrc/gemm_sliced.hip does not serve."""
+    if not ok or not gemm_sliced_ok(m, n, k, k2):
+        raise N.L2QError(f'{name}: {what}')
+    out = torch.empty((m, n), dtype=torch.float64, device=device)
+    return out, N.workspace(int(N.load().l2q_gemm_sliced_ws_bytes(m, n, k, k2)), device)
+
+
+def sliced_input_images(wx: torch.Tensor, wv: torch.Tensor, gate: str, gated: bool = True):
+    """Digit images (ix, iv) of the input layer's two weight matrices, or None when they do not fit comfortably
+    (memory gate `gate`; skipped with gated=False) or a matrix is refused.  The images take 7/8 of the weights' bytes
+    again (2 x 235 MB per vnet at cfg-4, 2 x 3.8 GB at 16^4): built only while that leaves most of the free memory
+    alone."""
+    need = 2 * (wx.numel() + wv.numel()) * 8
+    if gated and not mem_gate(gate, need, 0.25, wx.device):
+        return None
+    ix, iv = gemm_sliced_build(wx), gemm_sliced_build(wv)
+    return (ix, iv) if ix is not None and iv is not None else None
+
+
 def gemm_sliced(a: torch.Tensor, image: torch.Tensor, n: int, bias: Optional[torch.Tensor] = None, *,
                 a_exp: int = SLICED_INPUT_EXP, a2: Optional[torch.Tensor] = None,
                 image2: Optional[torch.Tensor] = None, a2_exp: int = SLICED_INPUT_EXP,
@@ -512,10 +532,8 @@ def gemm_sliced(a: torch.Tensor, image: torch.Tensor, n: int, bias: Optional[tor
     activations sliced on the fly: every |a| must be < 2^a_exp (else the output is NaN)."""
     m, k = a.shape
     k2 = 0 if a2 is None else a2.shape[1]
-    if a.dtype != torch.float64 or not gemm_sliced_ok(m, n, k, k2) or (a2 is not None and image2 is None):
-        raise N.L2QError(f'gemm_sliced: a{tuple(a.shape)} n {n} k2 {k2} {a.dtype}')
-    out = torch.empty((m, n), dtype=a.dtype, device=a.device)
-    ws = N.workspace(int(N.load().l2q_gemm_sliced_ws_bytes(m, n, k, k2)), a.device)
+    out, ws = _sliced_out_ws('gemm_sliced', a.dtype == torch.float64 and not (a2 is not None and image2 is None),
+                             m, n, k, k2, a.device, f'a{tuple(a.shape)} n {n} k2 {k2} {a.dtype}')
     N.call('l2q_gemm_sliced_f64', a, image, k, int(a_exp), a2, image2, k2, int(a2_exp), m, n, bias, bias2,
            coeff, float(scale), N.ACT[act], out, ws, ws.numel())
     return out
@@ -586,10 +604,8 @@ def gemm_digits(a: DigitImage, image: torch.Tensor, n: int, bias: Optional[torch
     """gemm_sliced with the activations given as digit images: the same bits."""
     m, k = a.shape
     k2 = 0 if a2 is None else a2.shape[1]
-    if not gemm_sliced_ok(m, n, k, k2) or (a2 is not None and (image2 is None or a2.shape[0] != m)):
-        raise N.L2QError(f'gemm_digits: a{a.shape} n {n} k2 {k2}')
-    out = torch.empty((m, n), dtype=torch.float64, device=a.buf.device)
-    ws = N.workspace(int(N.load().l2q_gemm_sliced_ws_bytes(m, n, k, k2)), a.buf.device)
+    out, ws = _sliced_out_ws('gemm_digits', not (a2 is not None and (image2 is None or a2.shape[0] != m)),
+                             m, n, k, k2, a.buf.device, f'a{a.shape} n {n} k2 {k2}')
     N.call('l2q_gemm_digits_f64', a.buf, image, k, a.exp, None if a2 is None else a2.buf, image2, k2,
            0 if a2 is None else a2.exp, m, n, bias, bias2, coeff, float(scale), N.ACT[act], out, ws, ws.numel())
     return out

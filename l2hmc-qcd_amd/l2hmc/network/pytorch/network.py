@@ -695,13 +695,8 @@ class LeapfrogLayer(nn.Module):
         elif sliced_exp is not None and ops.USE_SLICED_INPUT[0] and x.dtype == torch.float64 and \
                 ops.gemm_sliced_pays(x.shape[0], w['wx'].shape[0], x.shape[1], v.shape[1]):
             if 'input_img' not in w:
-                # the images take 7/8 of the weights' bytes again (2 x 235 MB per vnet at cfg-4, 2 x 3.8 GB
-                # at 16^4): built only while that leaves most of the free memory alone
-                need = 2 * (w['wx'].numel() + w['wv'].numel()) * 8
-                ix = iv = None
-                if not x.is_cuda or ops.mem_gate('sliced input-layer images', need, 0.25, x.device):
-                    ix, iv = ops.gemm_sliced_build(w['wx']), ops.gemm_sliced_build(w['wv'])
-                w['input_img'] = (ix, iv) if ix is not None and iv is not None else None
+                w['input_img'] = ops.sliced_input_images(w['wx'], w['wv'], 'sliced input-layer images',
+                                                         gated=x.is_cuda)
             if w['input_img'] is not None:
                 z = ops.gemm_sliced(x, w['input_img'][0], w['wx'].shape[0], w['bx'], a_exp=sliced_exp,
                                     a2=v, image2=w['input_img'][1], a2_exp=sliced_exp, bias2=w['bv'],
@@ -1130,10 +1125,7 @@ class LeapfrogLayer(nn.Module):
         imgs = None
         if (ops.USE_SLICED_INPUT[0] and wx.dtype == torch.float64 and wx.is_cuda
                 and ops.gemm_sliced_pays(nb, wx.shape[0], wx.shape[1], wv.shape[1])):
-            need = 2 * (wx.numel() + wv.numel()) * 8
-            if ops.mem_gate('sliced input-layer images (training tape)', need, 0.25, wx.device):
-                ix, iv = ops.gemm_sliced_build(wx), ops.gemm_sliced_build(wv)
-                imgs = (ix, iv) if ix is not None and iv is not None else None
+            imgs = ops.sliced_input_images(wx, wv, 'sliced input-layer images (training tape)')
         nat['input_img'] = imgs
         return imgs
 

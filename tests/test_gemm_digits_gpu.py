@@ -159,3 +159,23 @@ def test_producer_flag_poisons_the_layer_once(ops):
         ab[2, 100] = bad
         assert bool(torch.isnan(ops.gemm_digits(ops.gemm_digits_slice(ab), img, n, b)).all()), bad
         assert bool(torch.isfinite(ops.gemm_digits(ops.gemm_digits_slice(a), img, n, b)).all())
+
+
+def test_gemm_digits_long_groups(ops):
+    """Workgroups whose k-group spans more than one int32 range (16 384 k): the shared slab loop folds the group sums
+    into fp64 after slab 256 and runs on.  256 x 256 x 278 528 (= 17 x 16 384) has k-groups of 17 408, the smallest
+    such shape at this tile count; the workspace size pins the k-grouping so the flush stays reached."""
+    from l2hmc import native as N
+    m, n, k = 256, 256, 17 * 16384
+    assert int(N.load().l2q_gemm_sliced_ws_bytes(m, n, k, 0)) == 16 * m * n * 8 + 512
+    g = torch.Generator(device='cuda').manual_seed(4)
+    a = (torch.rand(m, k, dtype=torch.float64, device='cuda', generator=g) - 0.5) * 4.6
+    w = (torch.rand(n, k, dtype=torch.float64, device='cuda', generator=g) - 0.5) * (2.0 / k ** 0.5)
+    b = 0.1 * torch.randn(n, dtype=torch.float64, device='cuda', generator=g)
+    img = ops.gemm_sliced_build(w)
+    assert img is not None
+    want = ops.gemm_sliced(a, img, n, b)
+    got = ops.gemm_digits(ops.gemm_digits_slice(a), img, n, b)
+    assert torch.equal(got, want)
+    ref = ops.gemm(a, w, b)
+    assert float((got - ref).abs().max()) < 5e-13 * max(1.0, float(ref.abs().max()))

@@ -17,7 +17,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc')
-KERNEL = '_ZN3l2q18gemm_digits_kernelENS_6GdArgsEi'
+KERNEL = 'gemm_digits_kernel'          # (found by this part of its mangled name)
 
 
 def isa() -> str:
@@ -39,9 +39,9 @@ def regs(tok: str):
 
 
 def check(text: str):
-    body = text[text.index(KERNEL + ':'):]
+    body = text[re.search(r'^\w*' + KERNEL + r'\w*:', text, re.M).start():]
     body = body[:body.index('.Lfunc_end')]
-    meta = text[text.index('.name:           ' + KERNEL):]
+    meta = text[re.search(r'\.name:\s+\w*' + KERNEL, text).start():]
     spill = int(re.search(r'\.vgpr_spill_count:\s*(\d+)', meta).group(1))
     vgpr = int(re.search(r'\.vgpr_count:\s*(\d+)', meta).group(1))
     errors = []

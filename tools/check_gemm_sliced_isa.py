@@ -61,10 +61,10 @@ def loops(lines):
 
 def check(text: str):
     problems = []
-    k = text[text.index('_ZN3l2q18gemm_sliced_kernelENS_6GsArgsEi:'):]
+    k = text[re.search(r'^\w*gemm_sliced_kernel\w*:', text, re.M).start():]      # (by this part of its mangled name)
     k = k[:k.index('.Lfunc_end')]
     lines = k.split('\n')
-    meta = text[text.index('.name:           _ZN3l2q18gemm_sliced_kernelENS_6GsArgsEi'):]
+    meta = text[re.search(r'\.name:\s+\w*gemm_sliced_kernel', text).start():]
     spill = int(re.search(r'\.vgpr_spill_count:\s+(\d+)', meta).group(1))
     vgpr = int(re.search(r'\.vgpr_count:\s+(\d+)', meta).group(1))
     if spill:
