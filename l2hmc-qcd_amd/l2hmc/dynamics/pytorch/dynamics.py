@@ -34,7 +34,7 @@ from torch import nn
 import l2hmc.configs as cfgs
 from l2hmc import DEVICE
 from l2hmc import _ops as ops
-from l2hmc.dynamics.pytorch.trajectory import SamplerStepper, run_trajectory
+from l2hmc.dynamics.pytorch.trajectory import X_HALVES, SamplerStepper, VInputs, run_trajectory
 from l2hmc.group.su3.pytorch.group import SU3
 from l2hmc.group.u1.pytorch.group import U1Phase
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
@@ -636,66 +636,11 @@ class Dynamics(nn.Module):
         return (w.get('input_img') is not None and w['wx'].dtype == torch.float64
                 and ops.gemm_sliced_pays(nb, w['wx'].shape[0], 32 * V, 32 * V))
 
-    def _v_inputs_n(self, vnet, xn: Tensor, beta, ts: Optional[SamplerStepper] = None):
-        """(force, hidden activation z, kernel weights) for the fused heads kernel.  `ts`
-        (trajectory-local, `ts.reuse`): the force, the vec8 network inputs and z depend only on x
-        (and the network), and x does not change between the closing v-update of one leapfrog step
-        and the opening v-update of the next (nor across the momentum flip), so they are computed
-        once per distinct x -- 9 instead of 16 evaluations in a merged nlf = 4 trajectory.
-        Same inputs, same deterministic kernels: bitwise identical results."""
-        nb = xn.shape[0]
-        reuse = ts is not None and ts.reuse
-        if reuse and ts.valid:
-            fn = ts.F
-        else:
-            if reuse and ts.want_pe:
-                # the potential of this x is consumed: it comes out of the force launch
-                fn, ts.plaq = ops.su3_force_action_n(xn, _beta(beta), self.latvolume)
-            else:
-                fn = self._force_n(xn, beta)
-                if reuse:
-                    ts.plaq = None
-            if reuse:                  # what was kept belongs to another x (xv_pre is of the new x already)
-                ts.valid, ts.F = True, fn
-                ts.xv = ts.fv = None
-                ts.z = {}
-        if not self._can_fuse_heads(vnet):
-            return fn, None, None
-        p = self._perms()
-        w = vnet.kernel_weights(p['in'], p['out'])
-        hs = w['heads_scaled']
-        # int8 slice image of the head weights (csrc/heads_sliced.hip); lives in the version-keyed
-        # weight cache, so it is rebuilt whenever a parameter changes.  Both knobs are consulted on
-        # EVERY call (`use_sliced`), the image is built the first time they are both on.
-        hs['use_sliced'] = bool(self._sliced_wanted(vnet) and ops.USE_SLICED_HEADS[0])
-        if hs['use_sliced'] and 'sliced' not in hs:
-            hs['sliced'] = ops.heads_sliced_build(hs)
-        if reuse and id(vnet) in ts.z:
-            return fn, ts.z[id(vnet)], w
-        if reuse and ts.xv is not None:
-            xv, fv = ts.xv, ts.fv
-            if isinstance(xv, ops.DigitImage) and not self._digit_inputs(vnet, nb, xn.shape[-1]):
-                # kept for another network of this x; this one takes fp64 activations
-                xv = ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
-                fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
-        else:
-            pre = None
-            if reuse:
-                pre, ts.xv_pre = ts.xv_pre, None     # vec8(x) emitted by the x-update that produced x
-            if self._digit_inputs(vnet, nb, xn.shape[-1]):
-                xv = pre if isinstance(pre, ops.DigitImage) else ops.su3_projsu_digits_n(xn)
-                fv = ops.su3_projsu_digits_n(fn)
-            else:
-                if isinstance(pre, ops.DigitImage):      # (a knob changed since the x-update: x itself is at hand)
-                    pre = None
-                xv = pre if pre is not None else ops.su3_projsu_vec8_n(xn).reshape(nb, -1)
-                fv = ops.su3_projsu_vec8_n(fn).reshape(nb, -1)
-            if reuse:
-                ts.xv, ts.fv = xv, fv
-        z = vnet.hidden_flat(xv, fv, w, sliced_exp=ops.SLICED_INPUT_EXP if self.sliced_input else None)
-        if reuse:
-            ts.z[id(vnet)] = z
-        return fn, z, w
+    def _v_inputs_n(self, vnet, xn: Tensor, beta, ts=None):
+        """(force, hidden activation z, kernel weights) for the fused heads kernel at xn, kept nowhere (what a
+        trajectory keeps of them is `trajectory.VInputs`; `ts` is None: a trajectory's state lives in its stepper)."""
+        assert ts is None
+        return VInputs(self, beta).get(vnet, xn)
 
     def _sliced_wanted(self, vnet) -> bool:
         """`sliced_heads`: True -> networks whose last hidden activation is BOUNDED (tanh: every row
@@ -724,18 +669,10 @@ class Dynamics(nn.Module):
                 and getattr(net, 'half_dtype', None) is not None)
 
     def _update_v_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool,
-                    ts: Optional[SamplerStepper] = None, acc: Optional[Tensor] = None,
-                    v_src: Optional[Tensor] = None, norm2: Optional[list] = None) -> Tensor:
+                    acc: Optional[Tensor] = None) -> Tensor:
         """v-update in place (dynamics.py:1266-1297); returns logdet [nb] (the fused U(1) kernel
-        adds it into `acc` when given).  `norm2`: a list that receives sum |v'|^2 [nb] of the updated momentum
-        when the kernel that runs emits it (ops.vnet_heads_vupdate_), and stays empty otherwise.  `v_src`: the momentum is read from there and only
-        written to vn (the heads kernel does that itself; the other paths copy first)."""
-        eps = self._eps('v', step)
-        nb = xn.shape[0]
-        vnet = self._get_vnet(step)
-        if v_src is not None and not (self.group == 'SU3' and self._can_fuse_heads(vnet)):
-            vn.copy_(v_src)
-            v_src = None
+        adds it into `acc` when given)."""
+        nb, eps, vnet = xn.shape[0], self._eps('v', step), self._get_vnet(step)
         fw = self._fused_u1(vnet)
         if fw is not None:            # force + vnet + update in one launch
             return ops.u1_vstep_(xn, vn, _beta(beta), eps, forward, self.latvolume, fw, acc)
@@ -748,38 +685,7 @@ class Dynamics(nn.Module):
             z = vnet.hidden_flat_h(x.reshape(nb, -1), fn.reshape(nb, -1), w)
             return ops.u1_heads_update_h_(z, w['h']['heads_scaled'], vnet.nw.t, vn.reshape(nb, -1),
                                           fn.reshape(nb, -1), eps, forward)
-        fn, z, w = self._v_inputs_n(vnet, xn, beta, ts)
-        if z is not None:
-            # heads + momentum update in one kernel: s, t, q never reach HBM
-            return ops.vnet_heads_vupdate_(z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q),
-                                           vn.reshape(nb, -1), fn.reshape(nb, -1), eps, forward,
-                                           None if v_src is None else v_src.reshape(nb, -1), norm2=norm2)
-        if v_src is not None:
-            vn.copy_(v_src)
-        s, t, q = self._vnet_n(step, xn, fn)
-        return ops.v_update_(vn.reshape(nb, -1), fn.reshape(nb, -1), s, t, q, eps, forward)
-
-    def _update_v_pair_n(self, step0: int, forward0: bool, flip: bool, step1: int,
-                         forward1: bool, xn: Tensor, vn: Tensor, beta,
-                         ts: Optional[SamplerStepper] = None) -> Tensor:
-        """The closing v-update of one leapfrog step and the opening v-update of the next (same
-        x, same network => same s, t, q), optionally with the merged trajectory's v -> -v in
-        between (dynamics.py:1001), from ONE evaluation of the heads.  Sum of both logdets.
-        With `ts.late` (per-step metrics, verbose=True): the kernel also returns the first update's
-        logdet and the kinetic energy of the momentum between the two updates; they are left in
-        ts.ld1 / ts.ke and the return value is the SECOND update's logdet alone."""
-        nb = xn.shape[0]
-        vnet = self._get_vnet(step1)
-        fn, z, w = self._v_inputs_n(vnet, xn, beta, ts)
-        args = (z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q), vn.reshape(nb, -1),
-                fn.reshape(nb, -1), self._eps('v', step0), forward0, flip, self._eps('v', step1),
-                forward1)
-        if ts is None or not ts.late:
-            return ops.vnet_heads_vupdate_pair_(*args)
-        ld, ts.ld1, vn2 = ops.vnet_heads_vupdate_pair_mid_(*args)
-        # group/su3/pytorch/group.py:125-126 as l2q_su3_kinetic_reduce evaluates it
-        ts.ke = self._kinetic_from_norm2(vn2)
-        return ld - ts.ld1
+        return VInputs(self, beta).update_v(step, xn, vn, forward)
 
     def _can_pair_mid(self) -> bool:
         """The mid-point pair kernel (LDS-DMA heads kernel) needs whole 16-wide K-slabs."""
@@ -822,109 +728,47 @@ class Dynamics(nn.Module):
             return ops.scale(vn, -1.0, out=vn)
         return vn.neg_()
 
-    def _lf_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool,
-              ts: Optional[SamplerStepper] = None) -> Tensor:
-        """One generalised leapfrog step in place; returns logdet [nb]
-        (dynamics.py:1187-1228).  `ts` (optional): the state of the trajectory this step belongs
-        to (trajectory.SamplerStepper).  `ts.defer` defers the closing v-update: it is then executed
-        together with the next step's opening v-update (`_update_v_pair_n`), its logdet being
-        returned by that next call; the caller flushes a last pending update with
-        `_flush_pending_n`.  `ts.late` (with `ts.defer`, per-step metrics): the deferred closing
-        update's logdet and the kinetic energy right after it are left in ts.ld1 / ts.ke, and the
-        returned logdet covers THIS step's sub-updates only.  `ts.x_src` (first step of a
-        trajectory, SU(3)): the configuration is READ from there and the x-update writes it into
-        xn, so the trajectory never copies its input; `ts.v_src` likewise for the momentum of the
-        step's opening v-update."""
-        if forward:
-            st, order = step, ((False, True), (True, False))     # (complement, first)
-        else:
-            st = self.config.nleapfrog - step - 1
-            order = ((True, False), (False, True))
-        m = self._native_masks()[st]
-        if self.group == 'U1' and self.fuse_u1_steps:
-            fv = self._fused_u1(self._get_vnet(st))
-            fx = {True: self._fused_u1(self._get_xnet(st, True)),
-                  False: self._fused_u1(self._get_xnet(st, False))} if fv is not None else None
-            if fv is not None and fx[True] is not None and fx[False] is not None:
-                # four one-launch sub-updates, the log-det summed inside the kernels
-                nb, b = xn.shape[0], _beta(beta)
-                ev, ex = self._eps('v', st), self._eps('x', st)
-                ld = ops.u1_vstep_(xn, vn, b, ev, forward, self.latvolume, fv)
-                for comp, first in order:
-                    ops.u1_xstep_(xn.reshape(nb, -1), vn, m, comp, ex, forward,
-                                  self.config.use_ncp, fx[first], ld)
-                ops.u1_vstep_(xn, vn, b, ev, forward, self.latvolume, fv, ld)
-                return ld
-        prev = x_src = v_src = None
-        if ts is not None:                   # taken: the pending update and the sources are this step's to use
-            prev, x_src, v_src = ts.pending, ts.x_src, ts.v_src
-            ts.pending = ts.x_src = ts.v_src = None
-            # per-step metrics: the potential of every x a step produced is consumed (not the trajectory's input's)
-            ts.want_pe = bool(ts.energies and ts.late and prev is not None)
-        late = bool(prev is not None and ts.late)
-        xr = xn if x_src is None else x_src              # where this step reads x before its x-update
-        if v_src is not None and prev is not None:
-            vn.copy_(v_src)
-            v_src = None
-        if prev is not None:
-            st0, f0, flip = prev
-            v0, v1 = self._get_vnet(st0), self._get_vnet(st)
-            if v0 is v1 and self._can_fuse_heads(v1):
-                ld = self._update_v_pair_n(st0, f0, flip, st, forward, xr, vn, beta, ts)
-            else:
-                ld = self._update_v_n(st0, xr, vn, beta, f0, ts)
-                if late:
-                    ts.ld1, ts.ke = ld, self._kinetic_n(vn)
-                if flip:
-                    self._flip_v_n(vn)
-                l1 = self._update_v_n(st, xr, vn, beta, forward, ts)
-                ld = l1 if late else ld + l1
-        else:
-            ld = self._update_v_n(st, xr, vn, beta, forward, ts, v_src=v_src)
+    def _update_x_both_n(self, st: int, xn: Tensor, vn: Tensor, m: Tensor, forward: bool, ld: Tensor,
+                         x_src: Optional[Tensor] = None) -> Tensor:
+        """Both x half-updates of step `st` (mask m) in place on xn (`x_src`: read from there); returns ld + their logdet"""
         if self.group == 'SU3' and self.fuse_x_updates:
             # both half-updates share expm(eps v): one kernel, one pass over x
             eps = self._eps('x', st)
-            if (ts is not None and ts.reuse and self.fuse_x_vec8
-                    and self._can_fuse_heads(self._get_vnet(st))):
-                if self._digit_inputs(self._get_vnet(st), xn.shape[0], xn.shape[-1]):
-                    _, ts.xv_pre = ops.su3_expm_mul2_digits_n(xr, vn, eps if forward else -eps, m, not forward,
-                                                              out=xn)
-                else:
-                    _, xv = ops.su3_expm_mul2_vec8_n(xr, vn, eps if forward else -eps, m, not forward,
-                                                     out=xn)
-                    ts.xv_pre = xv.reshape(xn.shape[0], -1)
-            else:
-                ops.su3_expm_mul2_n(xr, vn, eps if forward else -eps, m, not forward, out=xn)
-        else:
-            if x_src is not None:
-                xn.copy_(x_src)
-            for comp, first in order:
-                l = self._update_x_n(st, xn, vn, m, comp, forward, first)
-                if l is not None:
-                    ld = ld + l
-        if ts is not None:
-            ts.valid = False                           # x changed
-            if ts.defer:
-                ts.pending = (st, forward, False)      # closing v-update deferred
-                return ld
-        return ld + self._update_v_n(st, xn, vn, beta, forward, ts)
-
-    def _flush_pending_n(self, ts: Optional[SamplerStepper], xn, vn, beta) -> Optional[Tensor]:
-        prev = ts.pending if ts is not None else None
-        if prev is None:
-            return None
-        ts.pending = None
-        st0, f0, flip = prev
-        # the trajectory's last update: the force launch leaves the potential of the final x in ts.plaq and
-        # the heads kernel the final momentum's sum |v|^2 (the sign flip does not change it)
-        n2 = [] if ts.energies else None
-        ts.want_pe = ts.energies
-        ld = self._update_v_n(st0, xn, vn, beta, f0, ts, norm2=n2)
-        ts.want_pe = False
-        ts.ke_out = self._kinetic_from_norm2(n2[0]) if n2 else None
-        if flip:
-            self._flip_v_n(vn)
+            ops.su3_expm_mul2_n(xn if x_src is None else x_src, vn, eps if forward else -eps, m, not forward, out=xn)
+            return ld
+        if x_src is not None:
+            xn.copy_(x_src)
+        for comp, first in X_HALVES[forward]:
+            l = self._update_x_n(st, xn, vn, m, comp, forward, first)
+            if l is not None:
+                ld = ld + l
         return ld
+
+    def _lf_fused_u1_n(self, st: int, xn: Tensor, vn: Tensor, m: Tensor, beta, forward: bool) -> Optional[Tensor]:
+        """Leapfrog step `st` as four one-launch U(1) sub-updates, the log-det summed inside the kernels; None
+        (nothing done) unless all three networks of the step take them."""
+        fv = self._fused_u1(self._get_vnet(st)) if self.group == 'U1' else None
+        fx = None if fv is None else {first: self._fused_u1(self._get_xnet(st, first)) for first in (True, False)}
+        if fv is None or fx[True] is None or fx[False] is None:
+            return None
+        nb, b, ev, ex = xn.shape[0], _beta(beta), self._eps('v', st), self._eps('x', st)
+        ld = ops.u1_vstep_(xn, vn, b, ev, forward, self.latvolume, fv)
+        for comp, first in X_HALVES[forward]:
+            ops.u1_xstep_(xn.reshape(nb, -1), vn, m, comp, ex, forward, self.config.use_ncp, fx[first], ld)
+        ops.u1_vstep_(xn, vn, b, ev, forward, self.latvolume, fv, ld)
+        return ld
+
+    def _lf_n(self, step: int, xn: Tensor, vn: Tensor, beta, forward: bool) -> Tensor:
+        """One generalised leapfrog step in place, with no memory of the steps around it; returns logdet [nb]
+        (dynamics.py:1187-1228).  What adjacent steps of a trajectory share is kept by `trajectory.SamplerStepper`."""
+        st = step if forward else self.config.nleapfrog - step - 1
+        m = self._native_masks()[st]
+        ld = self._lf_fused_u1_n(st, xn, vn, m, beta, forward)
+        if ld is not None:
+            return ld
+        ld = self._update_v_n(st, xn, vn, beta, forward)
+        ld = self._update_x_both_n(st, xn, vn, m, forward, ld)
+        return ld + self._update_v_n(st, xn, vn, beta, forward)
 
     # ------------------------------------------------------------------ public sub-updates
     def group_to_vec(self, x: Tensor) -> Tensor:

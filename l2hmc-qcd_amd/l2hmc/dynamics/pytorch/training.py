@@ -539,8 +539,8 @@ def _lf_train(dyn, tape: Tape, step: int, x, v, beta, forward: bool, share: Opti
 
 class TapeStepper:
     """trajectory.run_trajectory's stepper for training: functional steps (`_lf_train`) recorded on a Tape.
-    Nothing is deferred, so the metrics of a step are never late."""
-    late = False
+    Nothing is deferred, so the metrics of a step are never late, and the Hamiltonian's terms are passes of their own."""
+    late = energies = False
 
     def __init__(self, dyn, beta: float, merged: bool):
         if not dyn._networks_built:
