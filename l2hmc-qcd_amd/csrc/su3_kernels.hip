@@ -662,6 +662,16 @@ __device__ __forceinline__ int su3_vec8_to_digits(const double (&w)[8], char* im
   }
   return bad;
 }
+// The 18 values of a matrix through an empty asm: what was computed before this point is complete here and
+// nothing after it is moved in front.  The instantiations of su3_expm_mul_body must give each other's bits
+// (links, vec8, digits of the same arguments), and m3_expm leaves its multiply-adds to the compiler, which
+// fuses only inside a basic block: without the pin the optimiser moved part of the exponential's last sums
+// into a later block in ONE instantiation (the digits one, after its tail changed) and its links differed in
+// the last bit from the other two.
+__device__ __forceinline__ void m3_pin(M3& m) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(m.re[i]), "+v"(m.im[i]));
+}
 // VEC: 0 links only, 1 + vec8 as fp64 (out_vec), 2 + vec8 as digits (out_vec is the image; V % 64 == 0)
 template <bool TWO, int VEC>
 __device__ __forceinline__ void su3_expm_mul_body(const double2* xn, const double2* __restrict__ vn, double eps,
@@ -682,6 +692,7 @@ __device__ __forceinline__ void su3_expm_mul_body(const double2* xn, const doubl
 #pragma unroll
     for (int i = 0; i < 9; ++i) { a.re[i] = e.re[i] * eps; a.im[i] = e.im[i] * eps; }
     m3_expm(e, a);
+    m3_pin(e);
   }
   // (the link is requested only now: it would otherwise be live across the exponential; the other
   // wavefronts of the SIMD cover its latency)
@@ -739,13 +750,12 @@ __device__ __forceinline__ void su3_expm_mul_body(const double2* xn, const doubl
     }
   }
   M3& r = x;
+  m3_pin(r);
   store_link(out + f * 9L * V, V, s, r);
   if constexpr (VEC != 0) {
     if (s >= lo) {
-      M3 p;
-      m3_project_su(p, r);
       double w[8];
-      m3_to_vec8(w, p);
+      m3_project_su_vec8(w, r);
       if constexpr (VEC == 1) {
 #pragma unroll
         for (int a = 0; a < 8; ++a) static_cast<double*>(out_vec)[(f * 8 + a) * (long)V + s] = w[a];
@@ -792,19 +802,19 @@ __global__ __launch_bounds__(kBlock) void su3_project_kernel(const double2* in,
   if (s >= V) return;
   M3 x, r;
   load_link(x, in + f * 9L * V, V, s);
-  if (MODE == 2) {
-    m3_tah(r, x);
-  } else if (MODE == 3) {
-    m3_project_u(r, x);
-  } else {
-    m3_project_su(r, x);
-  }
-  if (MODE == 1) {
+  if constexpr (MODE == 1) {
     double v[8];
-    m3_to_vec8(v, r);
+    m3_project_su_vec8(v, x);
 #pragma unroll
     for (int a = 0; a < 8; ++a) out_vec[(f * 8 + a) * (long)V + s] = v[a];
   } else {
+    if (MODE == 2) {
+      m3_tah(r, x);
+    } else if (MODE == 3) {
+      m3_project_u(r, x);
+    } else {
+      m3_project_su(r, x);
+    }
     store_link(out_links + f * 9L * V, V, s, r);
   }
 }
@@ -814,11 +824,10 @@ __global__ __launch_bounds__(kBlock) void su3_project_digits_kernel(const double
   const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
   const int s = (int)blk * kBlock + threadIdx.x;
   if (s >= V) return;
-  M3 x, r;
+  M3 x;
   load_link(x, in + f * 9L * V, V, s);
-  m3_project_su(r, x);
   double v[8];
-  m3_to_vec8(v, r);
+  m3_project_su_vec8(v, x);
   if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
 }
 

@@ -254,6 +254,23 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
   static constexpr double kInv[22] = {
       1.0 / 1, 1.0 / 2, 1.0 / 3, 1.0 / 4, 1.0 / 5, 1.0 / 6, 1.0 / 7, 1.0 / 8, 1.0 / 9, 1.0 / 10, 1.0 / 11,
       1.0 / 12, 1.0 / 13, 1.0 / 14, 1.0 / 15, 1.0 / 16, 1.0 / 17, 1.0 / 18, 1.0 / 19, 1.0 / 20, 1.0 / 21, 1.0 / 22};
+  // Early exit, same bits as all 20 steps.  With |a|_F <= 0.5 the eigenvalues obey sum |l_i|^2 <= 1/4, hence
+  // |p2| <= 0.87, |p1| <= 0.25, |p0| <= 0.025, and one step maps S = |a_n| + |b_n| + |c_n| (moduli) to
+  //   S' <= (|c| |p0| + |a| + |c| |p1| + |b| + |c| |p2|) / (n + 1) <= 1.14 S / (n + 1) <= 0.29 S      (n + 1 >= 4
+  // for every step after the first), the roundings of a step adding a few 2^-53 relative to the same sums of
+  // moduli.  So once T = sum of the six |components| (>= S) satisfies 2^53 T <= |f| for each of the six real
+  // sums f, every later term component t has |t| <= 0.29 T < 2^-54 |f|, less than half the gap from f to either
+  // neighbour: f + t rounds to f, f never moves again and the induction carries to step 20.  A sum that is
+  // exactly zero (a real matrix: all imaginary parts) is passed only by T == 0, after which all terms stay zero.
+  // A NaN fails every comparison and runs all steps; so does the capped scaling (|a|_F may exceed 0.5 there,
+  // `big` = +inf), and an infinite or NaN norm.
+#ifndef L2Q_EXPM_EARLY_EXIT
+#define L2Q_EXPM_EARLY_EXIT 1
+#endif
+  const double big = nrm < 0x1p59 ? 0x1p53 : HUGE_VAL;
+#ifdef L2Q_EXPM_COUNT_STEPS
+  int steps = 0;
+#endif
 #pragma unroll 1
   for (int n = 2; n < 22; ++n) {
     const double inv = L2Q_EXPM_DIV ? 1.0 / (double)(n + 1) : kInv[n];
@@ -266,7 +283,19 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
     const double ncr = (br + zr) * inv, nci = (bi + zi) * inv;
     ar = nar; ai = nai; br = nbr; bi = nbi; cr = ncr; ci = nci;
     f0r += ar; f0i += ai; f1r += br; f1i += bi; f2r += cr; f2i += ci;
+#ifdef L2Q_EXPM_COUNT_STEPS
+    ++steps;
+#endif
+    if (L2Q_EXPM_EARLY_EXIT) {
+      const double tt = big * (((fabs(ar) + fabs(ai)) + (fabs(br) + fabs(bi))) + (fabs(cr) + fabs(ci)));
+      if ((tt <= fabs(f0r)) & (tt <= fabs(f0i)) & (tt <= fabs(f1r)) & (tt <= fabs(f1i)) & (tt <= fabs(f2r)) &
+          (tt <= fabs(f2i)))
+        break;
+    }
   }
+#ifdef L2Q_EXPM_COUNT_STEPS
+  L2Q_EXPM_COUNT_STEPS(steps);
+#endif
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     double xr, xi, yr, yi;
@@ -284,15 +313,25 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
   }
 }
 
+// The routines from here to m3_project_su_vec8 (the projection) are inlined into several kernels that must give each other's
+// bits (the vec8 and the digit producers): every fused multiply-add in them is written out and the compiler is
+// told not to form others, so that no kernel's schedule decides which product of a sum gets fused.
+#if defined(__clang__)
+#define L2Q_FP_AS_WRITTEN _Pragma("clang fp contract(off)")
+#else
+#define L2Q_FP_AS_WRITTEN
+#endif
+
 // Closed-form eigenvalues of a 3x3 positive Hermitian matrix from (tr, tr(M^2), det).
 // utils.py:227-283 (same clamps: +-3e38 on 1/q^1.5, acos argument to +-(1 - 1e-12)).
 __device__ __forceinline__ void eigs3x3(double& e0, double& e1, double& e2, double tr, double p2,
                                         double det) {
+  L2Q_FP_AS_WRITTEN
   const double tr3 = (1.0 / 3.0) * tr;
   const double p23 = (1.0 / 3.0) * p2;
   const double tr32 = tr3 * tr3;
   const double q = fabs(0.5 * (p23 - tr32));
-  const double r = 0.25 * tr3 * (5.0 * tr32 - p2) - 0.5 * det;
+  const double r = fma(0.25 * tr3, fma(5.0, tr32, -p2), -(0.5 * det));
   const double sq = sqrt(q);
   const double sq3 = q * sq;
   double isq3 = 1.0 / sq3;
@@ -306,39 +345,151 @@ __device__ __forceinline__ void eigs3x3(double& e0, double& e1, double& e2, doub
   const double sqc = sq * ct;
   const double sqs = 1.7320508075688772 * sq * st;
   const double ll = tr3 + sqc;
-  e0 = tr3 - 2.0 * sqc;
+  e0 = fma(-2.0, sqc, tr3);
   e1 = ll + sqs;
   e2 = ll - sqs;
 }
 
-// m = x (x^H x)^(-1/2)                                 utils.py:286-338
-__device__ __forceinline__ void m3_project_u(M3& m, const M3& x) {
-  M3 t, t2;
-  m3_mul_an(t, x, x);
-  m3_mul_nn(t2, t, t);
-  const double tr = t.re[0] + t.re[4] + t.re[8];
-  const double p2 = t2.re[0] + t2.re[4] + t2.re[8];
-  double detr, deti;
-  m3_det(detr, deti, t);
+// A Hermitian 3x3 matrix held as what fixes it: the real diagonal and the upper triangle
+// (o = 0: (0,1), 1: (0,2), 2: (1,2)); the lower triangle is the conjugate and is never formed.
+struct H3 {
+  double d[3];
+  double re[3];
+  double im[3];
+};
+
+// T = X^H X: the diagonal as column norms, the upper triangle with the sums of m3_mul_an
+__device__ __forceinline__ void h3_gram(H3& t, const M3& x) {
+  L2Q_FP_AS_WRITTEN
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { s = fma(x.re[3 * k + i], x.re[3 * k + i], s); s = fma(x.im[3 * k + i], x.im[3 * k + i], s); }
+    t.d[i] = s;
+  }
+#pragma unroll
+  for (int o = 0; o < 3; ++o) {
+    const int i = o == 2 ? 1 : 0, j = o == 0 ? 1 : 2;
+    double sr = 0.0, si = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double ar = x.re[3 * k + i], ai = -x.im[3 * k + i];
+      const double br = x.re[3 * k + j], bi = x.im[3 * k + j];
+      sr = fma(ar, br, sr); sr = fma(-ai, bi, sr);
+      si = fma(ar, bi, si); si = fma(ai, br, si);
+    }
+    t.re[o] = sr; t.im[o] = si;
+  }
+}
+
+// S = T T for Hermitian T (Hermitian again)
+__device__ __forceinline__ void h3_square(H3& s, const H3& t) {
+  L2Q_FP_AS_WRITTEN
+  const double n01 = fma(t.re[0], t.re[0], t.im[0] * t.im[0]);
+  const double n02 = fma(t.re[1], t.re[1], t.im[1] * t.im[1]);
+  const double n12 = fma(t.re[2], t.re[2], t.im[2] * t.im[2]);
+  s.d[0] = fma(t.d[0], t.d[0], n01 + n02);
+  s.d[1] = fma(t.d[1], t.d[1], n01 + n12);
+  s.d[2] = fma(t.d[2], t.d[2], n02 + n12);
+  // (0,1) = (t00 + t11) t01 + t02 conj(t12)
+  const double a01 = t.d[0] + t.d[1], a02 = t.d[0] + t.d[2], a12 = t.d[1] + t.d[2];
+  s.re[0] = fma(a01, t.re[0], fma(t.re[1], t.re[2], t.im[1] * t.im[2]));
+  s.im[0] = fma(a01, t.im[0], fma(t.im[1], t.re[2], -(t.re[1] * t.im[2])));
+  // (0,2) = (t00 + t22) t02 + t01 t12
+  s.re[1] = fma(a02, t.re[1], fma(t.re[0], t.re[2], -(t.im[0] * t.im[2])));
+  s.im[1] = fma(a02, t.im[1], fma(t.re[0], t.im[2], t.im[0] * t.re[2]));
+  // (1,2) = (t11 + t22) t12 + conj(t01) t02
+  s.re[2] = fma(a12, t.re[2], fma(t.re[0], t.re[1], t.im[0] * t.im[1]));
+  s.im[2] = fma(a12, t.im[2], fma(t.re[0], t.im[1], -(t.im[0] * t.re[1])));
+}
+
+// det of a Hermitian matrix (real): t00 t11 t22 + 2 Re(t01 t12 conj(t02)) - t00 |t12|^2 - t11 |t02|^2 - t22 |t01|^2
+__device__ __forceinline__ double h3_det(const H3& t) {
+  L2Q_FP_AS_WRITTEN
+  const double n01 = fma(t.re[0], t.re[0], t.im[0] * t.im[0]);
+  const double n02 = fma(t.re[1], t.re[1], t.im[1] * t.im[1]);
+  const double n12 = fma(t.re[2], t.re[2], t.im[2] * t.im[2]);
+  const double qr = fma(t.re[0], t.re[2], -(t.im[0] * t.im[2]));      // t01 t12
+  const double qi = fma(t.re[0], t.im[2], t.im[0] * t.re[2]);
+  const double tri = fma(qr, t.re[1], qi * t.im[1]);                  // Re(t01 t12 conj(t02))
+  double det = t.d[0] * fma(t.d[1], t.d[2], -n12);
+  det = fma(-t.d[1], n02, det);
+  det = fma(-t.d[2], n01, det);
+  return fma(2.0, tri, det);
+}
+
+// r = (x^H x)^(-1/2) as c0 + c1 t + c2 t^2, t = x^H x          utils.py:286-338
+__device__ __forceinline__ void h3_rsqrt_gram(H3& r, const M3& x) {
+  L2Q_FP_AS_WRITTEN
+  H3 t, t2;
+  h3_gram(t, x);
+  h3_square(t2, t);
+  const double tr = t.d[0] + t.d[1] + t.d[2];
+  const double p2 = t2.d[0] + t2.d[1] + t2.d[2];
+  const double det = h3_det(t);
   double e0, e1, e2;
-  eigs3x3(e0, e1, e2, tr, p2, detr);
+  eigs3x3(e0, e1, e2, tr, p2, det);
   const double se0 = sqrt(fabs(e0)), se1 = sqrt(fabs(e1)), se2 = sqrt(fabs(e2));
   const double u = se0 + se1 + se2;
   const double w = se0 * se1 * se2;
   const double d = w * (se0 + se1) * (se0 + se2) * (se1 + se2);
   const double di = 1.0 / d;
-  const double c0 = di * (w * u * u + e0 * se0 * (e1 + e2) + e1 * se1 * (e0 + e2)
-                          + e2 * se2 * (e0 + e1));
-  const double c1 = -(tr * u + w) * di;
+  const double c0 = di * fma(e2 * se2, e0 + e1, fma(e1 * se1, e0 + e2, fma(e0 * se0, e1 + e2, w * u * u)));
+  const double c1 = -fma(tr, u, w) * di;
   const double c2 = u * di;
-  M3 r;
 #pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    r.re[i] = c1 * t.re[i] + c2 * t2.re[i];
-    r.im[i] = c1 * t.im[i] + c2 * t2.im[i];
+  for (int i = 0; i < 3; ++i) {
+    r.d[i] = fma(c2, t2.d[i], fma(c1, t.d[i], c0));
+    r.re[i] = fma(c2, t2.re[i], c1 * t.re[i]);
+    r.im[i] = fma(c2, t2.im[i], c1 * t.im[i]);
   }
-  r.re[0] += c0; r.re[4] += c0; r.re[8] += c0;
-  m3_mul_nn(m, x, r);
+}
+
+// m3_det with its fused multiply-adds written out (m3_det itself is shared with m3_expm, whose bits are left as
+// the compiler makes them)
+__device__ __forceinline__ void m3_det_as_written(double& dr, double& di, const M3& m) {
+  L2Q_FP_AS_WRITTEN
+  auto mul = [](double& cr, double& ci, double ar, double ai, double br, double bi) {
+    cr = fma(ar, br, -(ai * bi));
+    ci = fma(ar, bi, ai * br);
+  };
+  double t0r, t0i, t1r, t1i, t2r, t2i, ar, ai, br, bi;
+  mul(ar, ai, m.re[4], m.im[4], m.re[8], m.im[8]);
+  mul(br, bi, m.re[5], m.im[5], m.re[7], m.im[7]);
+  mul(t0r, t0i, m.re[0], m.im[0], ar - br, ai - bi);
+  mul(ar, ai, m.re[3], m.im[3], m.re[8], m.im[8]);
+  mul(br, bi, m.re[5], m.im[5], m.re[6], m.im[6]);
+  mul(t1r, t1i, m.re[1], m.im[1], ar - br, ai - bi);
+  mul(ar, ai, m.re[3], m.im[3], m.re[7], m.im[7]);
+  mul(br, bi, m.re[4], m.im[4], m.re[6], m.im[6]);
+  mul(t2r, t2i, m.re[2], m.im[2], ar - br, ai - bi);
+  dr = (t0r - t1r) + t2r; di = (t0i - t1i) + t2i;
+}
+
+// entry (i, j) of X R, R Hermitian
+__device__ __forceinline__ void m3_mul_h3_entry(double& sr, double& si, const M3& x, const H3& r, int i, int j) {
+  L2Q_FP_AS_WRITTEN
+  sr = x.re[3 * i + j] * r.d[j]; si = x.im[3 * i + j] * r.d[j];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (k == j) continue;
+    const int lo = k < j ? k : j, hi = k < j ? j : k, o = lo + hi - 1;
+    const double br = r.re[o], bi = k < j ? r.im[o] : -r.im[o];    // r_kj: stored for k < j, its conjugate below
+    const double ar = x.re[3 * i + k], ai = x.im[3 * i + k];
+    sr = fma(ar, br, sr); sr = fma(-ai, bi, sr);
+    si = fma(ar, bi, si); si = fma(ai, br, si);
+  }
+}
+
+// m = x (x^H x)^(-1/2)                                 utils.py:286-338
+__device__ __forceinline__ void m3_project_u(M3& m, const M3& x) {
+  H3 r;
+  h3_rsqrt_gram(r, x);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) m3_mul_h3_entry(m.re[3 * i + j], m.im[3 * i + j], x, r, i, j);
 }
 
 // out = projectU(x) * exp(-i arg(det)/3)                utils.py:341-346
@@ -355,6 +506,44 @@ __device__ __forceinline__ void m3_project_su(M3& out, const M3& x) {
     out.re[i] = m.re[i] * cp - m.im[i] * sp;
     out.im[i] = m.re[i] * sp + m.im[i] * cp;
   }
+}
+
+// v = m3_to_vec8(m3_project_su(x)) to rounding, forming only what the eight components read: the strict upper
+// triangle and the diagonal of x r (the rotated diagonal's imaginary part needs both parts of the unrotated
+// one).  The phase is taken from det x: det(x r) = det x det r, and det r is real (r is Hermitian) and
+// positive whenever c0 + c1 l + c2 l^2 > 0 at the three eigenvalues l of x^H x -- it approximates l^(-1/2)
+// there, also at the clamps of eigs3x3 (a degenerate spectrum: q = 0 gives three equal e, the polynomial is
+// then exact at that l).  It fails only where the closed form itself has lost the spectrum (condition numbers
+// of 1e4 and beyond), where the full form is no better.
+__device__ __forceinline__ void m3_project_su_vec8(double v[8], const M3& x) {
+  L2Q_FP_AS_WRITTEN
+  H3 r;
+  h3_rsqrt_gram(r, x);
+  double detr, deti;
+  m3_det_as_written(detr, deti, x);
+  const double p = (-1.0 / 3.0) * atan2(deti, detr);
+  double sp, cp;
+  sincos(p, &sp, &cp);
+  double mr[3], mi[3], dr[3], dim[3];
+#pragma unroll
+  for (int o = 0; o < 3; ++o) m3_mul_h3_entry(mr[o], mi[o], x, r, o == 2 ? 1 : 0, o == 0 ? 1 : 2);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) m3_mul_h3_entry(dr[i], dim[i], x, r, i, i);
+  double ure[3], uim[3], di[3];
+#pragma unroll
+  for (int o = 0; o < 3; ++o) {
+    ure[o] = fma(mr[o], cp, -(mi[o] * sp));
+    uim[o] = fma(mr[o], sp, mi[o] * cp);
+    di[o] = fma(dr[o], sp, dim[o] * cp);
+  }
+  v[0] = -2.0 * uim[0];
+  v[1] = -2.0 * ure[0];
+  v[2] = di[1] - di[0];
+  v[3] = -2.0 * uim[1];
+  v[4] = -2.0 * ure[1];
+  v[5] = -2.0 * uim[2];
+  v[6] = -2.0 * ure[2];
+  v[7] = 0.57735026918962584 * (fma(2.0, di[2], -di[1]) - di[0]);
 }
 
 // 8 real adjoint components (utils.py:394-420)
