@@ -239,6 +239,25 @@ int l2q_su3_flow_stage(const void* x_in, const void* p_in, double c, double s, v
  * x_in, x_out, ws_x must be three different fields. */
 int l2q_su3_flow_step(const void* x_in, void* x_out, void* ws_p, void* ws_x, double eps, int nb, int T, int X,
                       int Y, int Z, void* stream);
+/* The same step with an embedded error estimate for a step-size controller (csrc/su3_flow_adaptive.hip; Fritzsch &
+ * Ramos, arXiv:1301.4388 App. D).  With G_i = TAH(W_i A(W_i)), Z_i = -eps G_i and the low-storage generators kept
+ * apart, P1 = G0, P2 = P1 - 32/17 G1, P3 = P2 + 27/17 G2 (as l2q_su3_flow_step_bwd keeps them),
+ *   W3 = exp(-17 eps/36 P3) W2  -> x_out                                  (third order, the step of l2q_su3_flow_step)
+ *   W' = exp(-Z0 + 2 Z1) W0 = exp(eps/16 (17 P2 - P1)) W0                 (second order, never stored)
+ *   d[c] = max over mu, x of |W3 - W'|_F / 9                              (9 = N^2), an O(eps^3) quantity
+ * Stages 1 and 2 are l2q_su3_flow_stage, stage 3 the force kick into P3 and ONE kernel, thread per link, that reads
+ * W0, W2, P1, P2, P3, forms both products in registers, writes W3 and reduces d: 864 B per link (two
+ * l2q_su3_expm_mul and a distance pass move 1296 B).  A link whose distance is not finite makes d[c] = +inf.  The
+ * operations on a link depend on the link only: a chain's x_out and d[c] are the same bits alone and in a batch; x_out
+ * differs from l2q_su3_flow_step's only by the FMA contraction of the kernel hosting the last product (1e-16).
+ * x_in is only read, so a rejected step is retried from it.  ws_p3 is THREE consecutive fields of the links' size
+ * (P1, P2, P3), ws_x one; x_in, x_out, ws_x must be three different fields outside ws_p3 (L2Q_EINVAL).  With the
+ * caller's two ping-pong fields that is six fields beside the input.  ws >= l2q_su3_flow_step_err_ws_bytes
+ * (one double per 256 links; L2Q_ESHAPE). */
+size_t l2q_su3_flow_step_err_ws_bytes(int nb, int T, int X, int Y, int Z);
+int l2q_su3_flow_step_err(const void* x_in, void* x_out, void* ws_p3 /* three fields */, void* ws_x, double eps,
+                          double* d /* [nb] */, int nb, int T, int X, int Y, int Z,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- Wilson loops R x T and Polyakov loops */
 /* A line is L_mu(x, n) = U_mu(x) U_mu(x + mu) ... U_mu(x + (n-1) mu), periodic; a field of lines has the shape and the

@@ -311,6 +311,89 @@ def su3_flow_step_n(xn: torch.Tensor, x_out: torch.Tensor, ws_p: torch.Tensor, w
     return x_out
 
 
+def su3_flow_step_err_n(xn: torch.Tensor, x_out: torch.Tensor, ws_p3: torch.Tensor, ws_x: torch.Tensor, eps: float,
+                        lat: Sequence[int], d: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`su3_flow_step_n` with its embedded error estimate (`l2q_su3_flow_step_err`): xn (only read) -> x_out, and
+    returns d [nb] float64 = max over the chain's links of |W3 - W'|_F / 9, W' the second-order result of the same
+    force evaluations (+inf where a link is not finite).  ws_p3 is three scratch fields, [3, *xn.shape]; ws_x one."""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    if tuple(ws_p3.shape) != (3, *xn.shape) or not ws_p3.is_contiguous():
+        raise ValueError(f'su3_flow_step_err_n: ws_p3 must be contiguous [3, {", ".join(map(str, xn.shape))}], got '
+                         f'{list(ws_p3.shape)}')
+    d = torch.empty(nb, dtype=torch.float64, device=xn.device) if d is None else d
+    ws = N.workspace(int(N.load().l2q_su3_flow_step_err_ws_bytes(nb, T, X, Y, Z)), xn.device)
+    N.call('l2q_su3_flow_step_err', xn, x_out, ws_p3, ws_x, float(eps), d, nb, T, X, Y, Z, ws, ws.numel())
+    return d
+
+
+class FlowStepController:
+    """Step-size control of the adaptive Wilson flow (Fritzsch & Ramos, arXiv:1301.4388, App. D); pure Python, it
+    never touches a tensor.  A step of size e whose error estimate is d (the largest over the batch) is accepted iff
+    d <= tol; accepted or not, the next proposal is e min(grow, safety (tol / d)^(1/3)) (d = 0: e grow), at most
+    eps_max where that is given.  A d that is not finite is a rejection that halves e.  More than max_reject
+    rejections in a row raise RuntimeError.
+
+        e = ctl.propose(remaining)      # the step to try: the proposal, shortened to `remaining` where it would pass it
+        ok = ctl.update(e, d, t)        # judges it; ctl.landed tells whether an accepted step ended on the target
+
+    A step shortened to land on a requested time carries forward the larger of its own proposal and the step size it
+    was shortened from, so landing times do not shrink the step."""
+
+    def __init__(self, tol: float, eps0: float = 0.01, eps_max: Optional[float] = None, safety: float = 0.95,
+                 grow: float = 2.0, max_reject: int = 20):
+        tol, eps0 = float(tol), float(eps0)
+        if not (tol > 0 and math.isfinite(tol)) or not (eps0 > 0 and math.isfinite(eps0)):
+            raise ValueError(f'FlowStepController: need finite tol > 0 and eps0 > 0, got {tol}, {eps0}')
+        if eps_max is not None and not float(eps_max) > 0:
+            raise ValueError(f'FlowStepController: need eps_max > 0, got {eps_max}')
+        if not 0 < float(safety) <= 1 or not float(grow) > 1 or int(max_reject) < 0:
+            raise ValueError(f'FlowStepController: need 0 < safety <= 1, grow > 1 and max_reject >= 0, got {safety}, '
+                             f'{grow}, {max_reject}')
+        self.tol, self.safety, self.grow, self.max_reject = tol, float(safety), float(grow), int(max_reject)
+        self.eps_max = None if eps_max is None else float(eps_max)
+        self.eps = self._cap(eps0)          # the next proposal
+        self.landed = False                 # the step judged last was shortened to its landing time
+        self.nreject = 0                    # all rejections
+        self._run = 0                       # rejections in a row
+        self._from = None                   # the proposal that the step in flight was shortened from
+
+    def _cap(self, e: float) -> float:
+        return e if self.eps_max is None else min(e, self.eps_max)
+
+    def propose(self, remaining: Optional[float] = None) -> float:
+        self._from = None
+        if remaining is not None and self.eps >= remaining:
+            self._from = self.eps
+            return float(remaining)
+        return self.eps
+
+    def next_eps(self, e: float, d: float) -> float:
+        """the proposal that follows a step of size e with estimate d"""
+        if not math.isfinite(d):
+            return 0.5 * e
+        f = self.grow if d == 0.0 else min(self.grow, self.safety * (self.tol / d) ** (1.0 / 3.0))
+        return self._cap(e * f)
+
+    def update(self, e: float, d: float, t: float = float('nan')) -> bool:
+        e, d = float(e), float(d)
+        ok = math.isfinite(d) and d <= self.tol
+        nxt = self.next_eps(e, d)
+        self.landed = ok and self._from is not None
+        if ok:
+            self._run = 0
+            self.eps = max(nxt, self._from) if self._from is not None else nxt
+        else:
+            self.nreject += 1
+            self._run += 1
+            self.eps = nxt
+            if self._run > self.max_reject:
+                raise RuntimeError(f'FlowStepController: {self._run} rejected steps in a row at t = {t}, e = {e}, '
+                                   f'd = {d} (tol = {self.tol})')
+        self._from = None
+        return ok
+
+
 def su3_flow_checkpoints_n(xn: torch.Tensor, nsteps: int, eps: float, lat: Sequence[int]):
     """`nsteps` Wilson-flow steps of size eps that keep the field entering each step: -> (flowed, checkpoints) with
     checkpoints[k] the native links entering step k (checkpoints[0] is xn itself, which is never written) -- what

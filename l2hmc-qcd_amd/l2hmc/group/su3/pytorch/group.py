@@ -19,14 +19,35 @@ Tensor = torch.Tensor
 C128 = torch.complex128
 
 
+def _native4(x: Tensor) -> Tensor:
+    """[..., 3, 3] -> [1, 4, 9, m] native planes: the n matrices as the four fields of one chain, m = ceil(n / 4), zero
+    matrices behind the last one.  `l2q_su3_expm_mul` works on whole chains of four fields: handed the single field
+    of `_native` it reads and writes three fields' worth behind each buffer."""
+    x = x.to(device=DEVICE, dtype=C128).contiguous().reshape(-1, 9)
+    n = x.shape[0]
+    m = (n + 3) // 4
+    if 4 * m != n:
+        x = torch.cat([x, x.new_zeros((4 * m - n, 9))])
+    return ops.transpose(x.reshape(4, m, 9), 4, m, 9).reshape(1, 4, 9, m)
+
+
+def _reference4(xn: Tensor, shape: Sequence[int]) -> Tensor:
+    """the inverse of `_native4` for matrices of the given shape [..., 3, 3]"""
+    m = xn.shape[-1]
+    n = 1
+    for i in shape[:-2]:
+        n *= int(i)
+    return ops.transpose(xn.reshape(4, 9, m), 4, 9, m).reshape(4 * m, 9)[:n].reshape(*shape)
+
+
 class SU3(Group):
     def __init__(self) -> None:
         super().__init__(dim=4, shape=[3, 3], dtype=torch.complex128, name='SU3')
 
     def update_gauge(self, x: Tensor, p: Tensor) -> Tensor:
         """matrix_exp(p) @ x  (group.py:45-50) -> l2q_su3_expm_mul"""
-        xn, pn = _native(x), _native(p)
-        return _reference(ops.su3_expm_mul_n(xn, pn, 1.0), x.shape)
+        xn, pn = _native4(x), _native4(p)
+        return _reference4(ops.su3_expm_mul_n(xn, pn, 1.0), x.shape)
 
     def checkSU(self, x: Tensor):
         return checkSU(x)
@@ -46,10 +67,10 @@ class SU3(Group):
         return torch.diagonal(x, dim1=-2, dim2=-1).sum(-1)
 
     def exp(self, x: Tensor) -> Tensor:
-        xn = _native(x)
+        xn = _native4(x)
         eye = torch.zeros_like(xn)
         eye[..., (0, 4, 8), :] = 1.0
-        return _reference(ops.su3_expm_mul_n(eye, xn, 1.0), x.shape)
+        return _reference4(ops.su3_expm_mul_n(eye, xn, 1.0), x.shape)
 
     def diff_trace(self, x: Tensor) -> Tensor:
         log.error('TODO')                       # stubs in the reference too (group.py:80-86)

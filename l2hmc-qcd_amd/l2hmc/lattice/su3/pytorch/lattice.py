@@ -85,6 +85,45 @@ def static_potential(w: Tensor) -> Tensor:
     return _log_positive(w[..., :, :-1] / w[..., :, 1:])
 
 
+def _first_upward_crossing(t: Tensor, g: Tensor, target: float) -> Tensor:
+    """[nb]: where g[k, nb] on the points t[k] first goes from below `target` to at or above it, linearly interpolated
+    between the two points; NaN for a chain with no such pair"""
+    nan = torch.full(g.shape[1:], float('nan'), dtype=g.dtype, device=g.device)
+    if g.shape[0] < 2:
+        return nan
+    up = (g[:-1] < target) & (g[1:] >= target)
+    k = up.to(torch.int8).argmax(0)[None]
+    g0, g1 = g[:-1].gather(0, k)[0], g[1:].gather(0, k)[0]
+    t0, t1 = t[:-1][k[0]], t[1:][k[0]]
+    ok = up.any(0)
+    den = torch.where(ok, g1 - g0, torch.ones_like(g0))
+    return torch.where(ok, t0 + (t1 - t0) * ((target - g0) / den), nan)
+
+
+def scales_from_flow(t: Tensor, E: Tensor, target: float = 0.3) -> dict[str, Tensor]:
+    """The reference scales t0 and w0 (Luescher, arXiv:1006.4518; Borsanyi et al., arXiv:1203.4469) from the energy
+    density E[k, nb] on a uniform grid t[k] of flow times, {'t0': [nb], 'w0': [nb]}, in lattice units.  With
+    F = t^2 E: t0 is the first upward crossing of F through `target`, linearly interpolated between grid points;
+    w0 = sqrt(t*) with t* the first upward crossing of W_k = t_k (F_{k+1} - F_{k-1}) / (2 dt) = t dF/dt at the
+    interior points.  NaN where no crossing is bracketed; never raises on data.  A crossing depends only on the rows
+    up to the one after it, so a table cut off behind both crossings gives the same bits as the whole one.  ValueError
+    on a grid of fewer than four points or one that is not uniform."""
+    t = torch.as_tensor(t, dtype=torch.float64)
+    E = torch.as_tensor(E, dtype=torch.float64).to(t.device)
+    if t.dim() != 1 or E.dim() != 2 or E.shape[0] != t.shape[0]:
+        raise ValueError(f'scales_from_flow: need t [n] and E [n, nb], got {list(t.shape)} and {list(E.shape)}')
+    if t.shape[0] < 4:
+        raise ValueError(f'scales_from_flow: need at least four grid points, got {t.shape[0]}')
+    dt = t[1] - t[0]
+    if not bool(dt > 0) or not bool(((t[1:] - t[:-1] - dt).abs() <= 1e-9 * dt).all()):
+        raise ValueError('scales_from_flow: the grid of flow times must be uniform and increasing')
+    F = t[:, None] ** 2 * E
+    W = t[1:-1, None] * ((F[2:] - F[:-2]) / (2.0 * dt))
+    target = float(target)
+    tstar = _first_upward_crossing(t[1:-1], W, target)
+    return {'t0': _first_upward_crossing(t, F, target), 'w0': torch.sqrt(tstar)}
+
+
 class LatticeSU3(Lattice):
     """4D lattice with SU(3) links: x.shape = [nb, 4, nt, nx, ny, nz, 3, 3] complex128."""
     dim = 4
@@ -233,6 +272,124 @@ class LatticeSU3(Lattice):
             out[name] = torch.stack([getattr(r, name) for r in rows])
         out['t2E'] = tt[:, None] ** 2 * out['E']
         return out
+
+    # ------------------------------------------------------------ adaptive-step flow, t0 and w0
+    def _flow_adaptive_iter(self, xn: Tensor, ts, ctl: ops.FlowStepController, info: dict):
+        """yields the native field at each of the increasing times ts (a buffer that the step after next overwrites):
+        steps of `l2q_su3_flow_step_err` sized by ctl, the step before a time in ts shortened to land on it.  Six fields
+        beside xn, allocated once (two ping-pong, W2, P1..P3); xn is never written, a rejected step is retried from
+        its input.  One read of d [nb] from the device per step.  info collects the accepted steps."""
+        bufs = [torch.empty_like(xn) for _ in range(2)]
+        ws_x = torch.empty_like(xn)
+        ws_p3 = torch.empty((3, *xn.shape), dtype=xn.dtype, device=xn.device)
+        cur, t, k = xn, 0.0, 0
+        for target in ts:
+            while t < target:
+                e = ctl.propose(target - t)
+                out = bufs[k & 1]
+                d = ops.su3_flow_step_err_n(cur, out, ws_p3, ws_x, e, self._lattice_shape).cpu()
+                if ctl.update(e, float(d.max()), t):
+                    info['eps'].append(e)
+                    info['d'].append(d)
+                    t = target if ctl.landed else t + e
+                    cur = out
+                    k += 1
+            yield cur
+
+    @staticmethod
+    def _flow_times(ts, what: str) -> list[float]:
+        ts = [float(t) for t in ts]
+        if any(not b > a for a, b in zip([0.0] + ts[:-1], ts)) or not all(np.isfinite(ts)):
+            raise ValueError(f'{what}: the flow times must be finite, positive and increasing, got {ts}')
+        return ts
+
+    @staticmethod
+    def _flow_info(info: dict, ctl: ops.FlowStepController, nb: int) -> dict:
+        n = len(info['eps'])
+        return {'eps': torch.tensor(info['eps'], dtype=torch.float64),
+                'd': torch.stack(info['d']) if n else torch.empty((0, nb), dtype=torch.float64),
+                'nsteps': n, 'nreject': ctl.nreject}
+
+    def flow_adaptive_n(self, xn: Tensor, t: float, tol: float = 1e-6, eps0: float = 0.01,
+                        eps_max: Optional[float] = None):
+        """The Wilson flow of `flow_n` to time t in third-order steps whose size follows the embedded second-order
+        error estimate d = max over links of |W3 - W'|_F / 9 (`ops.FlowStepController`: a step is accepted iff
+        d <= tol, the next one is e min(2, 0.95 (tol / d)^(1/3))), starting at eps0; lands on t exactly.
+        -> (field, info): a new native field (xn itself for t = 0) and info = {'eps' [nsteps], 'd' [nsteps, nb] (host
+        tensors, the accepted steps), 'nsteps', 'nreject'}.  ONE step size serves the whole batch, driven by its worst
+        chain, so all chains stay at the same t; a chain's result therefore depends on its batch mates at the level
+        of tol.  tol bounds the estimate of each step, not the error at t: at tol = 1e-6 the error of E was below that
+        of `flow` at eps = 0.01 at t = 1 on a rough 4^4 field and twice it at t = 4 on thermalised 8^4 chains, in
+        half the steps (profiles/su3_flow_adaptive.md).  Six fields of memory beside xn."""
+        t = float(t)
+        if not t >= 0 or not np.isfinite(t):
+            raise ValueError(f'flow_adaptive: need a finite t >= 0, got {t}')
+        ctl = ops.FlowStepController(tol, eps0, eps_max)
+        info = {'eps': [], 'd': []}
+        cur = xn
+        for cur in self._flow_adaptive_iter(xn, [t] if t > 0 else [], ctl, info):
+            pass
+        return cur, self._flow_info(info, ctl, xn.shape[0])
+
+    def flow_adaptive(self, x: Tensor, t: float, tol: float = 1e-6, eps0: float = 0.01,
+                      eps_max: Optional[float] = None):
+        """`flow_adaptive_n` in the reference layout: -> (x flowed to t, info).  Not differentiable: the
+        differentiable flow (`flow_autograd`) stays fixed-step."""
+        self._no_grad(x, 'flow_adaptive')
+        xn, info = self.flow_adaptive_n(self.pack(x), t, tol, eps0, eps_max)
+        return self.unpack(xn), info
+
+    def flow_observables_adaptive(self, x: Tensor, ts, tol: float = 1e-6, eps0: float = 0.01,
+                                  eps_max: Optional[float] = None) -> dict:
+        """`flow_observables` on the adaptive flow: the observables at the increasing times ts, on each of which a step
+        lands.  't' [n+1], 'E', 'Eplaq', 'Q', 't2E' [n+1, nb] with row 0 at t = 0, and the info of `flow_adaptive_n`
+        ('eps', 'd', 'nsteps', 'nreject').  The step size is shared by the batch (see `flow_adaptive_n`)."""
+        self._no_grad(x, 'flow_observables_adaptive')
+        out, _ = self._flow_table(self.pack(x), self._flow_times(ts, 'flow_observables_adaptive'), tol, eps0, eps_max)
+        return out
+
+    def _flow_table(self, xn: Tensor, ts: list, tol: float, eps0: float, eps_max: Optional[float],
+                    kind: Optional[str] = None, target: float = 0.3):
+        """the table of `flow_observables_adaptive`; with `kind` the flow ends behind the first time at which
+        `scales_from_flow` of the rows so far has t0 and w0 for every chain.  -> (table, those scales or None)"""
+        ctl = ops.FlowStepController(tol, eps0, eps_max)
+        info = {'eps': [], 'd': []}
+        rows, scales = [self.clover_n(xn)], None
+        for k, cur in enumerate(self._flow_adaptive_iter(xn, ts, ctl, info), start=1):
+            rows.append(self.clover_n(cur))
+            if kind is not None and k + 1 >= 4:
+                tt = torch.tensor([0.0] + ts[:k], dtype=torch.float64, device=xn.device)
+                s = scales_from_flow(tt, torch.stack([getattr(r, kind) for r in rows]), target)
+                if not bool((torch.isnan(s['t0']) | torch.isnan(s['w0'])).any()):
+                    scales = s
+                    break
+        tt = torch.tensor([0.0] + ts[:len(rows) - 1], dtype=torch.float64, device=xn.device)
+        out = {'t': tt}
+        for name in Clover._fields:
+            out[name] = torch.stack([getattr(r, name) for r in rows])
+        out['t2E'] = tt[:, None] ** 2 * out['E']
+        out.update(self._flow_info(info, ctl, xn.shape[0]))
+        return out, scales
+
+    def flow_scales(self, x: Tensor, tmax: float, dt: float = 0.05, tol: float = 1e-6, kind: str = 'clover',
+                    target: float = 0.3) -> dict:
+        """t0 and w0 of every chain (`scales_from_flow`, lattice units): the adaptive flow measured on the grid
+        k dt, k = 0 .. round(tmax / dt), stopped as soon as both crossings of every chain are bracketed, else at
+        tmax.  kind = 'clover' or 'plaq' chooses the energy density.  -> {'t0', 'w0' [nb] (NaN: not reached before
+        tmax), 't_reached', 'table' (that of `flow_observables_adaptive` up to t_reached)}.  The early stop does not
+        change the answer: the same bits as `scales_from_flow` of the whole table to tmax on the same grid."""
+        self._no_grad(x, 'flow_scales')
+        if kind not in ('clover', 'plaq'):
+            raise ValueError(f"flow_scales: kind must be 'clover' or 'plaq', got {kind!r}")
+        tmax, dt = float(tmax), float(dt)
+        n = round(tmax / dt) if dt > 0 else 0
+        if n < 3 or abs(tmax / dt - n) > 1e-9:
+            raise ValueError(f'flow_scales: tmax / dt must be an integer >= 3, got tmax = {tmax}, dt = {dt}')
+        col = 'E' if kind == 'clover' else 'Eplaq'
+        table, s = self._flow_table(self.pack(x), [k * dt for k in range(1, n + 1)], tol, 0.01, None, col, target)
+        if s is None:
+            s = scales_from_flow(table['t'], table[col], target)
+        return {'t0': s['t0'], 'w0': s['w0'], 't_reached': float(table['t'][-1]), 'table': table}
 
     # ------------------------------------------------------------ Wilson loops R x T and Polyakov loops
     def wilson_loop_sums_n(self, xn: Tensor, rmax: int, tmax: int) -> Tensor:

@@ -63,6 +63,8 @@ SIGNATURES = {
     'l2q_su3_clover_reduce': (I, [P, I, I, I, I, I, P, P, Z, P]),
     'l2q_su3_flow_stage': (I, [P, P, D, D, P, P, I, I, I, I, I, P]),
     'l2q_su3_flow_step': (I, [P, P, P, P, D, I, I, I, I, I, P]),
+    'l2q_su3_flow_step_err_ws_bytes': (Z, [I, I, I, I, I]),
+    'l2q_su3_flow_step_err': (I, [P, P, P, P, D, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_line_extend': (I, [P, P, I, P, I, I, I, I, I, P]),
     'l2q_su3_loop_reduce': (I, [P, I, P, I, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_polyakov': (I, [P, I, P, I, I, I, I, I, P]),

@@ -141,7 +141,25 @@ def main():
     rec('  force_kick_to + expm_mul', timeit(two_launch), 3456)
     x3 = torch.empty_like(xn)
     rec('su3_flow_step (3 stages)', timeit(lambda: ops.su3_flow_step_n(xn, x2, p2, x3, 0.01, L)), 2880 + 2 * 3456)
-    del p2, x2, x3
+    # The step with its embedded error estimate: stages 1 and 2, the kick into P3 (1728 B) and ONE kernel that reads
+    # W0, W2, P1, P2, P3, writes W3 and reduces d (4 links x 864 B).  Next to it what that kernel replaces: the
+    # expm_mul for W3, the expm_mul for W' and a torch distance + amax (4 x 1296 B of algorithmic traffic), the two
+    # sides alternating so that each is repeated under the same conditions.
+    ws_p3 = torch.empty((3, *xn.shape), dtype=xn.dtype, device=dev)
+    x4 = torch.empty_like(xn)
+    ops.su3_flow_step_err_n(xn, x2, ws_p3, x3, 0.01, L)             # fills P1..P3 and W2 (x3) for the composition
+    pq = 17.0 * ws_p3[1] - ws_p3[0]
+
+    def composed():
+        ops.su3_expm_mul_n(x3, ws_p3[2], -17.0 / 36.0 * 0.01, out=x4)
+        ops.su3_expm_mul_n(xn, pq, 0.01 / 16.0, out=x2)
+        return torch.linalg.vector_norm(x4 - x2, dim=2).amax((1, 2)) / 9.0
+    for rnd in range(3):
+        rec(f'  2 x expm_mul + torch distance [{rnd}]', timeit(composed), 4 * 1296)
+        rec(f'su3_flow_step [{rnd}]', timeit(lambda: ops.su3_flow_step_n(xn, x2, p2, x4, 0.01, L)), 2880 + 2 * 3456)
+        rec(f'su3_flow_step_err [{rnd}]', timeit(lambda: ops.su3_flow_step_err_n(xn, x2, ws_p3, x3, 0.01, L)),
+            2880 + 3456 + 1728 + 3456)
+    del pq, x4, p2, x2, x3, ws_p3
     if a.flow_only:
         return
     rec('su3_plaq_reduce', timeit(lambda: ops.su3_plaq_sums_n(xn, L)), 576, 2800)
