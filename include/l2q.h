@@ -186,6 +186,10 @@ int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const flo
 int l2q_su3_expm_mul2_digits(const void* xn, const void* vn, double eps, const float* mask_n, int complement_first,
                              void* out, void* image, int a_exp, int nb, long V, void* stream);
 int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, long V, void* stream);
+/* l2q_su3_pack and l2q_su3_projsu_digits of its result from ONE read of the reference-layout field (a
+ * trajectory's entry): x_nat has the bits of l2q_su3_pack(x_ref), image the bytes of
+ * l2q_su3_projsu_digits(x_nat, nb * 4 fields).  V % 64 == 0 and 16-byte aligned pointers, as there. */
+int l2q_su3_pack_digits(const void* x_ref, void* x_nat, void* image, int a_exp, int nb, long V, void* stream);
 /* projectSU on every link (group/su3/pytorch/utils.py:341-346); out may alias in. */
 int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* stream);
 /* su3_to_vec(projectSU(.)) -> vec[nfields][8][V] double (group.py:138-147); the vnet

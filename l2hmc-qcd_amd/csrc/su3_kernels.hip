@@ -830,6 +830,38 @@ __global__ __launch_bounds__(kBlock) void su3_project_digits_kernel(const double
   m3_project_su_vec8(v, x);
   if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
 }
+// The trajectory's entry: reference layout x[f][site][9] -> the native planes (the bits of l2q_su3_pack) AND the
+// digits of vec8(projectSU(x)) (the bytes of su3_project_digits_kernel on those planes) from one read of x.  The
+// 64 links of a wavefront are 9216 contiguous bytes of x: read as nine lane-linear 16-byte loads, turned through
+// LDS (each wavefront its own 576 entries), after which lane <-> site holds its link as the other kernels do.
+// V % 64 == 0: whole wavefronts; one past the field (V % kBlock != 0) only waits at the barrier.
+__global__ __launch_bounds__(kBlock) void su3_pack_digits_kernel(const double2* __restrict__ xref,
+                                                                 double2* __restrict__ xn, char* __restrict__ image,
+                                                                 int V, long nblk, double dsc, double dlim, int* flag) {
+  __shared__ double2 tile[kBlock * 9];
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int s = (int)blk * kBlock + threadIdx.x;
+  const bool live = s < V;
+  double2* t = tile + w * 576;
+  if (live) {
+    const double2* src = xref + (f * V + (s - lane)) * 9L;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t[lane + 64 * k] = src[lane + 64 * k];
+  }
+  __syncthreads();
+  if (!live) return;
+  M3 x;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const double2 d = t[lane * 9 + e];
+    x.re[e] = d.x; x.im[e] = d.y;
+  }
+  store_link(xn + f * 9L * V, V, s, x);
+  double v[8];
+  m3_project_su_vec8(v, x);
+  if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
+}
 
 // out = op(a) * op(b) per link, op = identity or adjoint   (SU3.mul, group.py:56-69)
 __global__ __launch_bounds__(kBlock) void su3_mul_kernel(const double2* a, const double2* b,
@@ -1085,6 +1117,8 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
     snprintf(buf, buf_bytes, "su3_expm_mul_digits_kernel");
   } else if (!strcmp(entry, "l2q_su3_projsu_digits")) {
     snprintf(buf, buf_bytes, "su3_project_digits_kernel");
+  } else if (!strcmp(entry, "l2q_su3_pack_digits")) {
+    snprintf(buf, buf_bytes, "su3_pack_digits_kernel");
   } else if (!strcmp(entry, "l2q_gemm_f64")) {
     snprintf(buf, buf_bytes, "%s", gemm_f64_kernel_name());
   }
@@ -1294,6 +1328,26 @@ int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, 
                      (const double2*)in, (char*)image, (int)V, nblk, ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp),
                      flag);
   return check_launch("l2q_su3_projsu_digits");
+}
+
+int l2q_su3_pack_digits(const void* x_ref, void* x_nat, void* image, int a_exp, int nb, long V, void* stream) {
+  L2Q_REQUIRE(x_ref, L2Q_EINVAL, "null pointer: x_ref");
+  L2Q_REQUIRE(x_nat, L2Q_EINVAL, "null pointer: x_nat");
+  L2Q_REQUIRE(image, L2Q_EINVAL, "null pointer: image");
+  L2Q_REQUIRE(x_ref != x_nat, L2Q_EINVAL, "x_nat must not alias x_ref");
+  L2Q_REQUIRE(su3_field_ok(nb, V) && V % 64 == 0, L2Q_EINVAL, "V: the digit image serves V % 64 == 0");
+  L2Q_REQUIRE(a_exp > -900 && a_exp < 900, L2Q_EINVAL, "a_exp: bad operand exponent");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(x_ref) & 15) == 0, L2Q_ESHAPE, "x_ref must be 16-byte aligned");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(x_nat) & 15) == 0, L2Q_ESHAPE, "x_nat must be 16-byte aligned");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, L2Q_ESHAPE, "the image must be 16-byte aligned");
+  const long nblk = cdiv(V, kBlock);
+  L2Q_REQUIRE(nb * 4L * nblk <= 0x7fffffffL, L2Q_ESHAPE, "nb: grid too large");
+  int* flag = gs_flag();
+  L2Q_REQUIRE(flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
+  hipLaunchKernelGGL(su3_pack_digits_kernel, dim3((unsigned)(nb * 4L * nblk)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const double2*)x_ref, (double2*)x_nat, (char*)image, (int)V, nblk,
+                     ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp), flag);
+  return check_launch("l2q_su3_pack_digits");
 }
 
 int l2q_su3_project_su(const void* in, void* out, long nfields, long V, void* stream) {

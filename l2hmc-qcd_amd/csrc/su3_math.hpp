@@ -267,6 +267,9 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
 #ifndef L2Q_EXPM_EARLY_EXIT
 #define L2Q_EXPM_EARLY_EXIT 1
 #endif
+#ifndef L2Q_EXPM_TEST_EVERY
+#define L2Q_EXPM_TEST_EVERY 2
+#endif
   const double big = nrm < 0x1p59 ? 0x1p53 : HUGE_VAL;
 #ifdef L2Q_EXPM_COUNT_STEPS
   int steps = 0;
@@ -286,7 +289,9 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
 #ifdef L2Q_EXPM_COUNT_STEPS
     ++steps;
 #endif
-    if (L2Q_EXPM_EARLY_EXIT) {
+    // (tested after every second step, the first included -- a uniform branch on n skips the 12 instructions of
+    // the test on the others: an exit one step late adds a term that moves no sum, by the argument above)
+    if (L2Q_EXPM_EARLY_EXIT && (L2Q_EXPM_TEST_EVERY == 1 || (n & 1) == 0)) {
       const double tt = big * (((fabs(ar) + fabs(ai)) + (fabs(br) + fabs(bi))) + (fabs(cr) + fabs(ci)));
       if ((tt <= fabs(f0r)) & (tt <= fabs(f0i)) & (tt <= fabs(f1r)) & (tt <= fabs(f1i)) & (tt <= fabs(f2r)) &
           (tt <= fabs(f2i)))
@@ -322,6 +327,106 @@ __device__ __forceinline__ void m3_expm(M3& out, const M3& ain) {
 #define L2Q_FP_AS_WRITTEN
 #endif
 
+// The projection's transcendentals, reciprocals and roots on the ranges it calls them on (L2Q_RANGED_MATH 0: the
+// library calls, divisions and square roots as before -- A/B builds).
+#ifndef L2Q_RANGED_MATH
+#define L2Q_RANGED_MATH 1
+#endif
+
+// hardware estimates of 1 / x and x^(-1/2) (v_rcp_f64, v_rsq_f64: 2^29 ulp = 2^-23 relative; 0 -> inf, inf -> 0).  The
+// host build of the tests has no such instruction: the correctly rounded value cut to 24 bits stands in.
+__device__ __forceinline__ double m_cut24(double y) {
+  if (!(fabs(y) <= 1.7976931348623157e308) || y == 0.0) return y;
+  int ex;
+  const double f = frexp(y, &ex);
+  return ldexp((double)(long)(f * 16777216.0), ex - 24);
+}
+__device__ __forceinline__ double m_rcp_est(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcp(x);
+#else
+  return m_cut24(1.0 / x);
+#endif
+}
+__device__ __forceinline__ double m_rsq_est(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rsq(x);
+#else
+  return m_cut24(1.0 / sqrt(x));
+#endif
+}
+
+// 1 / x: three Newton steps on the estimate (relative error 2^-23 -> 2^-46 -> 2^-92, the third step is
+// the residual correction of a division: the result is the correctly rounded reciprocal or its neighbour).
+// x = 0, +-inf and NaN give what the division gives (the residual 1 - x y is NaN exactly there: 0 inf).
+__device__ __forceinline__ double m_rcp(double x) {
+  L2Q_FP_AS_WRITTEN
+  const double y0 = m_rcp_est(x);
+  const double e0 = fma(-x, y0, 1.0);
+  double y = fma(e0, y0, y0);
+  y = fma(fma(-x, y, 1.0), y, y);
+  y = fma(fma(-x, y, 1.0), y, y);
+  return e0 == e0 ? y : y0;
+}
+
+// g = sqrt(x), h = 1 / (2 sqrt(x)) for x >= 0: two coupled Newton steps on (x y, y / 2), y the estimate of
+// x^(-1/2) (2^-23 -> 2^-45 -> 2^-89), then the residual correction x - g^2 of the root.  x = 0: g = 0,
+// h = +inf, as sqrt and the division give (the estimate is inf there and 0 inf a NaN).
+__device__ __forceinline__ void m_sqrt_hrsq(double& g, double& h, double x) {
+  L2Q_FP_AS_WRITTEN
+  const double y = m_rsq_est(x);
+  double gg = x * y, hh = 0.5 * y;
+  double r = fma(-gg, hh, 0.5);
+  gg = fma(gg, r, gg); hh = fma(hh, r, hh);
+  r = fma(-gg, hh, 0.5);
+  gg = fma(gg, r, gg); hh = fma(hh, r, hh);
+  gg = fma(fma(-gg, gg, x), hh, gg);
+  const bool zero = x == 0.0;
+  g = zero ? 0.0 : gg;
+  h = zero ? HUGE_VAL : hh;
+}
+__device__ __forceinline__ double m_sqrt(double x) {
+#if L2Q_RANGED_MATH
+  double g, h;
+  m_sqrt_hrsq(g, h, x);
+  return g;
+#else
+  return sqrt(x);
+#endif
+}
+
+// sin t and cos t for |t| <= pi / 3 (both call sites: a third of an acos, a third of an atan2).  Above pi / 4
+// the argument is folded to u = pi / 2 - |t| in [pi / 6, pi / 4], held as uh + ul -- uh = pio2_hi - |t| is exact
+// (Sterbenz), ul the low word of pi / 2, entering both series to first order as in fdlibm's kernels -- and the two
+// series change places; no other reduction, no table, no integer work.  The series are the minimax polynomials of fdlibm's __kernel_sin / __kernel_cos on [-pi / 4, pi / 4]
+// (error below 2^-58 and 2^-57 relative to sin and cos), cos summed as w + ((1 - w) - z / 2 + z^2 (...)) with
+// w = 1 - z / 2 so that its leading terms round once: each result is within one ulp.
+__device__ __forceinline__ void m_sincos_third(double t, double& s, double& c) {
+  L2Q_FP_AS_WRITTEN
+  const double a = fabs(t);
+  const bool fold = a > 0.78539816339744828;
+  const double u = fold ? 1.57079632679489655800e+00 - a : a;
+  const double ul = fold ? 6.12323399573676603587e-17 : 0.0;
+  const double z = u * u;
+  double p = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+  p = fma(z, p, 2.75573137070700676789e-06);
+  p = fma(z, p, -1.98412698298579493134e-04);
+  p = fma(z, p, 8.33333333332248946124e-03);
+  p = fma(z, p, -1.66666666666666324348e-01);
+  const double hz = 0.5 * z;
+  const double w = 1.0 - hz;
+  const double su = u + fma(ul, w, (z * u) * p);     // sin(uh + ul) = sin uh + ul cos uh
+  double q = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+  q = fma(z, q, -2.75573143513906633035e-07);
+  q = fma(z, q, 2.48015872894767294178e-05);
+  q = fma(z, q, -1.38888888888741095749e-03);
+  q = fma(z, q, 4.16666666666666019037e-02);
+  const double cu = w + fma(-u, ul, fma(z * z, q, (1.0 - w) - hz));   // cos(uh + ul) = cos uh - ul sin uh
+  const double sa = fold ? cu : su;
+  s = copysign(sa, t);
+  c = fold ? su : cu;
+}
+
 // Closed-form eigenvalues of a 3x3 positive Hermitian matrix from (tr, tr(M^2), det).
 // utils.py:227-283 (same clamps: +-3e38 on 1/q^1.5, acos argument to +-(1 - 1e-12)).
 __device__ __forceinline__ void eigs3x3(double& e0, double& e1, double& e2, double tr, double p2,
@@ -332,16 +437,32 @@ __device__ __forceinline__ void eigs3x3(double& e0, double& e1, double& e2, doub
   const double tr32 = tr3 * tr3;
   const double q = fabs(0.5 * (p23 - tr32));
   const double r = fma(0.25 * tr3, fma(5.0, tr32, -p2), -(0.5 * det));
+#if L2Q_RANGED_MATH
+  // sqrt(q) and 1 / (q sqrt(q)) from one reciprocal root: (2 h)^3 is within a few ulp of 1 / sq3, one Newton step on
+  // sq3 itself takes it to the neighbourhood of the quotient (q = 0, a degenerate spectrum: +inf, clamped below)
+  double sq, hq;
+  m_sqrt_hrsq(sq, hq, q);
+  const double sq3 = q * sq;
+  const double iq = hq + hq;
+  double isq3 = iq * iq * iq;
+  const double eq = fma(-sq3, isq3, 1.0);
+  isq3 = eq == eq ? fma(eq, isq3, isq3) : isq3;
+#else
   const double sq = sqrt(q);
   const double sq3 = q * sq;
   double isq3 = 1.0 / sq3;
+#endif
   isq3 = fmin(3e38, fmax(-3e38, isq3));
   double rsq3 = r * isq3;
   rsq3 = fmin(1.0, fmax(-1.0, rsq3));
   rsq3 = fmin(1.0 - 1e-12, fmax(-1.0 + 1e-12, rsq3));
   const double t = (1.0 / 3.0) * acos(rsq3);
   double st, ct;
+#if L2Q_RANGED_MATH
+  m_sincos_third(t, st, ct);                         // t in [0, pi / 3]
+#else
   sincos(t, &st, &ct);
+#endif
   const double sqc = sq * ct;
   const double sqs = 1.7320508075688772 * sq * st;
   const double ll = tr3 + sqc;
@@ -430,11 +551,11 @@ __device__ __forceinline__ void h3_rsqrt_gram(H3& r, const M3& x) {
   const double det = h3_det(t);
   double e0, e1, e2;
   eigs3x3(e0, e1, e2, tr, p2, det);
-  const double se0 = sqrt(fabs(e0)), se1 = sqrt(fabs(e1)), se2 = sqrt(fabs(e2));
+  const double se0 = m_sqrt(fabs(e0)), se1 = m_sqrt(fabs(e1)), se2 = m_sqrt(fabs(e2));
   const double u = se0 + se1 + se2;
   const double w = se0 * se1 * se2;
   const double d = w * (se0 + se1) * (se0 + se2) * (se1 + se2);
-  const double di = 1.0 / d;
+  const double di = L2Q_RANGED_MATH ? m_rcp(d) : 1.0 / d;
   const double c0 = di * fma(e2 * se2, e0 + e1, fma(e1 * se1, e0 + e2, fma(e0 * se0, e1 + e2, w * u * u)));
   const double c1 = -fma(tr, u, w) * di;
   const double c2 = u * di;
@@ -500,7 +621,11 @@ __device__ __forceinline__ void m3_project_su(M3& out, const M3& x) {
   m3_det(detr, deti, m);
   const double p = (-1.0 / 3.0) * atan2(deti, detr);
   double sp, cp;
+#if L2Q_RANGED_MATH
+  m_sincos_third(p, sp, cp);                         // |p| <= pi / 3
+#else
   sincos(p, &sp, &cp);
+#endif
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     out.re[i] = m.re[i] * cp - m.im[i] * sp;
@@ -523,7 +648,11 @@ __device__ __forceinline__ void m3_project_su_vec8(double v[8], const M3& x) {
   m3_det_as_written(detr, deti, x);
   const double p = (-1.0 / 3.0) * atan2(deti, detr);
   double sp, cp;
+#if L2Q_RANGED_MATH
+  m_sincos_third(p, sp, cp);                         // |p| <= pi / 3
+#else
   sincos(p, &sp, &cp);
+#endif
   double mr[3], mi[3], dr[3], dim[3];
 #pragma unroll
   for (int o = 0; o < 3; ++o) m3_mul_h3_entry(mr[o], mi[o], x, r, o == 2 ? 1 : 0, o == 0 ? 1 : 2);

@@ -665,6 +665,20 @@ def su3_projsu_digits_n(xn: torch.Tensor, a_exp: int = SLICED_INPUT_EXP) -> Opti
     return DigitImage(buf, nb, 32 * V, int(a_exp))
 
 
+def su3_pack_digits(x: torch.Tensor, a_exp: int = SLICED_INPUT_EXP):
+    """(su3_pack(x), su3_projsu_digits_n(su3_pack(x))) from one read of x: the same bits and bytes.  None when
+    the lattice does not qualify (nothing is launched)."""
+    nb = x.shape[0]
+    x = x.to(C128).contiguous()
+    V = x.numel() // (nb * 36)
+    if not digits_ok(nb, V):
+        return None
+    out = torch.empty((nb, 4, 9, V), dtype=C128, device=x.device)
+    buf = _digit_buf(nb, 32 * V, x.device)
+    N.call('l2q_su3_pack_digits', x, out, buf, int(a_exp), nb, V)
+    return out, DigitImage(buf, nb, 32 * V, int(a_exp))
+
+
 def su3_expm_mul2_digits_n(xn: torch.Tensor, vn: torch.Tensor, eps: float, mask_n: torch.Tensor,
                            complement_first: bool, out: Optional[torch.Tensor] = None,
                            a_exp: int = SLICED_INPUT_EXP):

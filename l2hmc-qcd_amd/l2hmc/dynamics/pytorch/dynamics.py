@@ -207,6 +207,7 @@ class Dynamics(nn.Module):
         self.reuse_v_inputs = True  # force / vec8 / hidden activation once per distinct x
         self.pair_v_updates = True  # adjacent v-updates on the same x in one heads kernel
         self.fuse_x_vec8 = True     # SU3: the x-update also emits the next vnet input vec8(x')
+        self.fuse_entry_digits = True   # SU3: the pack of a trajectory's input also emits its digit image
         self.fuse_u1_steps = True   # U1 (small lattices, dense nets): one kernel per sub-update
         # Improved gauge action (c1 != 0): the reference evaluates H with potential_fn (the
         # Trainer's LatticeSU3(c1), trainers/pytorch/trainer.py:499-504) but takes the leapfrog
@@ -491,6 +492,19 @@ class Dynamics(nn.Module):
                 and self.cache_native_output):
             return c[2]
         return self._pack(x)
+
+    def _pack_input_digits(self, x: Tensor, st0: int):
+        """(_pack_input(x), the digit image of its vnet input or None).  The image comes out of the pack itself
+        (ops.su3_pack_digits: one read of x) exactly when the trajectory's first v-update, on the network of step
+        `st0`, is going to ask for it; everywhere else (fp64 network inputs, U(1), training, injected draws, a
+        native-output cache entry to consult, nothing kept per x) the projection stays the trajectory's own pass."""
+        if (self.fuse_entry_digits and self.group == 'SU3' and self._networks_built and self._inject is None
+                and self.reuse_v_inputs and self.config.nleapfrog > 0 and self._xcache is None
+                and self._digit_inputs(self._get_vnet(st0), x.shape[0], self.volume)):
+            got = ops.su3_pack_digits(x.to(DEVICE).reshape(x.shape[0], -1))
+            if got is not None:
+                return got
+        return self._pack_input(x), None
 
     def _unpack(self, an: Tensor) -> Tensor:
         if self.group == 'SU3':
@@ -978,14 +992,15 @@ class Dynamics(nn.Module):
             history = self._stack_history(history)
         return x_, v_, history
 
-    def _kernel_fb_n(self, xn, vn, beta):
-        """Merged forward + backward trajectory (dynamics.py:956-1029)."""
-        return run_trajectory(self, SamplerStepper(self, beta, True), xn, vn, beta, (True, False))[:3]
+    def _kernel_fb_n(self, xn, vn, beta, xv=None):
+        """Merged forward + backward trajectory (dynamics.py:956-1029).  `xv`: the vnet input of xn, where the
+        entry made it (`_pack_input_digits`)."""
+        return run_trajectory(self, SamplerStepper(self, beta, True, xv), xn, vn, beta, (True, False))[:3]
 
-    def _kernel_n(self, xn, vn, beta, forward: bool):
+    def _kernel_n(self, xn, vn, beta, forward: bool, xv=None):
         """Single-direction kernel (dynamics.py:1031-1063), including the reference's swapped
         arguments to compute_accept_prob."""
-        return run_trajectory(self, SamplerStepper(self, beta, False), xn, vn, beta, (forward,))[:3]
+        return run_trajectory(self, SamplerStepper(self, beta, False, xv), xn, vn, beta, (forward,))[:3]
 
     # ---- reference-shaped wrappers
     def _state_n(self, state: State):
@@ -1260,17 +1275,17 @@ class Dynamics(nn.Module):
         hit = self._auto_graphed('fb', x, beta)
         if hit is not None:
             return hit
-        xn = self._pack_input(x)
+        xn, xv = self._pack_input_digits(x, 0)
         vn = self._momentum_n(xn.shape[0])
-        x_, v_, hist = self._kernel_fb_n(xn, vn, beta)
+        x_, v_, hist = self._kernel_fb_n(xn, vn, beta, xv)
         return self._finish(xn, vn, x_, v_, beta, hist, with_sumlogdet=True)
 
     def apply_transition(self, inputs: tuple[Tensor, Tensor]) -> tuple[Tensor, dict]:
         x, beta = inputs
         forward = bool(torch.rand(1) > 0.5)
-        xn = self._pack_input(x)
+        xn, xv = self._pack_input_digits(x, 0 if forward else self.config.nleapfrog - 1)
         vn = self._momentum_n(xn.shape[0])
-        x_, v_, hist = self._kernel_n(xn, vn, beta, forward)
+        x_, v_, hist = self._kernel_n(xn, vn, beta, forward, xv)
         return self._finish(xn, vn, x_, v_, beta, hist, with_sumlogdet=True)
 
     def apply_transition_both(self, inputs: tuple[Tensor, Tensor]) -> tuple[Tensor, dict]:

@@ -119,9 +119,11 @@ class SamplerStepper:
     __slots__ = ('dyn', 'beta', 'reuse', 'defer', 'late', 'lazy', 'x_src', 'v_src', 'inputs',
                  'pending', 'flipped', 'ld1', 'ke', 'energies', 'ke_out')
 
-    def __init__(self, dyn, beta, merged: bool):
+    def __init__(self, dyn, beta, merged: bool, xv=None):
+        """`xv`: the vnet input of the trajectory's first x (or its digit image), where the entry emitted it"""
         verbose, su3 = dyn.config.verbose, dyn.group == 'SU3' and dyn._networks_built
         self.dyn, self.beta, self.inputs = dyn, beta, VInputs(dyn, beta)
+        self.inputs.x_changed(xv)
         self.reuse = bool(dyn.reuse_v_inputs)
         # (the single-direction kernel neither pairs its v-updates nor reads its input in place)
         can_pair = merged and su3 and self.reuse and dyn.pair_v_updates

@@ -51,6 +51,7 @@ SIGNATURES = {
     'l2q_su3_expm_mul2_vec8': (I, [P, P, D, P, I, P, P, I, L, P]),
     'l2q_su3_expm_mul2_digits': (I, [P, P, D, P, I, P, P, I, I, L, P]),
     'l2q_su3_projsu_digits': (I, [P, P, I, L, L, P]),
+    'l2q_su3_pack_digits': (I, [P, P, P, I, I, L, P]),
     'l2q_su3_project_su': (I, [P, P, L, L, P]),
     'l2q_su3_projsu_vec8': (I, [P, P, L, L, P]),
     'l2q_su3_project_tah': (I, [P, P, L, L, P]),
