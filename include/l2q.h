@@ -319,6 +319,39 @@ int l2q_su3_heatbath(void* xn, double beta, int mu, int parity, const double* u,
                      int T, int X, int Y, int Z, void* ws, size_t ws_bytes, void* stream);
 int l2q_su3_overrelax(void* xn, int mu, int parity, int nb, int T, int X, int Y, int Z, void* stream);
 
+/* ---------------------------------------------------------------- SU(3) Landau and Coulomb gauge fixing */
+/* Gauge directions D: a 4-bit set `dirmask` (bit mu = direction mu) in 1..15 with at least two bits set; Landau gauge is
+ * 15, Coulomb gauge with time direction t is 15 & ~(1 << t).  A gauge transformation acts in all four directions
+ * whatever D is: U_mu(x) -> g(x) U_mu(x) g(x+mu)^H.  Per chain:
+ *   functional (maximised)  F = (1 / (3 |D| V)) sum_x sum_{mu in D} Re tr U_mu(x)
+ *   residual                theta = (1 / (3 V)) sum_x tr Delta(x) Delta(x)^H,
+ *                           Delta(x) = sum_{mu in D} [A_mu(x) - A_mu(x-mu)],  A_mu(x) = (U - U^H) / (2i) - tr(.) / 3
+ * (conventions of Giusti et al., hep-lat/0104012).
+ * Local step at a site x (Los Alamos iteration with overrelaxation; SU(3) through the SU(2) subgroups and the
+ * quaternion / embed conventions of the heatbath above):  K(x) = sum_{mu in D} [U_mu(x) + U_mu(x-mu)^H], g = 1, W = K;
+ * for (i, j) = (0,1), (0,2), (1,2): r from W as above, k = |r|, rh = r / k; k zero or not finite: the subgroup step
+ * is the identity; else a = conj(rh) = (cos phi, n sin phi) with phi = atan2(|a_vec|, a0) in [0, pi], the step is the
+ * exact power a^omega = (cos(omega phi), n sin(omega phi)) (a_vec = 0: the identity), g <- embed(a^omega) g,
+ * W <- embed(a^omega) W.  Then for all four mu: U_mu(x) <- g U_mu(x), U_mu(x-mu) <- U_mu(x-mu) g^H.  For omega in
+ * [1, 2) every subgroup step has Re tr(a^omega W) >= Re tr W: F cannot decrease.
+ * l2q_su3_gaugefix_sweep does that step, IN PLACE, at the sites with (t + x + y + z) & 1 == parity (half-site order as
+ * the heatbath).  All four extents must be even (L2Q_ESHAPE): each link then has one end on each parity, so one launch
+ * rewrites every link of the field exactly once and reads only links that the same thread rewrites -- also at extent
+ * 2, where x+mu and x-mu are one site but U_mu(x) and U_mu(x-mu) two links.  One sweep is parity 0, then parity 1.
+ * gn (may be NULL): the accumulated transformation G[nb][9][V] complex128, one matrix per site, component-major as a
+ * link; with it G(x) <- g G(x).  active (may be NULL): int32 [nb] on the device; a chain with active[c] == 0 is not
+ * touched at all.  omega must be finite and in [1, 2) (L2Q_EINVAL).  Algorithmic traffic per launch: the field read
+ * and written once (8 links x 144 B each way per half-site), 144 B each way more with gn. */
+int l2q_su3_gaugefix_sweep(void* xn, void* gn, const int* active, int dirmask, int parity, double omega, int nb,
+                           int T, int X, int Y, int Z, void* stream);
+/* out[nb][2] = (F, theta) of each chain, any extents.  Two-stage reduction in a fixed order: ws >= nb * ceil(V/256) * 2
+ * doubles (l2q_reduce_ws_bytes(nb, V) covers it; L2Q_ESHAPE).  A chain's values do not depend on the batch. */
+int l2q_su3_gauge_condition(const void* xn, int dirmask, double* out, int nb, int T, int X, int Y, int Z, void* ws,
+                            size_t ws_bytes, void* stream);
+/* out_mu(x) = G(x) U_mu(x) G(x+mu)^H for all four mu, gn = G[nb][9][V] as above; any extents; out must alias neither
+ * xn nor gn (L2Q_EINVAL). */
+int l2q_su3_gauge_apply(const void* xn, const void* gn, void* out, int nb, int T, int X, int Y, int Z, void* stream);
+
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:
  *   forward : v' = exp(eps s/2) v - (eps/2) (F exp(eps q) + t),  logdet[c] =  sum eps s/2

@@ -16,33 +16,11 @@
 // not unrolled (live set: the sum, one product and two operands); the coordinates come by division as in
 // su3_loops.hip.  The kernel holds no generator: the uniforms are an input, u[chain][subgroup][4 ntry + 2][V/2].
 #include "su3_launch.hpp"
+#include "su3_subgroup.hpp"
 
 namespace l2q {
 
 constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-// periodic neighbour of site s in a direction of stride st and extent ext; dir = +1 / -1
-__device__ __forceinline__ int hb_hop(int s, int st, int ext, int dir) {
-  const int c = (s / st) % ext;
-  if (dir > 0) return c + 1 == ext ? s - (ext - 1) * st : s + st;
-  return c == 0 ? s + (ext - 1) * st : s - st;
-}
-
-struct Quat {
-  double q0, q1, q2, q3;
-};
-
-// the product of the 2 x 2 matrices that a and b stand for
-__device__ __forceinline__ Quat q_mul(const Quat& a, const Quat& b) {
-  Quat c;
-  c.q0 = a.q0 * b.q0 - a.q1 * b.q1 - a.q2 * b.q2 - a.q3 * b.q3;
-  c.q1 = a.q0 * b.q1 + a.q1 * b.q0 - (a.q2 * b.q3 - a.q3 * b.q2);
-  c.q2 = a.q0 * b.q2 + a.q2 * b.q0 - (a.q3 * b.q1 - a.q1 * b.q3);
-  c.q3 = a.q0 * b.q3 + a.q3 * b.q0 - (a.q1 * b.q2 - a.q2 * b.q1);
-  return c;
-}
-
-__device__ __forceinline__ Quat q_conj(const Quat& a) { return Quat{a.q0, -a.q1, -a.q2, -a.q3}; }
 
 // entry (R, C) of U A
 template <int R, int C>

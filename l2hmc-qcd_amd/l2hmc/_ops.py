@@ -468,6 +468,42 @@ def su3_overrelax_(xn: torch.Tensor, mu: int, parity: int, lat: Sequence[int]) -
     return xn
 
 
+def su3_gaugefix_sweep_(xn: torch.Tensor, parity: int, dirmask: int, omega: float, lat: Sequence[int],
+                        gn: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One overrelaxed Los Alamos gauge-fixing step at the sites of one parity, IN PLACE in the native field xn (every
+    link is rewritten once; see l2q.h).  dirmask: the gauge directions as a 4-bit set.  gn [nb, 9, V] complex128, when
+    given, accumulates the transformation in place; active int32 [nb], when given, freezes the chains that hold 0."""
+    nb, V = xn.shape[0], xn.shape[-1]
+    T, X, Y, Z = (int(i) for i in lat)
+    if gn is not None and (gn.dtype != C128 or tuple(gn.shape) != (nb, 9, V)):
+        raise ValueError(f'su3_gaugefix_sweep_: gn must be complex128 [{nb}, 9, {V}], got {gn.dtype} {list(gn.shape)}')
+    if active is not None and (active.dtype != torch.int32 or tuple(active.shape) != (nb,)):
+        raise ValueError(f'su3_gaugefix_sweep_: active must be int32 [{nb}], got {active.dtype} {list(active.shape)}')
+    N.call('l2q_su3_gaugefix_sweep', xn, gn, active, int(dirmask), int(parity), float(omega), nb, T, X, Y, Z)
+    return xn
+
+
+def su3_gauge_condition_n(xn: torch.Tensor, dirmask: int, lat: Sequence[int]) -> torch.Tensor:
+    """[nb, 2] float64: the gauge functional F and the residual theta of each chain for the directions in dirmask"""
+    nb = xn.shape[0]
+    T, X, Y, Z = (int(i) for i in lat)
+    out = torch.empty((nb, 2), dtype=torch.float64, device=xn.device)
+    ws = _ws(nb, T * X * Y * Z, xn.device)
+    N.call('l2q_su3_gauge_condition', xn, int(dirmask), out, nb, T, X, Y, Z, ws, ws.numel())
+    return out
+
+
+def su3_gauge_apply_n(xn: torch.Tensor, gn: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
+    """a new native field g(x) U_mu(x) g(x+mu)^H from gn [nb, 9, V] complex128"""
+    nb, V = xn.shape[0], xn.shape[-1]
+    T, X, Y, Z = (int(i) for i in lat)
+    if gn.dtype != C128 or tuple(gn.shape) != (nb, 9, V):
+        raise ValueError(f'su3_gauge_apply_n: gn must be complex128 [{nb}, 9, {V}], got {gn.dtype} {list(gn.shape)}')
+    out = torch.empty_like(xn)
+    N.call('l2q_su3_gauge_apply', xn, gn, out, nb, T, X, Y, Z)
+    return out
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

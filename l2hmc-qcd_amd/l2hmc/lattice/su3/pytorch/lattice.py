@@ -59,6 +59,19 @@ class Clover(NamedTuple):
     Eplaq: Tensor
 
 
+class GaugeCondition(NamedTuple):
+    """Per-chain gauge functional ``F = (1 / (3 |D| V)) sum_x sum_{mu in D} Re tr U_mu(x)`` and residual ``theta =
+    (1 / (3 V)) sum_x tr Delta Delta^H`` of the gauge directions D, [nb] float64 each (`l2q_su3_gauge_condition`)."""
+    F: Tensor
+    theta: Tensor
+
+
+# the overrelaxation parameter of `LatticeSU3.gauge_fix` when none is given: of {1.0, 1.3, 1.5, 1.7, 1.9} the one
+# with the fewest sweeps to theta <= 1e-12 on thermalised 8^4 chains at beta = 6, in Landau and in Coulomb gauge
+# (profiles/su3_gaugefix.md)
+GAUGEFIX_OMEGA = 1.7
+
+
 def _site_sum(w: Tensor) -> Tensor:
     """the reference's reduction of a trace field [nplanes, nb, T, X, Y, Z] to [nb] (lattice.py:209, 228)"""
     return w.sum(tuple(range(2, len(w.shape)))).sum(0)
@@ -546,6 +559,120 @@ class LatticeSU3(Lattice):
         self._local_update_checks(x, 'overrelax', nsweeps)
         xn = self.overrelax_n(self.pack(x), nsweeps)
         return AG.attach_native(self.unpack(xn), xn)
+
+    # ------------------------------------------------------------ Landau and Coulomb gauge fixing
+    @staticmethod
+    def _gauge_dirmask(gauge: str, time_dir: int, what: str) -> int:
+        """the gauge directions as the 4-bit set of l2q.h: all four (Landau), all but time_dir (Coulomb)"""
+        if gauge not in ('landau', 'coulomb'):
+            raise ValueError(f"LatticeSU3.{what}: gauge must be 'landau' or 'coulomb', got {gauge!r}")
+        if isinstance(time_dir, bool) or int(time_dir) != time_dir or not 0 <= int(time_dir) < 4:
+            raise ValueError(f'LatticeSU3.{what}: time_dir must be 0..3, got {time_dir!r}')
+        return 15 if gauge == 'landau' else 15 & ~(1 << int(time_dir))
+
+    def _gauge_fix_checks(self, x: Tensor, gauge, time_dir, omega, tol, max_sweeps, check_every) -> tuple[int, float]:
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError('LatticeSU3.gauge_fix: no autograd through gauge fixing')
+        mask = self._gauge_dirmask(gauge, time_dir, 'gauge_fix')
+        if any(int(n) % 2 for n in self._lattice_shape):
+            raise ValueError('LatticeSU3.gauge_fix: the checkerboard needs even extents, got '
+                             f'{list(self._lattice_shape)}')
+        omega = GAUGEFIX_OMEGA if omega is None else float(omega)
+        if not 1.0 <= omega < 2.0:
+            raise ValueError(f'LatticeSU3.gauge_fix: omega must be in [1, 2), got {omega}')
+        if not float(tol) > 0:
+            raise ValueError(f'LatticeSU3.gauge_fix: tol must be positive, got {tol}')
+        if int(check_every) < 1 or int(max_sweeps) < 0:
+            raise ValueError(f'LatticeSU3.gauge_fix: need check_every >= 1 and max_sweeps >= 0, got {check_every}, '
+                             f'{max_sweeps}')
+        return mask, omega
+
+    def _g_to_native(self, g: Tensor) -> Tensor:
+        """g[nb, T, X, Y, Z, 3, 3] -> gn[nb, 9, V]"""
+        nb = g.shape[0]
+        g = g.to(DEVICE).to(torch.complex128)
+        return ops.transpose(g.reshape(nb, self.volume, 9), nb, self.volume, 9).reshape(nb, 9, self.volume)
+
+    def _g_from_native(self, gn: Tensor) -> Tensor:
+        nb = gn.shape[0]
+        return ops.transpose(gn, nb, 9, self.volume).reshape(nb, *self._lattice_shape, 3, 3)
+
+    def gauge_fix_n(self, xn: Tensor, gauge: str = 'landau', time_dir: int = 0, omega: Optional[float] = None,
+                    tol: float = 1e-12, max_sweeps: int = 10000, check_every: int = 10, reunitarize: bool = True,
+                    return_transform: bool = False) -> tuple[Tensor, dict]:
+        """Landau (`gauge='landau'`) or Coulomb (`'coulomb'`, all directions but `time_dir`) gauge fixing of a native
+        field by overrelaxed Los Alamos sweeps (`l2q_su3_gaugefix_sweep`, parity 0 then parity 1): maximises the
+        functional F until the residual theta <= tol (definitions: include/l2q.h).  Returns (a new field, info); xn is
+        never written.  Every `check_every` sweeps one device read of theta[nb]; a chain with theta <= tol is frozen
+        from then on, so its result and its sweep count do not depend on its batch mates.  The loop ends when every
+        chain is frozen or after `max_sweeps` sweeps; a chain that did not get there shows in info['converged'], nothing
+        raises.  A chain that satisfies tol at the start gets no sweep and comes back bit-identical (before
+        `reunitarize`, one `l2q_su3_project_su` at the end).  omega in [1, 2), None = GAUGEFIX_OMEGA.
+        info: 'theta', 'functional' (of the returned field), 'sweeps' (int64), 'converged' (bool), 'theta0',
+        'functional0' (before the first sweep), each [nb]; with return_transform 'g' [nb, T, X, Y, Z, 3, 3], the
+        transformation that `gauge_transform` applies (to the input: the result before `reunitarize`)."""
+        mask, omega = self._gauge_fix_checks(xn, gauge, time_dir, omega, tol, max_sweeps, check_every)
+        tol, max_sweeps, check_every = float(tol), int(max_sweeps), int(check_every)
+        L = self._lattice_shape
+        xn = xn.detach().clone()
+        nb, dev = xn.shape[0], xn.device
+        gn = None
+        if return_transform:
+            gn = torch.zeros((nb, 9, self.volume), dtype=torch.complex128, device=dev)
+            gn[:, 0::4] = 1.0
+        cond0 = ops.su3_gauge_condition_n(xn, mask, L).cpu()
+        cond = cond0.clone()
+        live = ~(cond[:, 1] <= tol)                         # (a theta that is not a number stays live, and unconverged)
+        sweeps = torch.zeros(nb, dtype=torch.int64)
+        done = 0
+        while bool(live.any()) and done < max_sweeps:
+            n = min(check_every, max_sweeps - done)
+            active = live.to(torch.int32).to(dev)
+            for _ in range(n):
+                for parity in (0, 1):
+                    ops.su3_gaugefix_sweep_(xn, parity, mask, omega, L, gn, active)
+            done += n
+            sweeps[live] += n
+            cond = ops.su3_gauge_condition_n(xn, mask, L).cpu()     # frozen chains: untouched, the same bits again
+            live = live & ~(cond[:, 1] <= tol)
+        converged = ~live
+        if reunitarize:
+            xn = ops.su3_project_su_n(xn)
+            cond = ops.su3_gauge_condition_n(xn, mask, L).cpu()
+        info = {'theta': cond[:, 1].to(dev), 'functional': cond[:, 0].to(dev), 'sweeps': sweeps.to(dev),
+                'converged': converged.to(dev), 'theta0': cond0[:, 1].to(dev), 'functional0': cond0[:, 0].to(dev)}
+        if return_transform:
+            info['g'] = self._g_from_native(gn)
+        return xn, info
+
+    def gauge_fix(self, x: Tensor, gauge: str = 'landau', time_dir: int = 0, omega: Optional[float] = None,
+                  tol: float = 1e-12, max_sweeps: int = 10000, check_every: int = 10, reunitarize: bool = True,
+                  return_transform: bool = False) -> tuple[Tensor, dict]:
+        """`gauge_fix_n` in the reference layout: (x_fixed, info); x is never written."""
+        self._gauge_fix_checks(x, gauge, time_dir, omega, tol, max_sweeps, check_every)
+        xn, info = self.gauge_fix_n(self.pack(x), gauge, time_dir, omega, tol, max_sweeps, check_every, reunitarize,
+                                    return_transform)
+        return AG.attach_native(self.unpack(xn), xn), info
+
+    def gauge_condition(self, x: Tensor, gauge: str = 'landau', time_dir: int = 0) -> GaugeCondition:
+        """The gauge functional F and the residual theta of x, [nb] float64 each (`l2q_su3_gauge_condition`; any
+        extents)."""
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError('LatticeSU3.gauge_condition: no autograd through the gauge condition')
+        mask = self._gauge_dirmask(gauge, time_dir, 'gauge_condition')
+        c = ops.su3_gauge_condition_n(self.pack(x), mask, self._lattice_shape)
+        return GaugeCondition(F=c[:, 0].contiguous(), theta=c[:, 1].contiguous())
+
+    def gauge_transform(self, x: Tensor, g: Tensor) -> Tensor:
+        """U_mu(x) -> g(x) U_mu(x) g(x+mu)^H for g[nb, T, X, Y, Z, 3, 3] (`l2q_su3_gauge_apply`; any extents); a new
+        tensor."""
+        if any(isinstance(a, torch.Tensor) and a.requires_grad for a in (x, g)):
+            raise ValueError('LatticeSU3.gauge_transform: no autograd through a gauge transformation')
+        want = (x.shape[0], *[int(n) for n in self._lattice_shape], 3, 3)
+        if tuple(g.shape) != want:
+            raise ValueError(f'LatticeSU3.gauge_transform: g must be {list(want)}, got {list(g.shape)}')
+        yn = ops.su3_gauge_apply_n(self.pack(x), self._g_to_native(g), self._lattice_shape)
+        return AG.attach_native(self.unpack(yn), yn)
 
     # ------------------------------------------------------------ reference API
     def coeffs(self, beta: Tensor) -> dict[str, Tensor]:
