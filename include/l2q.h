@@ -151,7 +151,17 @@ int l2q_su3_force(const void* xn, double beta, void* fn, int nb, int T, int X, i
 size_t l2q_su3_force_action_ws_bytes(int nb, int T, int X, int Y, int Z);
 int l2q_su3_force_action(const void* xn, double beta, void* fn, double* plaq, int nb, int T, int X, int Y, int Z,
                          void* ws, size_t ws_bytes, void* stream);
-/* fused plain-HMC half-kick: v += coef * F(x)   (dynamics/pytorch/dynamics.py:903-911,
+/* The two calls above with an UPPER-PLANE output.  F is anti-Hermitian, plane (j, i) of a link is (-re, im) of plane
+ * (i, j): fu [nb][4][6][V] holds planes e = 0, 4, 8 (the diagonal), 1, 2, 5 (i < j) of the native [nb][4][9][V]
+ * field -- the same bits, signed zero on the real diagonal included -- and the other three are neither formed nor
+ * stored (960 instead of 1152 B per (chain, site) with the read of x).  plaq keeps its bits.  An output form of the
+ * thread-per-link kernel alone: L2Q_ESHAPE, nothing launched, where another force kernel serves the lattice (or
+ * force_tile selects one) -- l2q_kernel_name answers "" there -- and the caller keeps the full field.  Consumers:
+ * l2q_su3_projsu_digits_upper, l2q_vnet_heads_vupdate_sliced_upper_f64. */
+int l2q_su3_force_upper(const void* xn, double beta, void* fu, int nb, int T, int X, int Y, int Z, void* stream);
+int l2q_su3_force_action_upper(const void* xn, double beta, void* fu, double* plaq, int nb, int T, int X, int Y,
+                               int Z, void* ws, size_t ws_bytes, void* stream);
+/* fused plain-HMC half-kick: v += coef * F(x)  (dynamics/pytorch/dynamics.py:903-911,
  * coef = -eps/2); F is never materialised. */
 int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int nb, int T,
                        int X, int Y, int Z, void* stream);
@@ -186,6 +196,10 @@ int l2q_su3_expm_mul2_vec8(const void* xn, const void* vn, double eps, const flo
 int l2q_su3_expm_mul2_digits(const void* xn, const void* vn, double eps, const float* mask_n, int complement_first,
                              void* out, void* image, int a_exp, int nb, long V, void* stream);
 int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, long V, void* stream);
+/* l2q_su3_projsu_digits of an anti-Hermitian field given in upper-plane form, in[nfields][6][V]
+ * (l2q_su3_force_upper): the three planes that are not stored are rebuilt in registers (a zero keeps the sign the
+ * force kernel writes); the image bytes and the out-of-range flag are those of the full field. */
+int l2q_su3_projsu_digits_upper(const void* in, void* image, int a_exp, long nfields, long V, void* stream);
 /* l2q_su3_pack and l2q_su3_projsu_digits of its result from ONE read of the reference-layout field (a
  * trajectory's entry): x_nat has the bits of l2q_su3_pack(x_ref), image the bytes of
  * l2q_su3_projsu_digits(x_nat, nb * 4 fields).  V % 64 == 0 and 16-byte aligned pointers, as there. */
@@ -501,6 +515,19 @@ int l2q_vnet_heads_vupdate_sliced_f64(const double* Z, int M, int K, long N, con
                                       int forward1, int pair, int flip_between, double eps2, int forward2,
                                       double* logdet, double* logdet1, double* vnorm2_mid, void* ws,
                                       size_t ws_bytes, void* stream);
+/* The same call with one more property of `force`.  force_upper = 1: force is an upper-plane SU(3) force
+ * [M][4][6][V] (l2q_su3_force_upper) instead of the full [M][N] field; needs is_complex, N = 36 V, V % 64 == 0 and
+ * M * 192 * V < 2^32.  The kernel reads the three planes that are not stored from their transposes' planes and
+ * flips the sign of the real part: the results are those of the full field bit for bit, except that a real part
+ * that is an exact zero off the diagonal enters as the other zero (visible only where the t head is an exact zero
+ * as well).  force_upper = 0: l2q_vnet_heads_vupdate_sliced_f64 itself (V is not read). */
+int l2q_vnet_heads_vupdate_sliced_upper_f64(const double* Z, int M, int K, long N, const void* sliced,
+                                            const double* bs, const double* cs, double scale_s, const double* bt,
+                                            double scale_t, const double* bq, const double* cq, double scale_q,
+                                            const void* v_in, void* v, const void* force, int is_complex,
+                                            double eps1, int forward1, int pair, int flip_between, double eps2,
+                                            int forward2, double* logdet, double* logdet1, double* vnorm2_mid,
+                                            void* ws, size_t ws_bytes, int force_upper, long V, void* stream);
 /* The forward pass of the TRAINING tape on the same kernel (network.py:547-551 + dynamics.py:1266-1297 under
  * autograd: trainers/pytorch/trainer.py:1316-1367): one (not paired) out-of-place v-update v_in -> v AND the
  * three heads as the update uses them -- s = cs tanh(.), t = scale_t (.), q = cq tanh(.), [M][N] fp64 each --

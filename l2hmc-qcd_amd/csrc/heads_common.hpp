@@ -99,6 +99,12 @@ struct HeadsArgs {
   double* tape_q = nullptr;
   // single-update kernels of heads_sliced.hip: also accumulate sum |v_out|^2 into ke_part (a run-time request)
   int want_ke = 0;
+  // heads_sliced.hip: F is an upper-plane SU(3) force [M][4][6][fV] (su3_math.hpp: up_plane) instead of [M][N] with
+  // N = 36 fV -- a run-time, wave-uniform property of the launch.  f_magic = ceil(2^32 / (fV / 16)): the tile -> plane
+  // division as one scalar multiply (the launcher checks that it is exact for every tile of the launch).
+  int f_upper = 0;
+  int fV = 0;
+  unsigned f_magic = 0;
 };
 
 }  // namespace l2q

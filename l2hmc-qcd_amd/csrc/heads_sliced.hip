@@ -41,6 +41,9 @@
 // (First version: 256-thread workgroups of four symmetric wavefronts, two per CU: 40-140 spilled
 // VGPRs -- the A fragments, the fp64 constants of the epilogue and its operands do not fit one
 // wavefront's 256 registers, and scratch traffic shares vmcnt with the LDS-DMA.)
+// (F of a complex update may be an upper-plane SU(3) force, [M][4][6][V]: a run-time property of the launch, see
+// `fetch`.  A plane below the diagonal is read from its transpose's plane with a PLAIN sign flip of the real part, so
+// a real part that is an exact zero enters as -0 where the full field holds +0.)
 #include "heads_common.hpp"
 #include <type_traits>
 #include <vector>
@@ -400,14 +403,53 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
   struct Operands {
     double2 vv[4], ff[4];
     double b0, b1, b2, pcs, pcq, w0, w1, w2;
+    unsigned fsgn;          // XORed into the high dword of Re F (wave-uniform: the sign bit on a rebuilt plane, else 0)
   };
   // rows past M re-read the last valid chain, columns past N the last valid entry (never stored)
   long rowoff[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) rowoff[r] = ((mrow + r) < a.M ? (mrow + r) : (long)a.M - 1) * (long)a.N;
+  // Where F is read.  Full layout: [M][N], element (row, column) as v.  Upper-plane SU(3) force (a.f_upper, a
+  // property of the launch): [M][4][6][V] with N = 36 V and V % 16 == 0, so the 16 columns of a tile lie in ONE
+  // plane (mu, e) = t 16 / V: an entry below the diagonal is read from its transpose's plane, and the sign of its
+  // real part is flipped once the load has landed (sign_f).  Either path issues the same four 16-byte loads per
+  // tile -- only their addresses differ -- so the vmcnt(16) of `fetch` stands.
+  // The element of row m at column n, stored in plane p, sits at m 24 V + p V + n % V
+  //   = (m 36 V + n) + (p - n / V) V - m 12 V:  v's own offset, a scalar of the plane, and a per-row term.
+  // As bytes from v's address: (F - vin) + 16 (p - n / V) V, a 64-bit scalar that changes once in V / 16 tiles
+  // (`pl_*`: decoded in scalar code when a tile leaves [pl_lo, pl_hi)), minus 192 V m, 32 bits per row (the launcher
+  // checks M 192 V < 2^32).  Per tile: two scalar compares and one 64-bit add per row.
+  // (The flip is a plain XOR of the sign bit: a real part that is an exact zero comes out with the other sign than
+  // the full field holds, (+0, +0) there.  It enters the update only through F e^q + t, so the bits of v can differ
+  // only where t is an exact zero as well.)
+  constexpr bool UPPER_OK = CPLX && !TAPE;           // (the instances an upper-plane launch can reach)
+  const bool upper = UPPER_OK && a.f_upper;
+  unsigned rowb[4];                                  // 192 V m: what row m's F lies closer to the start than its v
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int mr = (int)mrow + r;
+    rowb[r] = upper ? (unsigned)(mr < a.M ? mr : a.M - 1) * (192u * (unsigned)a.fV) : 0u;
+  }
+  unsigned pl_lo = 1u, pl_hi = 0u, pl_sgn = 0u;      // tiles of the decoded plane (none yet), its sign mask
+  long pl_bytes = 0;
+  auto upper_tile = [&](long t) {
+    const unsigned ts = __builtin_amdgcn_readfirstlane((unsigned)t);
+    if (ts >= pl_lo && ts < pl_hi) return;
+    const unsigned tp = (unsigned)a.fV >> 4;
+    const unsigned tv = (unsigned)(((unsigned long long)ts * a.f_magic) >> 32);        // = t / (V / 16) = 9 mu + e
+    const unsigned mu = tv / 9u, e = tv - 9u * mu, i = e / 3u, j = e - 3u * i;
+    const unsigned lo = i < j ? i : j, hi = i < j ? j : i;
+    const unsigned pl = lo == hi ? lo : lo + hi + 2u;                                  // up_plane of (lo, hi)
+    pl_lo = tv * tp; pl_hi = pl_lo + tp;
+    pl_sgn = i > j ? 0x80000000u : 0u;
+    pl_bytes = (long)(reinterpret_cast<uintptr_t>(a.F) - reinterpret_cast<uintptr_t>(a.vin)) +
+               16L * (((int)(6u * mu + pl) - (int)tv) * a.fV);
+  };
   auto fetch = [&](long t, Operands& q) {
     const long n = t * 16 + (lane & 15);
     const long nc = n < a.N ? n : (long)a.N - 1;
+    q.fsgn = 0u;
+    if (upper) { upper_tile(t); q.fsgn = pl_sgn; }
     q.b0 = a.b[0][nc]; q.b1 = a.b[1][nc]; q.b2 = a.b[2][nc];
     q.pcs = a.cs[nc];
     q.pcq = a.cq[nc];
@@ -416,8 +458,13 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
     for (int r = 0; r < 4; ++r) {
       const long oo = rowoff[r] + nc;
       if (CPLX) {
-        q.vv[r] = reinterpret_cast<const double2*>(a.vin)[oo];
-        q.ff[r] = reinterpret_cast<const double2*>(a.F)[oo];
+        const double2* vp = reinterpret_cast<const double2*>(a.vin) + oo;
+        q.vv[r] = *vp;
+        if (upper) {
+          q.ff[r] = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(vp) + (pl_bytes - (long)rowb[r]));
+        } else {
+          q.ff[r] = reinterpret_cast<const double2*>(a.F)[oo];
+        }
       } else {
         q.vv[r] = make_double2(a.vin[oo], 0.0);
         q.ff[r] = make_double2(a.F[oo], 0.0);
@@ -540,6 +587,13 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
       exp4x2(xa, xb, es2_, eq2_);
     }
   };
+  // the sign of Re F on a rebuilt plane (fetch): one 32-bit XOR per row, in the tile's lightest period
+  auto sign_f = [&](Operands& q) {
+    if (!UPPER_OK) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      q.ff[r].x = __hiloint2double(__double2hiint(q.ff[r].x) ^ (int)q.fsgn, __double2loint(q.ff[r].x));
+  };
   auto stage_c = [&](long t, const Operands& q, double2 (&outv)[4]) {
     const long n = t * 16 + (lane & 15);
 #pragma unroll
@@ -649,6 +703,7 @@ __global__ __launch_bounds__(512, 1) void heads_sliced_kernel(HeadsArgs a, Slice
         L2Q_SL_T(prof_conv, conv(3 * u + 3, gs));
       }
       stage_b();
+      sign_f(cur);
       if (more) {
         L2Q_SL_CBAR(0);                                // B(3u + 5)
         L2Q_SL_T(prof_mem, issue(3 * u + 7, L2Q_SL_NPD));
@@ -718,7 +773,7 @@ static int sliced_launch(const char* who, double* tape_s, double* tape_t, double
                                       const void* v_in, void* v, const void* force, int is_complex, double eps1,
                                       int forward1, int pair, int flip_between, double eps2, int forward2,
                                       double* logdet, double* logdet1, double* vnorm2_mid, void* ws,
-                                      size_t ws_bytes, void* stream) {
+                                      size_t ws_bytes, void* stream, int force_upper = 0, long fV = 0) {
   L2Q_REQUIRE(Z && sliced && bs && bt && bq && cs && cq && v && force && logdet && ws, L2Q_EINVAL,
               "null pointer (the sliced kernel takes per-entry scales cs / cq)");
   L2Q_REQUIRE(K == OZ_K, L2Q_ESHAPE, "the sliced heads kernel serves K = 256");
@@ -731,6 +786,20 @@ static int sliced_launch(const char* who, double* tape_s, double* tape_t, double
   L2Q_REQUIRE(al(Z) && al(v) && al(vin) && al(force) && (reinterpret_cast<uintptr_t>(sliced) & 255) == 0 &&
                   (reinterpret_cast<uintptr_t>(ws) & 255) == 0,
               L2Q_ESHAPE, "operands must be 16-byte aligned (slice buffer and workspace 256-byte)");
+  unsigned f_magic = 0;
+  if (force_upper) {
+    // [M][4][6][fV]: whole 16-column tiles per plane, and the kernel's tile -> plane multiply exact on this launch
+    // (monotone in the tile, so the two tiles at every plane boundary decide it)
+    L2Q_REQUIRE(is_complex && !tape_s && fV > 0 && fV % 64 == 0 && N == 36 * fV, L2Q_ESHAPE,
+                "an upper-plane force belongs to a complex SU(3) update with N = 36 V, V % 64 == 0");
+    const unsigned long long tp = (unsigned long long)fV / 16, magic = ((1ull << 32) + tp - 1) / tp;
+    bool exact = magic < (1ull << 32);
+    for (unsigned long long pv = 1; pv <= 36 && exact; ++pv)
+      exact = ((pv * tp * magic) >> 32) == pv && (((pv * tp - 1) * magic) >> 32) == pv - 1;
+    L2Q_REQUIRE(exact && (unsigned long long)M * 192ull * (unsigned long long)fV < (1ull << 32), L2Q_ESHAPE,
+                "field too large for the upper-plane force in the sliced heads kernel");
+    f_magic = (unsigned)magic;
+  }
   hipStream_t st = (hipStream_t)stream;
   const int rg = sliced_rg(M), ncw = sliced_ncw(M);
   const long mpad = (long)rg * 64;
@@ -751,6 +820,7 @@ static int sliced_launch(const char* who, double* tape_s, double* tape_t, double
   // a single update asked for vnorm2_mid (no mid-point exists): sum |v_out|^2 of the momentum it writes
   const bool vn2 = !pair && !mid && !tape_s && vnorm2_mid != nullptr;
   a.want_ke = vn2 ? 1 : 0;
+  if (force_upper) { a.f_upper = 1; a.fV = (int)fV; a.f_magic = f_magic; }
   SlicedArgs o;
   o.Zs = zs; o.zscale = zscale; o.Wsl = (const char*)sliced;
   o.wscale = (const double*)((const char*)sliced + sliced_scale_off(N));
@@ -875,6 +945,20 @@ int l2q_vnet_heads_vupdate_sliced_f64(const double* Z, int M, int K, long N, con
   return sliced_launch("l2q_vnet_heads_vupdate_sliced_f64", nullptr, nullptr, nullptr, Z, M, K, N, sliced, bs, cs,
                        scale_s, bt, scale_t, bq, cq, scale_q, v_in, v, force, is_complex, eps1, forward1, pair,
                        flip_between, eps2, forward2, logdet, logdet1, vnorm2_mid, ws, ws_bytes, stream);
+}
+
+int l2q_vnet_heads_vupdate_sliced_upper_f64(const double* Z, int M, int K, long N, const void* sliced,
+                                            const double* bs, const double* cs, double scale_s, const double* bt,
+                                            double scale_t, const double* bq, const double* cq, double scale_q,
+                                            const void* v_in, void* v, const void* force, int is_complex,
+                                            double eps1, int forward1, int pair, int flip_between, double eps2,
+                                            int forward2, double* logdet, double* logdet1, double* vnorm2_mid,
+                                            void* ws, size_t ws_bytes, int force_upper, long V, void* stream) {
+  L2Q_REQUIRE(force_upper == 0 || force_upper == 1, L2Q_EINVAL, "force_upper is 0 or 1");
+  return sliced_launch("l2q_vnet_heads_vupdate_sliced_upper_f64", nullptr, nullptr, nullptr, Z, M, K, N, sliced, bs,
+                       cs, scale_s, bt, scale_t, bq, cq, scale_q, v_in, v, force, is_complex, eps1, forward1, pair,
+                       flip_between, eps2, forward2, logdet, logdet1, vnorm2_mid, ws, ws_bytes, stream, force_upper,
+                       V);
 }
 
 int l2q_vnet_heads_vupdate_sliced_tape_f64(const double* Z, int M, int K, long N, const void* sliced,

@@ -81,9 +81,14 @@ __host__ __device__ constexpr int lk_other(int mu, int j) { return j + (j >= mu 
 // MODE 3: MODE 0 that also forms the real diagonal of W = U A and returns the thread's sum of Re tr W over its
 //   sweep (sum over links of Re tr(U_mu A_mu) = 4 * sum over plaquettes of Re tr P: the Wilson action of the x
 //   the force was taken at).  The other modes return 0.
+// MODE 4 / 5: MODE 0 / 3 with an UPPER-PLANE output, [chain][mu][6][V]: F is anti-Hermitian, plane (j, i) is
+//   (-re, im) of plane (i, j), so only the diagonal and the i < j planes are stored, in the order of up_plane (su3_math.hpp) --
+//   the same bits as those planes of the full field (the lower planes' outv is never formed).
 template <int MODE, int MU, int INM>
 __device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
-  constexpr bool ACTION = MODE == 3;
+  constexpr bool ACTION = MODE == 3 || MODE == 5;
+  constexpr bool UP = MODE >= 4;
+  constexpr int NPL = UP ? 6 : 9;                     // planes per direction of the output
   double esum = 0.0;
   constexpr bool IN_MU = lk_in<INM>(MU);
   const Dims& d = c.d;
@@ -288,7 +293,7 @@ __device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
           ua.re[3 * i + j] = sr; ua.im[3 * i + j] = si;
         }
       }
-      const int so = MU * 9 * V16 + gcur;
+      const int so = MU * NPL * V16 + gcur;
       if (ACTION) esum += (ua.re[0] + ua.re[4]) + ua.re[8];
       const double tri = (ua.im[0] + ua.im[4] + ua.im[8]) / 3.0;     // the trace term is imaginary
 #pragma unroll
@@ -296,6 +301,7 @@ __device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const int e = 3 * i + j, et = 3 * j + i;
+          if (UP && i > j) continue;
           const double fr = (!L2Q_LK_FULL_DIAG && i == j) ? 0.0 : 0.5 * (ua.re[e] - ua.re[et]);
           double fi = 0.5 * (ua.im[e] + ua.im[et]);
           if (i == j) fi -= tri;
@@ -308,11 +314,14 @@ __device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
         }
       if (!(L2Q_LK_EXP & 32)) {
 #pragma unroll
-        for (int e = 0; e < 9; ++e)
+        for (int e = 0; e < 9; ++e) {
+          const int pe = UP ? up_plane(e) : e;
+          if (pe < 0) continue;
           if (!(L2Q_LK_EXP & 2) || outv[e].x == 1.2345e300) {
-            if (L2Q_LK_EXP & 16) buf_st(ro, q_sp, so + e * V16, outv[e]);
-            else buf_st_nt(ro, q_sp, so + e * V16, outv[e]);
+            if (L2Q_LK_EXP & 16) buf_st(ro, q_sp, so + pe * V16, outv[e]);
+            else buf_st_nt(ro, q_sp, so + pe * V16, outv[e]);
           }
+        }
       }
     }
     if (!(L2Q_LK_EXP & 8)) __syncthreads();           // slice tcur consumed
@@ -322,11 +331,13 @@ __device__ __forceinline__ double force_link_sweep(const LkCtx& c) {
       for (int e = 0; e < 9; ++e) *reinterpret_cast<double2*>(fr_lds + dst + e * kEnt) = pre[e];
     }
     if ((L2Q_LK_EXP & 32) && MODE != 2 && it >= c.lo) {
-      const int so = MU * 9 * V16 + gcur;
+      const int so = MU * NPL * V16 + gcur;
 #pragma unroll
       for (int e = 0; e < 9; ++e) {
-        if (L2Q_LK_EXP & 16) buf_st(ro, q_sp, so + e * V16, outv[e]);
-        else buf_st_nt(ro, q_sp, so + e * V16, outv[e]);
+        const int pe = UP ? up_plane(e) : e;
+        if (pe < 0) continue;
+        if (L2Q_LK_EXP & 16) buf_st(ro, q_sp, so + pe * V16, outv[e]);
+        else buf_st_nt(ro, q_sp, so + pe * V16, outv[e]);
       }
     }
     cur ^= 1;
@@ -368,9 +379,12 @@ __device__ __forceinline__ double force_link_block(const double2* __restrict__ x
   k.t0 = tc * tlen;
   k.t1 = min(T, k.t0 + tlen);
   const int chain_bytes = 36 * k.V16;
+  constexpr long OPL = MODE >= 4 ? 24 : 36;          // planes per chain of the output (MODE 4 / 5: upper-plane)
   k.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xn + c * 36L * V), 0, chain_bytes, 0x00020000);
-  k.ro = __builtin_amdgcn_make_buffer_rsrc((void*)(out + c * 36L * V), 0, chain_bytes, 0x00020000);
-  k.rv = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE == 1 || MODE == 2 ? vin : out) + c * 36L * V), 0, chain_bytes, 0x00020000);
+  k.ro = __builtin_amdgcn_make_buffer_rsrc((void*)(out + c * OPL * V), 0, (int)OPL * k.V16, 0x00020000);
+  k.rv = MODE == 1 || MODE == 2
+             ? __builtin_amdgcn_make_buffer_rsrc((void*)(vin + c * 36L * V), 0, chain_bytes, 0x00020000)
+             : k.ro;                                  // (read by the kick and the VJP only)
   k.sp = sb * kRS + k.lt;
   {
     int q = k.sp;
@@ -399,15 +413,28 @@ __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_kernel(
 // The plain force that also leaves part[w] = this workgroup's sum over its links of Re tr(U A): one reduction over
 // the block after its sweep, one store at a fixed index, no atomics (l2q_su3_force_action sums the partials in a
 // fixed order).  A workgroup belongs to one chain, so the partials of a chain are contiguous.
+template <int MODE, int INM>
+__device__ __forceinline__ void force_link_action_block(const double2* __restrict__ xn, const Dims& d, int nsb,
+                                                        int tsplit, int swz, double coef, double2* out, int lo,
+                                                        int stagger, double* __restrict__ part) {
+  long w;
+  const double e = force_link_block<MODE, INM>(xn, d, nsb, tsplit, swz, coef, out, out, lo, stagger, w);
+  // (the sweep ends at a workgroup barrier: nobody reads the tile's LDS any more)
+  const double r = block_sum(e, reinterpret_cast<double*>(fr_lds));
+  if (threadIdx.x == 0) part[w] = r;
+}
 template <int INM>
 __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_action_kernel(
     const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz, double coef, double2* out, int lo,
     int stagger, double* __restrict__ part) {
-  long w;
-  const double e = force_link_block<3, INM>(xn, d, nsb, tsplit, swz, coef, out, out, lo, stagger, w);
-  // (the sweep ends at a workgroup barrier: nobody reads the tile's LDS any more)
-  const double r = block_sum(e, reinterpret_cast<double*>(fr_lds));
-  if (threadIdx.x == 0) part[w] = r;
+  force_link_action_block<3, INM>(xn, d, nsb, tsplit, swz, coef, out, lo, stagger, part);
+}
+// ... with the upper-plane output (MODE 5): the same sweep and the same partial sums
+template <int INM>
+__global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_action_upper_kernel(
+    const double2* __restrict__ xn, Dims d, int nsb, int tsplit, int swz, double coef, double2* out, int lo,
+    int stagger, double* __restrict__ part) {
+  force_link_action_block<5, INM>(xn, d, nsb, tsplit, swz, coef, out, lo, stagger, part);
 }
 
 template <int MODE, int INM>
@@ -456,29 +483,45 @@ static int force_link_tsplit(const Dims& d, int nb) {
 
 long force_link_action_parts(const Dims& d, int nb) { return (long)(d.X * d.Y * d.Z / kRS) * force_link_tsplit(d, nb); }
 
-template <int INM>
+template <int INM, bool UP>
 static void launch_link_action(const double2* xn, Dims d, int nb, int nsb, int tsplit, double coef, double2* out,
                                double* part, hipStream_t st) {
+  const auto kern = UP ? su3_force_link_action_upper_kernel<INM> : su3_force_link_action_kernel<INM>;
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)su3_force_link_action_kernel<INM>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLkLds);
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLkLds);
   }
-  hipLaunchKernelGGL((su3_force_link_action_kernel<INM>), dim3((unsigned)((long)nb * nsb * tsplit)),
-                     dim3(kLkThreads), kLkLds, st, xn, d, nsb, tsplit, tuning().xcd_swizzle, coef, out, 1,
-                     tuning().force_stagger, part);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long)nb * nsb * tsplit)), dim3(kLkThreads), kLkLds, st, xn, d, nsb,
+                     tsplit, tuning().xcd_swizzle, coef, out, 1, tuning().force_stagger, part);
 }
 
-// part: nb * force_link_action_parts(d, nb) doubles
+// part: nb * force_link_action_parts(d, nb) doubles; upper: out is the upper-plane field [nb][4][6][V]
 void launch_force_link_action(const double2* xn, Dims d, int nb, double coef, double2* out, double* part,
-                              hipStream_t st) {
+                              hipStream_t st, bool upper) {
+  const int nsb = d.X * d.Y * d.Z / kRS;
+  const int tsplit = force_link_tsplit(d, nb);
+#define L2Q_LK_CASE(M)                                                                         \
+  if (upper) launch_link_action<M, true>(xn, d, nb, nsb, tsplit, coef, out, part, st);         \
+  else launch_link_action<M, false>(xn, d, nb, nsb, tsplit, coef, out, part, st);              \
+  break;
+  switch (force_link_inmask(d)) {
+    case 7: L2Q_LK_CASE(7)
+    case 6: L2Q_LK_CASE(6)
+    case 4: L2Q_LK_CASE(4)
+    default: L2Q_LK_CASE(0)
+  }
+#undef L2Q_LK_CASE
+}
+
+// the plain force into the upper-plane field [nb][4][6][V] (MODE 4)
+void launch_force_link_upper(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
   const int nsb = d.X * d.Y * d.Z / kRS;
   const int tsplit = force_link_tsplit(d, nb);
   switch (force_link_inmask(d)) {
-    case 7: launch_link_action<7>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
-    case 6: launch_link_action<6>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
-    case 4: launch_link_action<4>(xn, d, nb, nsb, tsplit, coef, out, part, st); break;
-    default: launch_link_action<0>(xn, d, nb, nsb, tsplit, coef, out, part, st);
+    case 7: launch_link_variant<4, 7>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
+    case 6: launch_link_variant<4, 6>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
+    case 4: launch_link_variant<4, 4>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
+    default: launch_link_variant<4, 0>(xn, d, nb, nsb, tsplit, coef, out, out, st);
   }
 }
 

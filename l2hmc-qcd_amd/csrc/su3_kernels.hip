@@ -830,6 +830,23 @@ __global__ __launch_bounds__(kBlock) void su3_project_digits_kernel(const double
   m3_project_su_vec8(v, x);
   if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
 }
+// ... of an anti-Hermitian field given in upper-plane form ([f][6][V], su3_math.hpp: m3_from_upper): six loads, the
+// other three entries rebuilt in registers; the bytes of su3_project_digits_kernel on the full field
+__global__ __launch_bounds__(kBlock) void su3_project_digits_upper_kernel(const double2* in, char* __restrict__ image,
+                                                                          int V, long nblk, double dsc, double dlim,
+                                                                          int* flag) {
+  const long f = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int s = (int)blk * kBlock + threadIdx.x;
+  if (s >= V) return;
+  double2 u[6];
+#pragma unroll
+  for (int p = 0; p < 6; ++p) u[p] = in[(f * 6L + p) * V + s];
+  M3 x;
+  m3_from_upper(x, u);
+  double v[8];
+  m3_project_su_vec8(v, x);
+  if (su3_vec8_to_digits(v, image, f, s, V, dsc, dlim)) atomicOr(flag, 1);
+}
 // The trajectory's entry: reference layout x[f][site][9] -> the native planes (the bits of l2q_su3_pack) AND the
 // digits of vec8(projectSU(x)) (the bytes of su3_project_digits_kernel on those planes) from one read of x.  The
 // 64 links of a wavefront are 9216 contiguous bytes of x: read as nine lane-linear 16-byte loads, turned through
@@ -1061,6 +1078,10 @@ static void force_kernel_name(const Dims& d, char* buf, size_t n) {
   }
 }
 
+// The upper-plane force (l2q_su3_force_upper, l2q_su3_force_action_upper) is an output form of the thread-per-link
+// kernel alone: where the ladder picks another kernel the entries refuse and the caller keeps the full field.
+static bool force_upper_applicable(const Dims& d) { return pick_force(d, false) == ForceKernel::Link; }
+
 // The plaquette sum: the slice-resident kernel where the spatial volume is whole tiles -- <true> where the tile is
 // whole (y, z) planes (Y*Z | 128), which keeps +y, +z inside it -- else the flat kernel.
 enum class PlaqKernel { SliceYZ, Slice, Flat };
@@ -1093,6 +1114,14 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
       (void)l2q_kernel_name("l2q_su3_plaq_reduce", T, X, Y, Z, plaq, sizeof(plaq));
       snprintf(buf, buf_bytes, "%s + %s", force, plaq);
     }
+  } else if (!strcmp(entry, "l2q_su3_force_upper") || !strcmp(entry, "l2q_su3_force_action_upper")) {
+    // (the thread-per-link kernel only; "": the entry refuses this lattice / force_tile)
+    if (force_upper_applicable(dd)) {
+      if (entry[14] == 'u') snprintf(buf, buf_bytes, "su3_force_link_kernel<4, %d>", force_link_inmask(dd));
+      else snprintf(buf, buf_bytes, "su3_force_link_action_upper_kernel<%d>", force_link_inmask(dd));
+    }
+  } else if (!strcmp(entry, "l2q_su3_projsu_digits_upper")) {
+    snprintf(buf, buf_bytes, "su3_project_digits_upper_kernel");
   } else if (!strcmp(entry, "l2q_su3_clover_reduce")) {
     snprintf(buf, buf_bytes, "%s", clover_slice_applicable(dd) ? "su3_clover_slice_kernel" : "su3_clover_kernel");
   } else if (!strcmp(entry, "l2q_su3_flow_stage")) {
@@ -1101,7 +1130,8 @@ int l2q_kernel_name(const char* entry, int T, int X, int Y, int Z, char* buf, si
     char kick[128];
     force_kernel_name<true>(dd, kick, sizeof(kick));
     snprintf(buf, buf_bytes, "%s + su3_expm_mul_kernel<false, false>", kick);
-  } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64")) {
+  } else if (!strcmp(entry, "l2q_vnet_heads_vupdate_sliced_f64") ||
+             !strcmp(entry, "l2q_vnet_heads_vupdate_sliced_upper_f64")) {
     snprintf(buf, buf_bytes, "heads_sliced_kernel");
   } else if (!strncmp(entry, "l2q_vnet_heads_vupdate", 22)) {
     snprintf(buf, buf_bytes, "%s", heads_f64_kernel_name());
@@ -1240,6 +1270,32 @@ int l2q_su3_force_action(const void* xn, double beta, void* fn, double* plaq, in
   return check_launch("l2q_su3_force_action");
 }
 
+int l2q_su3_force_upper(const void* xn, double beta, void* fu, int nb, int T, int X, int Y, int Z, void* stream) {
+  L2Q_REQUIRE(xn && fu, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(xn != fu, L2Q_EINVAL, "force output must not alias the gauge field");
+  const Dims d = make_dims(T, X, Y, Z);
+  L2Q_REQUIRE(force_upper_applicable(d), L2Q_ESHAPE,
+              "the upper-plane force is the thread-per-link kernel's: not on this lattice / force_tile");
+  launch_force_link_upper((const double2*)xn, d, nb, beta / 3.0, (double2*)fu, (hipStream_t)stream);
+  return check_launch("l2q_su3_force_upper");
+}
+
+int l2q_su3_force_action_upper(const void* xn, double beta, void* fu, double* plaq, int nb, int T, int X, int Y,
+                               int Z, void* ws, size_t ws_bytes, void* stream) {
+  L2Q_REQUIRE(xn && fu && plaq && ws, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
+  L2Q_REQUIRE(xn != fu, L2Q_EINVAL, "force output must not alias the gauge field");
+  L2Q_REQUIRE(ws_bytes >= l2q_su3_force_action_ws_bytes(nb, T, X, Y, Z), L2Q_ESHAPE, "workspace too small");
+  const Dims d = make_dims(T, X, Y, Z);
+  L2Q_REQUIRE(force_upper_applicable(d), L2Q_ESHAPE,
+              "the upper-plane force is the thread-per-link kernel's: not on this lattice / force_tile");
+  hipStream_t st = (hipStream_t)stream;
+  launch_force_link_action((const double2*)xn, d, nb, beta / 3.0, (double2*)fu, (double*)ws, st, true);
+  launch_finalize((const double*)ws, plaq, nb, force_link_action_parts(d, nb), 1, 0.25, 0.0, st);
+  return check_launch("l2q_su3_force_action_upper");
+}
+
 int l2q_su3_force_kick(const void* xn, double beta, double coef, void* vn, int nb, int T, int X,
                        int Y, int Z, void* stream) {
   L2Q_REQUIRE(xn && vn, L2Q_EINVAL, "null pointer");
@@ -1328,6 +1384,21 @@ int l2q_su3_projsu_digits(const void* in, void* image, int a_exp, long nfields, 
                      (const double2*)in, (char*)image, (int)V, nblk, ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp),
                      flag);
   return check_launch("l2q_su3_projsu_digits");
+}
+
+int l2q_su3_projsu_digits_upper(const void* in, void* image, int a_exp, long nfields, long V, void* stream) {
+  L2Q_REQUIRE(in && image, L2Q_EINVAL, "null pointer");
+  L2Q_REQUIRE(su3_field_ok(nfields, V) && V % 64 == 0 && nfields % 4 == 0, L2Q_EINVAL,
+              "the digit image serves whole chains (4 fields each) with V % 64 == 0");
+  L2Q_REQUIRE(a_exp > -900 && a_exp < 900, L2Q_EINVAL, "bad operand exponent");
+  L2Q_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, L2Q_ESHAPE, "the image must be 16-byte aligned");
+  int* flag = gs_flag();
+  L2Q_REQUIRE(flag, L2Q_EHIP, "device symbol gs_flag_dev not found");
+  const long nblk = cdiv(V, kBlock);
+  hipLaunchKernelGGL(su3_project_digits_upper_kernel, dim3((unsigned)(nfields * nblk)), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const double2*)in, (char*)image, (int)V, nblk,
+                     ldexp(1.0, GS_BITS - a_exp), ldexp(1.0, a_exp), flag);
+  return check_launch("l2q_su3_projsu_digits_upper");
 }
 
 int l2q_su3_pack_digits(const void* x_ref, void* x_nat, void* image, int a_exp, int nb, long V, void* stream) {

@@ -33,8 +33,11 @@ void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const
                            hipStream_t st);
 // the plain force that also stores one partial sum of Re tr(U A) per workgroup: part[nb][force_link_action_parts]
 long force_link_action_parts(const Dims& d, int nb);
+// upper: out is the upper-plane field [nb][4][6][V] (planes e = 0, 4, 8, 1, 2, 5 of F; the other three are their
+// anti-Hermitian images and are not stored); launch_force_link_upper: the plain force into such a field
 void launch_force_link_action(const double2* xn, Dims d, int nb, double coef, double2* out, double* part,
-                              hipStream_t st);
+                              hipStream_t st, bool upper = false);
+void launch_force_link_upper(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);
 // su3_force_plaq.hip: plaquettes shared between their four links (plain force only)
 bool force_plaq_applicable(const Dims& d);
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st);

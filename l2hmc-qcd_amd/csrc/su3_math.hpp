@@ -211,6 +211,24 @@ __device__ __forceinline__ void m3_tah(M3& r, const M3& x) {
   r.im[0] -= di; r.im[4] -= di; r.im[8] -= di;
 }
 
+// Upper-plane form of an anti-Hermitian field (the force as its kernel stores it): of the nine planes only the
+// diagonal and the i < j ones are kept, as six planes in the order e = 0, 4, 8, 1, 2, 5; plane (j, i) is
+// (-re, im) of plane (i, j).  up_plane: entry e -> its plane, -1 for the three that are not stored.
+__device__ __forceinline__ constexpr int up_entry(int p) { return p < 3 ? 4 * p : p == 3 ? 1 : p == 4 ? 2 : 5; }
+__device__ __forceinline__ constexpr int up_plane(int e) {
+  return e == 0 ? 0 : e == 4 ? 1 : e == 8 ? 2 : e == 1 ? 3 : e == 2 ? 4 : e == 5 ? 5 : -1;
+}
+// The full matrix from its six stored entries.  Where the two real parts of a transposed pair coincide the force
+// kernel writes the SAME signed zero into both planes (0.5 * (a - a) on either side), so a zero keeps its sign.
+__device__ __forceinline__ void m3_from_upper(M3& x, const double2 (&u)[6]) {
+#pragma unroll
+  for (int p = 0; p < 6; ++p) {
+    const int e = up_entry(p), et = 3 * (e % 3) + e / 3;
+    x.re[e] = u[p].x; x.im[e] = u[p].y;
+    if (et != e) { x.re[et] = u[p].x == 0.0 ? u[p].x : -u[p].x; x.im[et] = u[p].y; }
+  }
+}
+
 // exp(A) for a general complex 3x3 A.  Scaling & squaring; the scaled exponential is summed
 // through the Cayley-Hamilton recursion A^(n+1) = p0 A^(n-2) - p1 A^(n-1) + p2 A^n carried
 // on the three scalar coefficients of {I, A, A^2}, so it costs one matmul (A^2), 20 scalar

@@ -158,6 +158,51 @@ def su3_force_action_n(xn: torch.Tensor, beta: float, lat: Sequence[int]):
     return f, plaq
 
 
+class UpperForce:
+    """An SU(3) force in upper-plane form (include/l2q.h: l2q_su3_force_upper): `buf` complex128 [nb, 4, 6, V], planes
+    e = 0, 4, 8, 1, 2, 5 of the native [nb, 4, 9, V] field; the other three are their anti-Hermitian images.  Taken
+    by su3_projsu_digits_n and by the int8-sliced heads kernel (`_sliced_call`), by nothing else."""
+    __slots__ = ('buf',)
+
+    def __init__(self, buf: torch.Tensor):
+        self.buf = buf
+
+    def full(self) -> torch.Tensor:
+        """the native [nb, 4, 9, V] field (a zero keeps the sign the force kernel writes); for tests and tools"""
+        u = self.buf
+        low = torch.complex(torch.where(u.real == 0, u.real, -u.real), u.imag)
+        return torch.stack([u[:, :, 0], u[:, :, 3], u[:, :, 4], low[:, :, 3], u[:, :, 1], u[:, :, 5],
+                            low[:, :, 4], low[:, :, 5], u[:, :, 2]], dim=2)
+
+
+def flat_force(f, nb: int):
+    """the [nb, N] view of a force for the heads kernels; an UpperForce as it is"""
+    return f if isinstance(f, UpperForce) else f.reshape(nb, -1)
+
+
+def su3_force_upper_ok(nb: int, lat: Sequence[int]) -> bool:
+    """The force kernel of this lattice has the upper-plane output and the sliced heads kernel can address it
+    (csrc/heads_sliced.hip: a 32-bit row term, an exact tile -> plane multiply)."""
+    V = int(lat[0]) * int(lat[1]) * int(lat[2]) * int(lat[3])
+    return (V % 64 == 0 and nb * 192 * V < 2 ** 32 and 36 * (V // 16) ** 2 <= 2 ** 32
+            and N.kernel_name('l2q_su3_force_upper', lat) != '')
+
+
+def su3_force_upper_n(xn: torch.Tensor, beta: float, lat: Sequence[int], want_plaq: bool = False):
+    """(UpperForce, plaq [nb] or None): su3_force_n / su3_force_action_n with the upper-plane output -- the same bits
+    in the six planes that are stored, the same plaq.  Raises where su3_force_upper_ok says no."""
+    nb, V = xn.shape[0], xn.shape[-1]
+    T, X, Y, Z = (int(i) for i in lat)
+    f = torch.empty((nb, 4, 6, V), dtype=xn.dtype, device=xn.device)
+    if not want_plaq:
+        N.call('l2q_su3_force_upper', xn, float(beta), f, nb, T, X, Y, Z)
+        return UpperForce(f), None
+    plaq = torch.empty(nb, dtype=torch.float64, device=xn.device)
+    ws = N.workspace(int(N.load().l2q_su3_force_action_ws_bytes(nb, T, X, Y, Z)), xn.device)
+    N.call('l2q_su3_force_action_upper', xn, float(beta), f, plaq, nb, T, X, Y, Z, ws, ws.numel())
+    return UpperForce(f), plaq
+
+
 def su3_force_kick_n(xn: torch.Tensor, beta: float, coef: float, vn: torch.Tensor,
                      lat: Sequence[int], v_src: Optional[torch.Tensor] = None) -> torch.Tensor:
     """vn += coef * F(xn) in place; with v_src: vn = v_src + coef * F(xn) (vn only written)."""
@@ -690,9 +735,14 @@ def gemm_digits_slice(a: torch.Tensor, a_exp: int = SLICED_INPUT_EXP) -> Optiona
     return DigitImage(buf, m, k, int(a_exp))
 
 
-def su3_projsu_digits_n(xn: torch.Tensor, a_exp: int = SLICED_INPUT_EXP) -> Optional[DigitImage]:
+def su3_projsu_digits_n(xn, a_exp: int = SLICED_INPUT_EXP) -> Optional[DigitImage]:
     """su3_projsu_vec8_n(xn).reshape(nb, -1) as a digit image ([nb, 4, 9, V] links); None when the lattice does
-    not qualify (digits_ok)."""
+    not qualify (digits_ok).  An UpperForce: the same bytes from its six planes."""
+    if isinstance(xn, UpperForce):
+        nb, _, _, V = xn.buf.shape
+        buf = _digit_buf(nb, 32 * V, xn.buf.device)
+        N.call('l2q_su3_projsu_digits_upper', xn.buf, buf, int(a_exp), nb * 4, V)
+        return DigitImage(buf, nb, 32 * V, int(a_exp))
     nb, V = xn.shape[0], xn.shape[-1]
     if xn.dim() != 4 or xn.shape[1] != 4 or not digits_ok(nb, V):
         return None
@@ -1027,11 +1077,29 @@ def _sliced_call(z, heads, scales, v, force, eps1, forward1, pair, flip, eps2, f
     out = torch.empty((3 if mid or norm2 else 1, m), dtype=torch.float64, device=z.device)
     nbytes = int(N.load().l2q_vnet_heads_sliced_ws_bytes(m, n))
     ws = N.workspace(nbytes, z.device)
-    N.call('l2q_vnet_heads_vupdate_sliced_f64', z, m, k, n, heads['sliced'], bs, cs, float(scales[0]), bt,
-           float(scales[1]), bq, cq, float(scales[2]), v_src, v, force, int(v.is_complex()), float(eps1),
-           int(forward1), int(pair), int(flip), float(eps2), int(forward2), out[0],
-           out[1] if mid else None, out[2] if mid or norm2 else None, ws, ws.numel())
+    args = (z, m, k, n, heads['sliced'], bs, cs, float(scales[0]), bt, float(scales[1]), bq, cq, float(scales[2]),
+            v_src, v, force.buf if isinstance(force, UpperForce) else force, int(v.is_complex()), float(eps1),
+            int(forward1), int(pair), int(flip), float(eps2), int(forward2), out[0], out[1] if mid else None,
+            out[2] if mid or norm2 else None, ws, ws.numel())
+    if isinstance(force, UpperForce):
+        N.call('l2q_vnet_heads_vupdate_sliced_upper_f64', *args, 1, force.buf.shape[-1])
+    else:
+        N.call('l2q_vnet_heads_vupdate_sliced_f64', *args)
     return out
+
+
+def heads_take_upper_force(heads: dict) -> bool:
+    """The heads + update of these weights run on the int8-sliced kernel (`_use_sliced` for an fp64 activation
+    of their width), the one heads kernel that reads an UpperForce."""
+    ws_ = heads['s'][0]
+    return bool(USE_SLICED_HEADS[0] and heads.get('use_sliced', True) and heads.get('sliced') is not None
+                and ws_.dtype == torch.float64 and ws_.shape[1] == SLICED_K
+                and heads['s'][2] is not None and heads['q'][2] is not None)
+
+
+def _full_force(force) -> None:
+    if isinstance(force, UpperForce):
+        raise N.L2QError('an upper-plane force reached a heads kernel that reads the full field')
 
 
 def _use_sliced(z, heads) -> bool:
@@ -1063,6 +1131,7 @@ def vnet_heads_vupdate_(z: torch.Tensor, heads: dict, scales, v: torch.Tensor,
         if norm2 is not None:
             norm2.append(out[2])
         return out[0]
+    _full_force(force)
     logdet = torch.empty(m, dtype=torch.float64, device=z.device)
     nbytes = int(N.load().l2q_vnet_heads_ws_bytes(m, n))
     ws = N.workspace(nbytes, z.device)
@@ -1090,6 +1159,7 @@ def vnet_heads_vupdate_pair_(z: torch.Tensor, heads: dict, scales, v: torch.Tens
     n = ws_.shape[0]
     if _use_sliced(z, heads):
         return _sliced_call(z, heads, scales, v, force, eps1, forward1, True, flip, eps2, forward2)[0]
+    _full_force(force)
     logdet = torch.empty(m, dtype=torch.float64, device=z.device)
     ws = N.workspace(int(N.load().l2q_vnet_heads_ws_bytes(m, n)), z.device)
     N.call('l2q_vnet_heads_vupdate_pair_f64', z, m, k, n, ws_, bs, cs, float(scales[0]), wt, bt,
@@ -1113,6 +1183,7 @@ def vnet_heads_vupdate_pair_mid_(z: torch.Tensor, heads: dict, scales, v: torch.
     if _use_sliced(z, heads):
         out = _sliced_call(z, heads, scales, v, force, eps1, forward1, True, flip, eps2, forward2, mid=True)
         return out[0], out[1], out[2]
+    _full_force(force)
     out = torch.empty((3, m), dtype=torch.float64, device=z.device)
     ws = N.workspace(int(N.load().l2q_vnet_heads_ws_bytes(m, n)), z.device)
     N.call('l2q_vnet_heads_vupdate_pair_mid_f64', z, m, k, n, ws_, bs, cs, float(scales[0]), wt, bt,

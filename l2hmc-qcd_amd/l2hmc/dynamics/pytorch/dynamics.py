@@ -208,6 +208,7 @@ class Dynamics(nn.Module):
         self.pair_v_updates = True  # adjacent v-updates on the same x in one heads kernel
         self.fuse_x_vec8 = True     # SU3: the x-update also emits the next vnet input vec8(x')
         self.fuse_entry_digits = True   # SU3: the pack of a trajectory's input also emits its digit image
+        self.upper_plane_force = True   # SU3: the sampler's force keeps its six upper planes (trajectory.VInputs)
         self.fuse_u1_steps = True   # U1 (small lattices, dense nets): one kernel per sub-update
         # Improved gauge action (c1 != 0): the reference evaluates H with potential_fn (the
         # Trainer's LatticeSU3(c1), trainers/pytorch/trainer.py:499-504) but takes the leapfrog
@@ -654,7 +655,7 @@ class Dynamics(nn.Module):
         """(force, hidden activation z, kernel weights) for the fused heads kernel at xn, kept nowhere (what a
         trajectory keeps of them is `trajectory.VInputs`; `ts` is None: a trajectory's state lives in its stepper)."""
         assert ts is None
-        return VInputs(self, beta).get(vnet, xn)
+        return VInputs(self, beta, upper=False).get(vnet, xn)       # (callers read the force: the full field)
 
     def _sliced_wanted(self, vnet) -> bool:
         """`sliced_heads`: True -> networks whose last hidden activation is BOUNDED (tanh: every row
@@ -1471,7 +1472,8 @@ class GraphedTransition:
                  d.fuse_u1_steps, d.fuse_half_heads, d.merge_hmc_kicks, d.sliced_heads,
                  ops.USE_SLICED_HEADS[0], d.sliced_input, ops.USE_SLICED_INPUT[0], ops.USE_DIGIT_INPUTS[0],
                  ops.USE_KERNEL_ENERGIES[0], d.pair_v_updates_verbose,
-                 getattr(d, 'fuse_x_vec8', None), d.net_precision, d.config.verbose, d.training)
+                 getattr(d, 'fuse_x_vec8', None), d.net_precision, d.config.verbose, d.training,
+                 d.upper_plane_force)
         return (ops.PARAM_GENERATION[0], params, masks, flags)
 
     def _run(self):

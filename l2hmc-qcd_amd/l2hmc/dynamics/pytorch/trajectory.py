@@ -37,10 +37,12 @@ class VInputs:
 
     `plaq`: sum Re tr P of the x the LAST force was taken at when that launch was asked for it (`want_pe`), else
     None; it outlives `x_changed` (the late metrics read it after the x-update)."""
-    __slots__ = ('dyn', 'beta', 'plaq', 'F', 'xv', 'fv', 'z')
+    __slots__ = ('dyn', 'beta', 'plaq', 'F', 'xv', 'fv', 'z', 'upper')
 
-    def __init__(self, dyn, beta):
-        self.dyn, self.beta, self.plaq = dyn, beta, None
+    def __init__(self, dyn, beta, upper: bool = True):
+        """`upper`: F may be held as an `ops.UpperForce` where every consumer takes one (`_upper_ok`); an owner
+        that hands F out (`Dynamics._v_inputs_n`) says False."""
+        self.dyn, self.beta, self.plaq, self.upper = dyn, beta, None, upper
         self.x_changed()
 
     def x_changed(self, emitted=None) -> None:
@@ -48,26 +50,49 @@ class VInputs:
         self.F = self.fv = None
         self.xv, self.z = emitted, {}
 
+    def _upper_ok(self, vnet, hs, xn: Tensor) -> bool:
+        """The force of this x may keep only its six upper planes: its two readers are then the digit projection
+        and the int8-sliced heads kernel of `vnet`, which both take that form.  The sampler only, SU(3) with the
+        plain Wilson action, on the lattices whose force kernel has that output; not under injected draws (the
+        launch-by-launch parity runs).  `dyn.upper_plane_force = False` keeps the full field everywhere."""
+        dyn = self.dyn
+        return bool(self.upper and dyn.upper_plane_force and hs is not None and dyn.group == 'SU3'
+                    and dyn.potential_c1 == 0.0 and not dyn.training and dyn._inject is None and xn.is_cuda
+                    and ops.heads_take_upper_force(hs) and dyn._digit_inputs(vnet, xn.shape[0], xn.shape[-1])
+                    and ops.su3_force_upper_ok(xn.shape[0], dyn.latvolume))
+
     def get(self, vnet, xn: Tensor, want_pe: bool = False):
         """(force, hidden activation z, kernel weights) for the fused heads kernel; (force, None, None) where that
         kernel does not run.  `want_pe`: the potential of this x is consumed, so a force that is not held yet
-        comes from the launch that also returns the plaquette sum."""
+        comes from the launch that also returns the plaquette sum.  The force is an `ops.UpperForce` where
+        `_upper_ok`, else the full field."""
         dyn = self.dyn
-        if self.F is None:
-            self.F, self.plaq = (ops.su3_force_action_n(xn, float(self.beta), dyn.latvolume) if want_pe
-                                 else (dyn._force_n(xn, self.beta), None))
+        w = hs = None
+        if dyn._can_fuse_heads(vnet):
+            p = dyn._perms()
+            w = vnet.kernel_weights(p['in'], p['out'])
+            hs = w['heads_scaled']
+            # int8 slice image of the head weights (csrc/heads_sliced.hip); lives in the version-keyed
+            # weight cache, so it is rebuilt whenever a parameter changes.  Both knobs are consulted on
+            # EVERY call (`use_sliced`), the image is built the first time they are both on.
+            hs['use_sliced'] = bool(dyn._sliced_wanted(vnet) and ops.USE_SLICED_HEADS[0])
+            if hs['use_sliced'] and 'sliced' not in hs:
+                hs['sliced'] = ops.heads_sliced_build(hs)
+        upper = self._upper_ok(vnet, hs, xn)
+        if self.F is None or (isinstance(self.F, ops.UpperForce) and not upper):
+            # (an upper-plane force held for another network of this x that this one cannot read: taken again as
+            # the full field, the same bits; the projection and the plaquette sum of the first are kept)
+            held = None if self.F is None else self.plaq
+            if upper:
+                self.F, self.plaq = ops.su3_force_upper_n(xn, float(self.beta), dyn.latvolume, want_pe)
+            else:
+                self.F, self.plaq = (ops.su3_force_action_n(xn, float(self.beta), dyn.latvolume) if want_pe
+                                     else (dyn._force_n(xn, self.beta), None))
+            if self.plaq is None:
+                self.plaq = held
         fn = self.F
-        if not dyn._can_fuse_heads(vnet):
+        if w is None:
             return fn, None, None
-        p = dyn._perms()
-        w = vnet.kernel_weights(p['in'], p['out'])
-        hs = w['heads_scaled']
-        # int8 slice image of the head weights (csrc/heads_sliced.hip); lives in the version-keyed
-        # weight cache, so it is rebuilt whenever a parameter changes.  Both knobs are consulted on
-        # EVERY call (`use_sliced`), the image is built the first time they are both on.
-        hs['use_sliced'] = bool(dyn._sliced_wanted(vnet) and ops.USE_SLICED_HEADS[0])
-        if hs['use_sliced'] and 'sliced' not in hs:
-            hs['sliced'] = ops.heads_sliced_build(hs)
         z = self.z.get(id(vnet))
         if z is None:
             nb = xn.shape[0]
@@ -96,7 +121,7 @@ class VInputs:
         if z is not None:
             # heads + momentum update in one kernel: s, t, q never reach HBM
             return ops.vnet_heads_vupdate_(z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q),
-                                           vn.reshape(nb, -1), fn.reshape(nb, -1), eps, forward,
+                                           vn.reshape(nb, -1), ops.flat_force(fn, nb), eps, forward,
                                            None if v_src is None else v_src.reshape(nb, -1), norm2=norm2)
         if v_src is not None:
             vn.copy_(v_src)
@@ -213,7 +238,7 @@ class SamplerStepper:
         vnet = dyn._get_vnet(st1) if closing and opening else None
         if vnet is not None and dyn._get_vnet(st0) is vnet and dyn._can_fuse_heads(vnet):
             fn, z, w = self.inputs.get(vnet, x, want_pe)
-            args = (z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q), v.reshape(nb, -1), fn.reshape(nb, -1),
+            args = (z, w['heads_scaled'], (vnet.nw.s, vnet.nw.t, vnet.nw.q), v.reshape(nb, -1), ops.flat_force(fn, nb),
                     dyn._eps('v', st0), f0, flip, dyn._eps('v', st1), f1)
             if not self.late:
                 return ops.vnet_heads_vupdate_pair_(*args)

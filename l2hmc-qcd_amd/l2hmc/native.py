@@ -45,12 +45,15 @@ SIGNATURES = {
     'l2q_su3_force_kick': (I, [P, D, D, P, I, I, I, I, I, P]),
     'l2q_su3_force_action_ws_bytes': (Z, [I, I, I, I, I]),
     'l2q_su3_force_action': (I, [P, D, P, P, I, I, I, I, I, P, Z, P]),
+    'l2q_su3_force_upper': (I, [P, D, P, I, I, I, I, I, P]),
+    'l2q_su3_force_action_upper': (I, [P, D, P, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_force_kick_to': (I, [P, D, D, P, P, I, I, I, I, I, P]),
     'l2q_su3_expm_mul': (I, [P, P, D, P, I, P, I, L, P]),
     'l2q_su3_expm_mul2': (I, [P, P, D, P, I, P, I, L, P]),
     'l2q_su3_expm_mul2_vec8': (I, [P, P, D, P, I, P, P, I, L, P]),
     'l2q_su3_expm_mul2_digits': (I, [P, P, D, P, I, P, P, I, I, L, P]),
     'l2q_su3_projsu_digits': (I, [P, P, I, L, L, P]),
+    'l2q_su3_projsu_digits_upper': (I, [P, P, I, L, L, P]),
     'l2q_su3_pack_digits': (I, [P, P, P, I, I, L, P]),
     'l2q_su3_project_su': (I, [P, P, L, L, P]),
     'l2q_su3_projsu_vec8': (I, [P, P, L, L, P]),
@@ -99,6 +102,8 @@ SIGNATURES = {
     'l2q_vnet_heads_sliced_ws_bytes': (Z, [I, L]),
     'l2q_vnet_heads_vupdate_sliced_f64': (I, [P, I, I, L, P, P, P, D, P, D, P, P, D, P, P, P, I, D, I, I, I, D,
                                               I, P, P, P, P, Z, P]),
+    'l2q_vnet_heads_vupdate_sliced_upper_f64': (I, [P, I, I, L, P, P, P, D, P, D, P, P, D, P, P, P, I, D, I, I, I,
+                                                    D, I, P, P, P, P, Z, I, L, P]),
     'l2q_vnet_heads_vupdate_sliced_tape_f64': (I, [P, I, I, L, P, P, P, P, D, P, P, P, P, P, I, D, I, P, P, P, P,
                                                    P, Z, P]),
     'l2q_gemm_f32': (I, [P, P, I, I, L, P, P, L, P, P, P, F, I, P, P, Z, P]),
