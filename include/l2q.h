@@ -59,8 +59,8 @@ int l2q_version(void);
  * calling thread's current HIP device -- the library's only state besides the last-error text
  * is this per-device table: "xcd_swizzle" in {0,1}; "force_tile" in {2,5,7} picks the SU(3) force
  * kernel design (5, the default: thread per link, su3_force_link.hip; 7: plaquettes shared between their
- * four links, su3_force_plaq.hip; 2: the slice-resident kernel that otherwise runs only on lattices too large
- * for 5).  Results agree to rounding across variants.  Returns the previous value, or L2Q_EINVAL for an unknown key/value.
+ * four links, su3_force_plaq.hip; 2: the slice-resident kernel of su3_force.hip, which otherwise runs only on lattices
+ * too large for 5; su3_force.hip: pick_force decides).  Results agree to rounding across variants.  Returns the previous value, or L2Q_EINVAL for an unknown key/value.
  * (The Python binding applies L2Q_TUNING="key=value,..." from the environment when it loads the library.) */
 int l2q_set_tuning(const char* key, int value);
 /* Name (template instantiation as rocprofv3 prints it, without the l2q:: prefix) of the device

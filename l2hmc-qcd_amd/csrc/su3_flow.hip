@@ -242,19 +242,13 @@ int l2q_su3_clover_reduce(const void* xn, int nb, int T, int X, int Y, int Z, do
   hipStream_t st = (hipStream_t)stream;
   const int swz = tuning().xcd_swizzle;
   if (clover_slice_applicable(d)) {
-    const int nsb = X * Y * Z / kCT;
-    const int tsplit = t_chunks((long)nb * nsb, T, 512);       // >= ~2 rounds of 256 CUs, one workgroup each
-    const long per_chain = (long)nsb * tsplit;
-    L2Q_REQUIRE(ws_bytes >= (size_t)nb * per_chain * 3 * sizeof(double), L2Q_ESHAPE, "workspace too small");
+    const SliceGrid g = slice_grid(d, nb, kCT, 512);           // >= ~2 rounds of 256 CUs, one workgroup each
+    L2Q_REQUIRE(ws_bytes >= (size_t)nb * g.per_chain * 3 * sizeof(double), L2Q_ESHAPE, "workspace too small");
     const size_t lds = 3ul * kCSlot * sizeof(double2);
-    static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-      (void)hipFuncSetAttribute((const void*)su3_clover_slice_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-    }
-    hipLaunchKernelGGL(su3_clover_slice_kernel, dim3((unsigned)(nb * per_chain)), dim3(kCThreads), lds, st,
-                       (const double2*)xn, d, nsb, tsplit, swz, 0, (double*)ws);
-    launch_finalize((const double*)ws, out, nb, per_chain, 3, 1.0, 0.0, st);
+    dynamic_lds_once<su3_clover_slice_kernel>(lds);
+    hipLaunchKernelGGL(su3_clover_slice_kernel, dim3((unsigned)g.blocks), dim3(kCThreads), lds, st,
+                       (const double2*)xn, d, g.nsb, g.tsplit, swz, 0, (double*)ws);
+    launch_finalize((const double*)ws, out, nb, g.per_chain, 3, 1.0, 0.0, st);
     return check_launch("l2q_su3_clover_reduce");
   }
   const long nblk = cdiv(d.V, kBlock);

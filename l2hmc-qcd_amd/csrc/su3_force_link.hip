@@ -28,6 +28,7 @@
 // slice kernel (same operation order per link).
 #include "su3_force_tile.hpp"
 #include "su3_launch.hpp"
+#include <type_traits>
 
 namespace l2q {
 
@@ -437,19 +438,6 @@ __global__ __launch_bounds__(kLkThreads, L2Q_LK_OCC) void su3_force_link_action_
   force_link_action_block<5, INM>(xn, d, nsb, tsplit, swz, coef, out, lo, stagger, part);
 }
 
-template <int MODE, int INM>
-static void launch_link_variant(const double2* xn, Dims d, int nb, int nsb, int tsplit, double coef,
-                                const double2* vin, double2* out, hipStream_t st) {
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)su3_force_link_kernel<MODE, INM>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLkLds);
-  }
-  hipLaunchKernelGGL((su3_force_link_kernel<MODE, INM>), dim3((unsigned)((long)nb * nsb * tsplit)),
-                     dim3(kLkThreads), kLkLds, st, xn, d, nsb, tsplit, tuning().xcd_swizzle, coef, vin, out, 1,
-                     tuning().force_stagger);
-}
-
 int force_link_inmask(const Dims& d) {
   int m = 0;
   if (kRS % d.Z == 0) m |= 4;
@@ -462,89 +450,60 @@ bool force_link_applicable(const Dims& d) {
   return (d.X * d.Y * d.Z) % kRS == 0 && 36.0 * d.V * 16.0 < 2.0e9;
 }
 
-// g_x += coef * TAH(g_F) A^H  (l2q_su3_force_bwd; the staple sum A recomputed by the force sweep)
-void launch_force_link_bwd(const double2* xn, Dims d, int nb, double coef, const double2* gf, double2* gx,
-                           hipStream_t st) {
-  const int Vs = d.X * d.Y * d.Z;
-  const int nsb = Vs / kRS;
-  const int tsplit = t_chunks((long)nb * nsb, d.T, 1024);
+// f(std::integral_constant<int, INM>) for the lattice's in-mask: the one place that spells out the four INM the
+// kernels are built for
+template <class F>
+static void with_inmask(const Dims& d, F&& f) {
   switch (force_link_inmask(d)) {
-    case 7: launch_link_variant<2, 7>(xn, d, nb, nsb, tsplit, coef, gf, gx, st); break;
-    case 6: launch_link_variant<2, 6>(xn, d, nb, nsb, tsplit, coef, gf, gx, st); break;
-    case 4: launch_link_variant<2, 4>(xn, d, nb, nsb, tsplit, coef, gf, gx, st); break;
-    default: launch_link_variant<2, 0>(xn, d, nb, nsb, tsplit, coef, gf, gx, st);
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 0>{});
   }
 }
 
-// >= ~2 resident rounds of 2 x 256 workgroups
-static int force_link_tsplit(const Dims& d, int nb) {
-  return t_chunks((long)nb * (d.X * d.Y * d.Z / kRS), d.T, 1024, tuning().force_tsplit);
+// >= ~2 resident rounds of 2 x 256 workgroups.  The VJP takes the launcher's own t-chunks; the other forms honour
+// tuning force_tsplit.
+static SliceGrid force_link_grid(const Dims& d, int nb, bool vjp = false) {
+  return slice_grid(d, nb, kRS, 1024, vjp ? 0 : tuning().force_tsplit);
 }
 
-long force_link_action_parts(const Dims& d, int nb) { return (long)(d.X * d.Y * d.Z / kRS) * force_link_tsplit(d, nb); }
+long force_link_action_parts(const Dims& d, int nb) { return force_link_grid(d, nb).per_chain; }
 
-template <int INM, bool UP>
-static void launch_link_action(const double2* xn, Dims d, int nb, int nsb, int tsplit, double coef, double2* out,
-                               double* part, hipStream_t st) {
-  const auto kern = UP ? su3_force_link_action_upper_kernel<INM> : su3_force_link_action_kernel<INM>;
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLkLds);
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)((long)nb * nsb * tsplit)), dim3(kLkThreads), kLkLds, st, xn, d, nsb,
-                     tsplit, tuning().xcd_swizzle, coef, out, 1, tuning().force_stagger, part);
-}
-
-// part: nb * force_link_action_parts(d, nb) doubles; upper: out is the upper-plane field [nb][4][6][V]
-void launch_force_link_action(const double2* xn, Dims d, int nb, double coef, double2* out, double* part,
-                              hipStream_t st, bool upper) {
-  const int nsb = d.X * d.Y * d.Z / kRS;
-  const int tsplit = force_link_tsplit(d, nb);
-#define L2Q_LK_CASE(M)                                                                         \
-  if (upper) launch_link_action<M, true>(xn, d, nb, nsb, tsplit, coef, out, part, st);         \
-  else launch_link_action<M, false>(xn, d, nb, nsb, tsplit, coef, out, part, st);              \
-  break;
-  switch (force_link_inmask(d)) {
-    case 7: L2Q_LK_CASE(7)
-    case 6: L2Q_LK_CASE(6)
-    case 4: L2Q_LK_CASE(4)
-    default: L2Q_LK_CASE(0)
-  }
-#undef L2Q_LK_CASE
-}
-
-// the plain force into the upper-plane field [nb][4][6][V] (MODE 4)
-void launch_force_link_upper(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
-  const int nsb = d.X * d.Y * d.Z / kRS;
-  const int tsplit = force_link_tsplit(d, nb);
-  switch (force_link_inmask(d)) {
-    case 7: launch_link_variant<4, 7>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
-    case 6: launch_link_variant<4, 6>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
-    case 4: launch_link_variant<4, 4>(xn, d, nb, nsb, tsplit, coef, out, out, st); break;
-    default: launch_link_variant<4, 0>(xn, d, nb, nsb, tsplit, coef, out, out, st);
+// The Action forms (MODE 3, 5) are kernels of their own, which take `part` where the others take `vin`.
+template <LinkForm FORM, int INM>
+static void launch_link(const double2* xn, const Dims& d, const SliceGrid& g, double coef, const double2* vin,
+                        double2* out, double* part, hipStream_t st) {
+  const dim3 grid((unsigned)g.blocks), block(kLkThreads);
+  const int swz = tuning().xcd_swizzle, stagger = tuning().force_stagger;
+  constexpr int MODE = (int)FORM;
+  if constexpr (MODE == 3 || MODE == 5) {
+    constexpr auto kern = MODE == 5 ? su3_force_link_action_upper_kernel<INM> : su3_force_link_action_kernel<INM>;
+    dynamic_lds_once<kern>(kLkLds);
+    hipLaunchKernelGGL(kern, grid, block, kLkLds, st, xn, d, g.nsb, g.tsplit, swz, coef, out, 1, stagger, part);
+  } else {
+    constexpr auto kern = su3_force_link_kernel<MODE, INM>;
+    dynamic_lds_once<kern>(kLkLds);
+    hipLaunchKernelGGL(kern, grid, block, kLkLds, st, xn, d, g.nsb, g.tsplit, swz, coef, vin, out, 1, stagger);
   }
 }
 
-void launch_force_link(bool kick, const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st,
-                       const double2* vin) {
+void launch_force_link(LinkForm form, const double2* xn, Dims d, int nb, double coef, const double2* vin, double2* out,
+                       double* part, hipStream_t st) {
   if (vin == nullptr) vin = out;
-  const int Vs = d.X * d.Y * d.Z;
-  const int nsb = Vs / kRS;
-  const int tsplit = force_link_tsplit(d, nb);
-#define L2Q_LK_CASE(M)                                                                    \
-  case M:                                                                                 \
-    if (kick) launch_link_variant<1, M>(xn, d, nb, nsb, tsplit, coef, vin, out, st);           \
-    else launch_link_variant<0, M>(xn, d, nb, nsb, tsplit, coef, vin, out, st);                \
-    break;
-  switch (force_link_inmask(d)) {
-    L2Q_LK_CASE(7)
-    L2Q_LK_CASE(6)
-    L2Q_LK_CASE(4)
-    default:
-      if (kick) launch_link_variant<1, 0>(xn, d, nb, nsb, tsplit, coef, vin, out, st);
-      else launch_link_variant<0, 0>(xn, d, nb, nsb, tsplit, coef, vin, out, st);
-  }
-#undef L2Q_LK_CASE
+  const SliceGrid g = force_link_grid(d, nb, form == LinkForm::Vjp);
+  with_inmask(d, [&](auto inm) {
+    constexpr int INM = decltype(inm)::value;
+    switch (form) {
+      case LinkForm::Force: launch_link<LinkForm::Force, INM>(xn, d, g, coef, vin, out, part, st); break;
+      case LinkForm::Kick: launch_link<LinkForm::Kick, INM>(xn, d, g, coef, vin, out, part, st); break;
+      case LinkForm::Vjp: launch_link<LinkForm::Vjp, INM>(xn, d, g, coef, vin, out, part, st); break;
+      case LinkForm::ForceAction: launch_link<LinkForm::ForceAction, INM>(xn, d, g, coef, vin, out, part, st); break;
+      case LinkForm::Upper: launch_link<LinkForm::Upper, INM>(xn, d, g, coef, vin, out, part, st); break;
+      case LinkForm::UpperAction: launch_link<LinkForm::UpperAction, INM>(xn, d, g, coef, vin, out, part, st); break;
+    }
+  });
 }
 
 }  // namespace l2q
+

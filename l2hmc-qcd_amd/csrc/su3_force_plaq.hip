@@ -522,17 +522,11 @@ bool force_plaq_applicable(const Dims& d) {
 }
 
 void launch_force_plaq(const double2* xn, Dims d, int nb, double coef, double2* out, hipStream_t st) {
-  const int Vs = d.X * d.Y * d.Z;
-  const int nsb = Vs / kRS;
   // one workgroup per CU: >= 2 rounds of 256
-  const int tsplit = t_chunks((long)nb * nsb, d.T, 512, tuning().force_tsplit);
-  static PerDeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute((const void*)su3_force_plaq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kPqfLds);
-  }
-  hipLaunchKernelGGL(su3_force_plaq_kernel, dim3((unsigned)((long)nb * nsb * tsplit)), dim3(kPqfThreads), kPqfLds,
-                     st, xn, d, nsb, tsplit, tuning().xcd_swizzle, coef, out);
+  const SliceGrid g = slice_grid(d, nb, kRS, 512, tuning().force_tsplit);
+  dynamic_lds_once<su3_force_plaq_kernel>(kPqfLds);
+  hipLaunchKernelGGL(su3_force_plaq_kernel, dim3((unsigned)g.blocks), dim3(kPqfThreads), kPqfLds, st, xn, d, g.nsb,
+                     g.tsplit, tuning().xcd_swizzle, coef, out);
 }
 
 }  // namespace l2q

@@ -554,8 +554,8 @@ int l2q_su3_force_bwd(const void* xn, const void* gf, double beta, void* gx, int
   // the slice-resident force sweep with the VJP epilogue (su3_force_link.hip, MODE 2) where the force itself
   // runs on it: the staple sum of the link from LDS-resident slices instead of 18 flat matrix loads per link
   if (force_link_runs(d)) {
-    launch_force_link_bwd((const double2*)xn, d, nb, beta / 3.0, (const double2*)gf, (double2*)gx,
-                          (hipStream_t)stream);
+    launch_force_link(LinkForm::Vjp, (const double2*)xn, d, nb, beta / 3.0, (const double2*)gf, (double2*)gx, nullptr,
+                      (hipStream_t)stream);
     return check_launch("l2q_su3_force_bwd");
   }
   const long nblk = cdiv(d.V, kBlock);
