@@ -366,6 +366,39 @@ int l2q_su3_gauge_condition(const void* xn, int dirmask, double* out, int nb, in
  * xn nor gn (L2Q_EINVAL). */
 int l2q_su3_gauge_apply(const void* xn, const void* gn, void* out, int nb, int T, int X, int Y, int Z, void* stream);
 
+/* ---------------------------------------------------------------- SU(3) APE and HYP link smearing */
+/* csrc/su3_smear.hip.  For a side field A (links of direction nu) and a forward field B (links of direction mu) the two
+ * staples of direction nu around a mu-link, in the plaquette convention of l2q_su3_force, are
+ *   S_nu[A, B](x) = A(x) B(x+nu) A(x+mu)^H  +  A(x-nu)^H B(x-nu) A(x-nu+mu).
+ * Proj is the projection of l2q_su3_project_su: the unitary (polar) factor X (X^H X)^(-1/2) with the phase of its
+ * determinant divided out -- not the iterative maximisation of Re tr(V X^H) that some codes use.  It is accurate while
+ * the matrix it is given stays well conditioned (condition number up to ~100: fields near the unit circle).
+ * All four entry points are out of place and take any extents (odd, 1 and 2 as well): nothing is updated in place, so
+ * the checkerboard kernels' even-extent rule does not apply.  L2Q_EINVAL, before any HIP call: a null pointer; an
+ * output that aliases an input; a non-positive size or a chain of more than 2^31 / 36 sites; alpha not finite or
+ * outside [0, 1]; for APE a dirmask outside 1..15 or with fewer than two bits set.  One thread per (chain, output field, site); a chain's result does not depend
+ * on the batch.
+ * APE step with the directions D = dirmask (bit mu = direction mu), n = |D| - 1:
+ *   mu in D:      out_mu = Proj[(1 - alpha) U_mu + (alpha / 2n) sum_{nu in D, nu != mu} S_nu[U_nu, U_mu]]
+ *   mu not in D:  out_mu = U_mu, copied bit for bit; such links enter no staple.
+ * dirmask 15 is the 4D step; 15 & ~(1 << t) smears the three directions of the slices of direction t within each slice.
+ * Algorithmic traffic: 1152 B per (chain, site), the field read and written once. */
+int l2q_su3_ape_smear(const void* xn, double alpha, int dirmask, void* out, int nb, int T, int X, int Y, int Z,
+                      void* stream);
+/* HYP smearing (Hasenfratz & Knechtli) in three levels, each projected; eta = 6 - mu - nu - rho, the fourth direction:
+ *   level 1:  B1[mu][eta] = Proj[(1 - alpha3) U_mu + (alpha3 / 2) S_eta[U_eta, U_mu]]          (V-bar_{mu; nu rho})
+ *   level 2:  B2[mu][nu]  = Proj[(1 - alpha2) U_mu + (alpha2 / 4) sum_{rho != mu, nu} S_rho[B1[rho][eta], B1[mu][eta]]]
+ *   level 3:  V_mu        = Proj[(1 - alpha1) U_mu + (alpha1 / 6) sum_{nu != mu} S_nu[B2[nu][mu], B2[mu][nu]]]
+ * b1 and b2 are decorated fields: the 12 fields F[mu][o], o != mu, of a level in the native layout [nb][4][3][9][V],
+ * index order mu, then k with o = k + (k >= mu) (the pair order of l2q_su3_loop_reduce), then entry, then site: three link
+ * fields in size (432 B per (chain, site)).  Algorithmic traffic per (chain, site): level 1 2304 B (links read, b1
+ * written), level 2 4032 B (links and b1 read, b2 written), level 3 2880 B (links and b2 read, links written). */
+int l2q_su3_hyp_level1(const void* xn, double alpha3, void* b1, int nb, int T, int X, int Y, int Z, void* stream);
+int l2q_su3_hyp_level2(const void* xn, const void* b1, double alpha2, void* b2, int nb, int T, int X, int Y, int Z,
+                       void* stream);
+int l2q_su3_hyp_level3(const void* xn, const void* b2, double alpha1, void* out, int nb, int T, int X, int Y, int Z,
+                       void* stream);
+
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:
  *   forward : v' = exp(eps s/2) v - (eps/2) (F exp(eps q) + t),  logdet[c] =  sum eps s/2

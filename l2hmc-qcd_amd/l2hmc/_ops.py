@@ -549,6 +549,63 @@ def su3_gauge_apply_n(xn: torch.Tensor, gn: torch.Tensor, lat: Sequence[int]) ->
     return out
 
 
+def _smear_out(what: str, xn: torch.Tensor, out: Optional[torch.Tensor], decorated: bool) -> torch.Tensor:
+    """the output of a smearing launch: a link field [nb, 4, 9, V] or a decorated field [nb, 4, 3, 9, V]"""
+    nb, V = xn.shape[0], xn.shape[-1]
+    want = (nb, 4, 3, 9, V) if decorated else (nb, 4, 9, V)
+    if out is None:
+        return torch.empty(want, dtype=C128, device=xn.device)
+    if out.dtype != C128 or tuple(out.shape) != want or not out.is_contiguous():
+        raise ValueError(f'{what}: out must be contiguous complex128 {list(want)}, got {out.dtype} {list(out.shape)}')
+    return out
+
+
+def _decorated_in(what: str, xn: torch.Tensor, bn: torch.Tensor) -> None:
+    want = (xn.shape[0], 4, 3, 9, xn.shape[-1])
+    if bn.dtype != C128 or tuple(bn.shape) != want or not bn.is_contiguous():
+        raise ValueError(f'{what}: the decorated field must be contiguous complex128 {list(want)}, got {bn.dtype} '
+                         f'{list(bn.shape)}')
+
+
+def su3_ape_smear_n(xn: torch.Tensor, alpha: float, dirmask: int, lat: Sequence[int],
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One APE step of the native field xn over the directions in the 4-bit set dirmask (see l2q.h): the links of the
+    other directions are copied.  Out of place: out None = a new field, never xn."""
+    T, X, Y, Z = (int(i) for i in lat)
+    out = _smear_out('su3_ape_smear_n', xn, out, False)
+    N.call('l2q_su3_ape_smear', xn, float(alpha), int(dirmask), out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_hyp_level1_n(xn: torch.Tensor, alpha3: float, lat: Sequence[int],
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Level 1 of a HYP step: the decorated field B1 [nb, 4, 3, 9, V] from the thin links (see l2q.h)."""
+    T, X, Y, Z = (int(i) for i in lat)
+    out = _smear_out('su3_hyp_level1_n', xn, out, True)
+    N.call('l2q_su3_hyp_level1', xn, float(alpha3), out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_hyp_level2_n(xn: torch.Tensor, b1: torch.Tensor, alpha2: float, lat: Sequence[int],
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Level 2 of a HYP step: the decorated field B2 from the thin links and B1; out is never b1."""
+    T, X, Y, Z = (int(i) for i in lat)
+    _decorated_in('su3_hyp_level2_n', xn, b1)
+    out = _smear_out('su3_hyp_level2_n', xn, out, True)
+    N.call('l2q_su3_hyp_level2', xn, b1, float(alpha2), out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_hyp_level3_n(xn: torch.Tensor, b2: torch.Tensor, alpha1: float, lat: Sequence[int],
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Level 3 of a HYP step: the smeared links from the thin links and B2; out is never xn."""
+    T, X, Y, Z = (int(i) for i in lat)
+    _decorated_in('su3_hyp_level3_n', xn, b2)
+    out = _smear_out('su3_hyp_level3_n', xn, out, False)
+    N.call('l2q_su3_hyp_level3', xn, b2, float(alpha1), out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

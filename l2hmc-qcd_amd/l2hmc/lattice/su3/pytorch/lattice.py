@@ -405,26 +405,34 @@ class LatticeSU3(Lattice):
         return {'t0': s['t0'], 'w0': s['w0'], 't_reached': float(table['t'][-1]), 'table': table}
 
     # ------------------------------------------------------------ Wilson loops R x T and Polyakov loops
-    def wilson_loop_sums_n(self, xn: Tensor, rmax: int, tmax: int) -> Tensor:
+    def wilson_loop_sums_n(self, xn: Tensor, rmax: int, tmax: int, xtn: Optional[Tensor] = None) -> Tensor:
         """[nb, rmax, tmax, 12] complex: entry [R-1, T-1, k] = sum over sites of tr W_{mu nu}(R, T), the loop with R links
         along mu and T links along nu, k = 3 mu + (nu if nu < mu else nu - 1).  The lines along mu grow by one link
         per R and the lines along nu by one link per T (`l2q_su3_line_extend`), in at most two fields beyond xn, which
-        is never written; one `l2q_su3_loop_reduce` per (R, T)."""
+        is never written; one `l2q_su3_loop_reduce` per (R, T).  With `xtn` (another native field, e.g. HYP-smeared)
+        the T lines along nu are built from xtn and the R lines along mu from xn; None: both from xn."""
         self._no_grad(xn, 'wilson_loop_sums_n')
         rmax, tmax = int(rmax), int(tmax)
         if rmax < 1 or tmax < 1:
             raise ValueError(f'wilson_loop_sums_n: need rmax, tmax >= 1, got {rmax}, {tmax}')
+        if xtn is None:
+            xtn = xn
+        else:
+            self._no_grad(xtn, 'wilson_loop_sums_n')
+            if xtn.shape != xn.shape or xtn.dtype != xn.dtype:
+                raise ValueError(f'wilson_loop_sums_n: xtn must be shaped like xn {list(xn.shape)}, got '
+                                 f'{list(xtn.shape)} {xtn.dtype}')
         L = self._lattice_shape
         out = torch.empty((xn.shape[0], rmax, tmax, 12), dtype=torch.complex128, device=xn.device)
         a, b_buf = xn, None
         for r in range(1, rmax + 1):
             if r > 1:       # a: lines of length r - 1 -> r (the first time into a new field, then in place)
                 a = ops.su3_line_extend_n(a, xn, r - 1, L, out=None if a is xn else a)
-            b = xn
+            b = xtn
             for t in range(1, tmax + 1):
                 if t > 1:
-                    b_buf = torch.empty_like(xn) if b_buf is None else b_buf
-                    b = ops.su3_line_extend_n(b, xn, t - 1, L, out=b_buf)
+                    b_buf = torch.empty_like(xtn) if b_buf is None else b_buf
+                    b = ops.su3_line_extend_n(b, xtn, t - 1, L, out=b_buf)
                 out[:, r - 1, t - 1] = ops.su3_loop_sums_n(a, r, b, t, L)
         return out
 
@@ -442,14 +450,34 @@ class LatticeSU3(Lattice):
         """W(R, T) [nb, rmax, tmax] real: the mean over sites and over the three pairs (mu != time_dir, nu = time_dir)
         of Re tr W_{mu nu}(R, T) / 3; with time_dir None the mean over all 12 ordered pairs.  Loops that would wrap
         around the lattice are refused: ValueError when rmax or tmax is below 1 or exceeds the smallest extent its
-        lines run along.  Measured on smeared links by passing `flow(x, t)`."""
+        lines run along.  Measured on smeared links by passing `flow(x, t)`, or, keeping the time direction sharp, by
+        `wilson_loop_table_xt` / `smeared_loop_table`."""
+        return self._loop_table(x, None, rmax, tmax, time_dir)
+
+    def wilson_loop_table_xt(self, x: Tensor, xt: Tensor, rmax: int, tmax: int, time_dir: int = 0) -> Tensor:
+        """`wilson_loop_table` with its two kinds of line from two fields: the R lines along mu != time_dir are built
+        from x (e.g. `ape_smear(x)`), the T lines along time_dir from xt (e.g. `hyp_smear(x)`); `smeared_loop_table`
+        does both.  xt = x gives the bits of `wilson_loop_table(x, ...)`.  Needs a time_dir (ValueError with None: over all 12
+        ordered pairs every direction is both an R line and a T line)."""
+        self._no_grad(x, 'wilson_loop_table_xt')
+        self._no_grad(xt, 'wilson_loop_table_xt')
+        if time_dir is None:
+            raise ValueError('wilson_loop_table_xt: needs a time_dir: with all 12 ordered pairs every direction is '
+                             'both an R line and a T line')
+        if not isinstance(xt, torch.Tensor) or xt.shape != x.shape:
+            raise ValueError(f'wilson_loop_table_xt: xt must be a tensor shaped like x {list(x.shape)}, got '
+                             f'{list(getattr(xt, "shape", []))}')
+        return self._loop_table(x, xt, rmax, tmax, time_dir)
+
+    def _loop_table(self, x: Tensor, xt: Optional[Tensor], rmax: int, tmax: int, time_dir: Optional[int]) -> Tensor:
+        """the table of `wilson_loop_table` (xt None) / `wilson_loop_table_xt`"""
         self._no_grad(x, 'wilson_loop_table')
         rmax, tmax = int(rmax), int(tmax)
         rlim, tlim = self._loop_extents(time_dir)
         if not (1 <= rmax <= rlim and 1 <= tmax <= tlim):
             raise ValueError(f'wilson_loop_table: need 1 <= rmax <= {rlim} and 1 <= tmax <= {tlim} on lattice '
                              f'{list(self._lattice_shape)} with time_dir = {time_dir}, got rmax = {rmax}, tmax = {tmax}')
-        s = self.wilson_loop_sums_n(self.pack(x), rmax, tmax).real
+        s = self.wilson_loop_sums_n(self.pack(x), rmax, tmax, None if xt is None else self.pack(xt)).real
         if time_dir is not None:
             td = int(time_dir)
             s = s[..., [3 * mu + (td if td < mu else td - 1) for mu in range(4) if mu != td]]
@@ -482,6 +510,102 @@ class LatticeSU3(Lattice):
         if xinit is not None:
             metrics['dploop'] = (metrics['ploop'] - self.polyakov(xinit, 0).abs()).abs()
         return metrics
+
+    # ------------------------------------------------------------ APE and HYP link smearing
+    def _smear_checks(self, x: Tensor, what: str, alphas, nsteps) -> tuple[list[float], int]:
+        self._no_grad(x, what)
+        try:
+            al = [float(a) for a in alphas]
+        except (TypeError, ValueError):
+            al = [float('nan')]
+        if not all(0.0 <= a <= 1.0 for a in al):
+            raise ValueError(f'LatticeSU3.{what}: every alpha must be a number in [0, 1], got {alphas!r}')
+        if isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 0:
+            raise ValueError(f'LatticeSU3.{what}: nsteps must be an integer >= 0, got {nsteps!r}')
+        return al, int(nsteps)
+
+    @staticmethod
+    def _ape_dirmask(dirs: str, time_dir: int) -> int:
+        """the APE directions as the 4-bit set of l2q.h: all four ('all'), all but time_dir ('spatial')"""
+        if dirs not in ('spatial', 'all'):
+            raise ValueError(f"LatticeSU3.ape_smear: dirs must be 'spatial' or 'all', got {dirs!r}")
+        if isinstance(time_dir, bool) or int(time_dir) != time_dir or not 0 <= int(time_dir) < 4:
+            raise ValueError(f'LatticeSU3.ape_smear: time_dir must be 0..3, got {time_dir!r}')
+        return 15 if dirs == 'all' else 15 & ~(1 << int(time_dir))
+
+    def ape_smear_n(self, xn: Tensor, alpha: float = 0.5, nsteps: int = 1, dirs: str = 'spatial',
+                    time_dir: int = 0) -> Tensor:
+        """`nsteps` APE smearing steps (Albanese et al.) of a native field,
+            U'_mu = Proj[(1 - alpha) U_mu + (alpha / 2n) sum_{nu in D, nu != mu} (two staples of direction nu)],
+        over the directions D: `dirs='spatial'` the three directions other than `time_dir`, with staples inside the
+        slice (n = 2; the links along time_dir are copied and enter nothing, so slices do not mix); `dirs='all'` the 4D
+        step (n = 3).  Proj is `l2q_su3_project_su`: the unitary (polar) factor with the determinant phase divided out,
+        not the iterative max-Re-tr projection of some codes.  One `l2q_su3_ape_smear` per step, ping-pong between two
+        fields; xn is never written.  Returns a new field (xn itself for nsteps = 0).  Any extents; no autograd."""
+        (alpha,), nsteps = self._smear_checks(xn, 'ape_smear', [alpha], nsteps)
+        mask = self._ape_dirmask(dirs, time_dir)
+        bufs: list = [None, None]
+        cur = xn
+        for k in range(nsteps):
+            if bufs[k & 1] is None:
+                bufs[k & 1] = torch.empty_like(xn)
+            cur = ops.su3_ape_smear_n(cur, alpha, mask, self._lattice_shape, out=bufs[k & 1])
+        return cur
+
+    def ape_smear(self, x: Tensor, alpha: float = 0.5, nsteps: int = 1, dirs: str = 'spatial',
+                  time_dir: int = 0) -> Tensor:
+        """`ape_smear_n` in the reference layout: a new tensor; x is never written."""
+        self._smear_checks(x, 'ape_smear', [alpha], nsteps)
+        self._ape_dirmask(dirs, time_dir)
+        yn = self.ape_smear_n(self.pack(x), alpha, nsteps, dirs, time_dir)
+        return AG.attach_native(self.unpack(yn), yn)
+
+    def hyp_smear_n(self, xn: Tensor, alphas=(0.75, 0.6, 0.3), nsteps: int = 1) -> Tensor:
+        """`nsteps` HYP smearing steps (Hasenfratz & Knechtli) of a native field with alphas = (alpha1, alpha2, alpha3):
+        three nested levels of projected staple sums that stay inside the hypercubes attached to the link
+        (`l2q_su3_hyp_level1/2/3`, definitions in include/l2q.h; the projection is that of `ape_smear_n`).  All four
+        directions are smeared.  Workspace: the two decorated fields B1, B2 of 12 fields each, six link fields in size
+        (3456 B per chain and site: 3.6 GB for 256 chains of 8^4), allocated once per call and reused across nsteps,
+        plus the ping-pong result fields; xn is never written.  Returns a new field (xn itself for nsteps = 0).  Any
+        extents; no autograd."""
+        if not (isinstance(alphas, (tuple, list)) and len(alphas) == 3):
+            raise ValueError(f'LatticeSU3.hyp_smear: alphas must be three numbers in [0, 1], got {alphas!r}')
+        (a1, a2, a3), nsteps = self._smear_checks(xn, 'hyp_smear', alphas, nsteps)
+        L = self._lattice_shape
+        cur = xn
+        if nsteps > 0:
+            b1 = torch.empty((xn.shape[0], 4, 3, 9, xn.shape[-1]), dtype=xn.dtype, device=xn.device)
+            b2 = torch.empty_like(b1)
+            bufs: list = [None, None]
+            for k in range(nsteps):
+                if bufs[k & 1] is None:
+                    bufs[k & 1] = torch.empty_like(xn)
+                ops.su3_hyp_level1_n(cur, a3, L, out=b1)
+                ops.su3_hyp_level2_n(cur, b1, a2, L, out=b2)
+                cur = ops.su3_hyp_level3_n(cur, b2, a1, L, out=bufs[k & 1])
+        return cur
+
+    def hyp_smear(self, x: Tensor, alphas=(0.75, 0.6, 0.3), nsteps: int = 1) -> Tensor:
+        """`hyp_smear_n` in the reference layout: a new tensor; x is never written."""
+        if not (isinstance(alphas, (tuple, list)) and len(alphas) == 3):
+            raise ValueError(f'LatticeSU3.hyp_smear: alphas must be three numbers in [0, 1], got {alphas!r}')
+        self._smear_checks(x, 'hyp_smear', alphas, nsteps)
+        yn = self.hyp_smear_n(self.pack(x), alphas, nsteps)
+        return AG.attach_native(self.unpack(yn), yn)
+
+    def smeared_loop_table(self, x: Tensor, rmax: int, tmax: int, time_dir: int = 0, ape_alpha: float = 0.5,
+                           ape_steps: int = 10, hyp_alphas=(0.75, 0.6, 0.3)) -> Tensor:
+        """W(R, T) [nb, rmax, tmax] for the static potential, the time direction kept sharp: the spatial lines from
+        `ape_steps` spatial APE steps at `ape_alpha`, the temporal lines from one HYP step at `hyp_alphas`:
+        `wilson_loop_table_xt(ape_smear(x, ape_alpha, ape_steps, 'spatial', time_dir), hyp_smear(x, hyp_alphas), rmax,
+        tmax, time_dir)`.  ape_steps = 0 leaves the spatial lines thin, hyp_alphas None the temporal ones."""
+        if time_dir is None:
+            raise ValueError('smeared_loop_table: needs a time_dir (0..3)')
+        xa = self.ape_smear(x, ape_alpha, ape_steps, 'spatial', time_dir) if int(ape_steps) != 0 else x
+        xh = None if hyp_alphas is None else self.hyp_smear(x, hyp_alphas, 1)
+        if xh is None:
+            return self.wilson_loop_table(xa, rmax, tmax, time_dir)
+        return self.wilson_loop_table_xt(xa, xh, rmax, tmax, time_dir)
 
     # ------------------------------------------------------------ heatbath and overrelaxation sweeps
     def _local_update_checks(self, xn: Tensor, what: str, nsweeps: int, nover: int = 0) -> None:

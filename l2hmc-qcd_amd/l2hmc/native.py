@@ -77,6 +77,10 @@ SIGNATURES = {
     'l2q_su3_gaugefix_sweep': (I, [P, P, P, I, I, D, I, I, I, I, I, P]),
     'l2q_su3_gauge_condition': (I, [P, I, P, I, I, I, I, I, P, Z, P]),
     'l2q_su3_gauge_apply': (I, [P, P, P, I, I, I, I, I, P]),
+    'l2q_su3_ape_smear': (I, [P, D, I, P, I, I, I, I, I, P]),
+    'l2q_su3_hyp_level1': (I, [P, D, P, I, I, I, I, I, P]),
+    'l2q_su3_hyp_level2': (I, [P, P, D, P, I, I, I, I, I, P]),
+    'l2q_su3_hyp_level3': (I, [P, P, D, P, I, I, I, I, I, P]),
     'l2q_v_update': (I, [P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_v_update_to': (I, [P, P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_accept': (I, [P, P, P, P, P, P, I, I, P]),
