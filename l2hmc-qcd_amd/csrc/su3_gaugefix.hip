@@ -26,30 +26,6 @@
 
 namespace l2q {
 
-// k = |r| and rh = r / k of the subgroup part r of a matrix, from its four entries (ii, ij, ji, jj); rh = (1, 0, 0, 0)
-// where k is zero or not finite
-__device__ __forceinline__ double su2_part_unit(Quat& rh, double iir, double iii, double ijr, double iji, double jir,
-                                                double jii, double jjr, double jji) {
-  const double r0 = 0.5 * (iir + jjr), r1 = 0.5 * (iji + jii), r2 = 0.5 * (ijr - jir), r3 = 0.5 * (iii - jji);
-  const double k = sqrt(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
-  rh = Quat{1.0, 0.0, 0.0, 0.0};
-  if (k > 0.0 && k <= 1.7976931348623157e308) { rh.q0 = r0 / k; rh.q1 = r1 / k; rh.q2 = r2 / k; rh.q3 = r3 / k; }
-  return k;
-}
-
-// u <- embed(g) u: rows I and J
-template <int I, int J>
-__device__ __forceinline__ void su2_embed_mul(M3& u, const Quat& g) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double xr = u.re[3 * I + c], xi = u.im[3 * I + c], yr = u.re[3 * J + c], yi = u.im[3 * J + c];
-    u.re[3 * I + c] = g.q0 * xr - g.q3 * xi + g.q2 * yr - g.q1 * yi;
-    u.im[3 * I + c] = g.q0 * xi + g.q3 * xr + g.q2 * yi + g.q1 * yr;
-    u.re[3 * J + c] = -g.q2 * xr - g.q1 * xi + g.q0 * yr + g.q3 * yi;
-    u.im[3 * J + c] = -g.q2 * xi + g.q1 * xr + g.q0 * yi - g.q3 * yr;
-  }
-}
-
 // one subgroup of the local step: g and W both take embed(a^omega) from the left
 template <int I, int J>
 __device__ __forceinline__ void gf_subgroup(M3& g, M3& w, double omega) {
@@ -79,14 +55,7 @@ __global__ __launch_bounds__(kBlock) void su3_gaugefix_kernel(double2* x, double
   const int V = d.V, vh = V / 2;
   const int h = (int)blk * kBlock + threadIdx.x;
   if (h >= vh) return;
-  // the site of this parity in the pair (2h, 2h + 1), which differ in z only (Z is even)
-  int s = 2 * h;
-  {
-    int q = s / Z;
-    const int y = q % Y; q /= Y;
-    const int xx = q % X; q /= X;
-    s += (parity - q - xx - y) & 1;
-  }
+  const int s = checkerboard_site(h, parity, X, Y, Z);
   double2* f = x + c * 36L * V;
   M3 k;
   m3_zero(k);
@@ -97,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void su3_gaugefix_kernel(double2* x, double
     M3 a;
     load_link(a, fm, V, s);
     m3_add(k, a);
-    load_link_adj(a, fm, V, hb_hop(s, stride_of(d, mu), extent_of(d, mu), -1));
+    load_link_adj(a, fm, V, site_hop(s, stride_of(d, mu), extent_of(d, mu), -1));
     m3_add(k, a);
   }
   M3 g;
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void su3_gaugefix_kernel(double2* x, double
 #pragma unroll 1
   for (int mu = 0; mu < 4; ++mu) {
     double2* fm = f + mu * 9 * V;
-    const int sm = hb_hop(s, stride_of(d, mu), extent_of(d, mu), -1);
+    const int sm = site_hop(s, stride_of(d, mu), extent_of(d, mu), -1);
     // both links before either store: the compiler cannot know that a store through fm leaves the other link alone
     M3 u, v, o;
     load_link(u, fm, V, s);
@@ -152,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void su3_gauge_condition_kernel(const doubl
     load_link(a, fm, V, s);
     fr += a.re[0] + a.re[4] + a.re[8];
     m3_add(sum, a);
-    load_link(a, fm, V, hb_hop(s, stride_of(d, mu), extent_of(d, mu), -1));
+    load_link(a, fm, V, site_hop(s, stride_of(d, mu), extent_of(d, mu), -1));
 #pragma unroll
     for (int e = 0; e < 9; ++e) { sum.re[e] -= a.re[e]; sum.im[e] -= a.im[e]; }
   }
@@ -192,14 +161,10 @@ __global__ __launch_bounds__(kBlock) void su3_gauge_apply_kernel(const double2* 
   load_link(g, fg, d.V, s);
   load_link(u, xn + off, d.V, s);
   m3_mul_nn(o, g, u);
-  load_link(g, fg, d.V, hb_hop(s, stride_of(d, mu), extent_of(d, mu), +1));
+  load_link(g, fg, d.V, site_hop(s, stride_of(d, mu), extent_of(d, mu), +1));
   m3_mul_na(u, o, g);
   store_link(out + off, d.V, s, u);
 }
-
-static bool gf_all_even(int T, int X, int Y, int Z) { return ((T | X | Y | Z) & 1) == 0; }
-// 1..15 with at least two directions
-static bool gf_dirmask_ok(int m) { return m >= 1 && m <= 15 && (m & (m - 1)) != 0; }
 
 }  // namespace l2q
 
@@ -212,10 +177,10 @@ int l2q_su3_gaugefix_sweep(void* xn, void* gn, const int* active, int dirmask, i
   L2Q_REQUIRE(xn, L2Q_EINVAL, "null pointer");
   L2Q_REQUIRE(gn != xn, L2Q_EINVAL, "gn must not alias xn");
   L2Q_REQUIRE(parity == 0 || parity == 1, L2Q_EINVAL, "parity must be 0 or 1");
-  L2Q_REQUIRE(gf_dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
+  L2Q_REQUIRE(dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
   L2Q_REQUIRE(omega >= 1.0 && omega < 2.0, L2Q_EINVAL, "omega must be finite and in [1, 2)");
   L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
-  L2Q_REQUIRE(gf_all_even(T, X, Y, Z), L2Q_ESHAPE, "a checkerboard update needs even extents");
+  L2Q_REQUIRE(all_even(T, X, Y, Z), L2Q_ESHAPE, "a checkerboard update needs even extents");
   const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V / 2, kBlock);
   hipLaunchKernelGGL(su3_gaugefix_kernel, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, (hipStream_t)stream,
@@ -227,12 +192,12 @@ int l2q_su3_gaugefix_sweep(void* xn, void* gn, const int* active, int dirmask, i
 int l2q_su3_gauge_condition(const void* xn, int dirmask, double* out, int nb, int T, int X, int Y, int Z, void* ws,
                             size_t ws_bytes, void* stream) {
   L2Q_REQUIRE(xn && out && ws, L2Q_EINVAL, "null pointer");
-  L2Q_REQUIRE(gf_dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
+  L2Q_REQUIRE(dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
   L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   const Dims d = make_dims(T, X, Y, Z);
   const long nblk = cdiv(d.V, kBlock);
   L2Q_REQUIRE(ws_bytes >= (size_t)nb * nblk * 2 * sizeof(double), L2Q_ESHAPE, "workspace too small");
-  const int nd = (dirmask & 1) + ((dirmask >> 1) & 1) + ((dirmask >> 2) & 1) + ((dirmask >> 3) & 1);
+  const int nd = dirmask_count(dirmask);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(su3_gauge_condition_kernel, dim3((unsigned)(nb * nblk)), dim3(kBlock), 0, st,
                      (const double2*)xn, dirmask, 1.0 / (3.0 * nd * d.V), 1.0 / (3.0 * d.V), T, X, Y, Z, nblk,

@@ -110,17 +110,10 @@ __global__ __launch_bounds__(kBlock) void su3_link_update_kernel(const double2* 
   const int h0 = (int)blk * kBlock + threadIdx.x;
   const bool live = h0 < vh;
   const int h = live ? h0 : 0;
-  // the site of this parity in the pair (2h, 2h + 1), which differ in z only (Z is even)
-  int s = 2 * h;
-  {
-    int q = s / Z;
-    const int y = q % Y; q /= Y;
-    const int x = q % X; q /= X;
-    s += (parity - q - x - y) & 1;
-  }
+  const int s = checkerboard_site(h, parity, X, Y, Z);
   const double2* f = xr + c * 36L * V;
   const int stm = stride_of(d, mu), em = extent_of(d, mu);
-  const int s_pm = hb_hop(s, stm, em, +1);
+  const int s_pm = site_hop(s, stm, em, +1);
   M3 acc;
   m3_zero(acc);
 #pragma unroll 1
@@ -132,13 +125,13 @@ __global__ __launch_bounds__(kBlock) void su3_link_update_kernel(const double2* 
     M3 a, b, t;
     // up:   U_nu(x+mu) U_mu(x+nu)^H U_nu(x)^H
     load_link(a, fn, V, s_pm);
-    load_link(b, fm, V, hb_hop(s, stn, en, +1));
+    load_link(b, fm, V, site_hop(s, stn, en, +1));
     m3_mul_na(t, a, b);
     load_link(a, fn, V, s);
     m3_mac_na(acc, t, a);
     // down: U_nu(x+mu-nu)^H U_mu(x-nu)^H U_nu(x-nu)
-    const int s_mn = hb_hop(s, stn, en, -1);
-    load_link(a, fn, V, hb_hop(s_pm, stn, en, -1));
+    const int s_mn = site_hop(s, stn, en, -1);
+    load_link(a, fn, V, site_hop(s_pm, stn, en, -1));
     load_link(b, fm, V, s_mn);
     m3_mul_aa(t, a, b);
     load_link(a, fn, V, s_mn);
@@ -158,8 +151,6 @@ __global__ __launch_bounds__(kBlock) void su3_link_update_kernel(const double2* 
     if (threadIdx.x == 0) partial[c * nblk + blk] = tot;
   }
 }
-
-static bool all_even(int T, int X, int Y, int Z) { return ((T | X | Y | Z) & 1) == 0; }
 
 }  // namespace l2q
 

@@ -13,6 +13,11 @@ inline bool su3_dims_ok(int nb, int T, int X, int Y, int Z) {
 }
 // the same for the per-link entry points, which take n chains or fields of V sites
 inline bool su3_field_ok(long n, long V) { return n > 0 && V > 0 && V <= 200000000L; }
+// what a checkerboard update needs of the extents
+inline bool all_even(int T, int X, int Y, int Z) { return ((T | X | Y | Z) & 1) == 0; }
+// a set of directions (bit mu of m): 1..15 with at least two directions; and its size
+inline bool dirmask_ok(int m) { return m >= 1 && m <= 15 && (m & (m - 1)) != 0; }
+inline int dirmask_count(int m) { return (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1); }
 
 // Slice-resident kernels sweep t with one workgroup per (chain, spatial tile, t-chunk): the chunks per tile that bring
 // `groups` = chains x tiles to about `target` workgroups, at most T, evened out so that no chunk is empty.

@@ -78,6 +78,21 @@ __device__ __forceinline__ int bwd(int s, int cm, const Dims& d, int mu) {
   return (cm == 0) ? s + (n - 1) * st : s - st;
 }
 
+// The flat site kernels keep no coordinates (a Site indexed by a loop-variant direction is copied to scratch): the
+// coordinate comes by division.  Periodic neighbour of site s in a direction of stride st and extent ext; dir = +1 / -1
+__device__ __forceinline__ int site_hop(int s, int st, int ext, int dir) {
+  const int c = (s / st) % ext;
+  if (dir > 0) return c + 1 == ext ? s - (ext - 1) * st : s + st;
+  return c == 0 ? s + (ext - 1) * st : s - st;
+}
+// ... and site s moved n steps forward, 0 <= n < ext
+__device__ __forceinline__ int site_shifted(int s, int st, int ext, int n) {
+  const int c = (s / st) % ext;
+  int c2 = c + n;
+  if (c2 >= ext) c2 -= ext;
+  return s + (c2 - c) * st;
+}
+
 // the slice-resident kernels sweep t and keep a thread's place inside a time slice
 struct SPos {
   int q, x, y, z;        // spatial site index and coordinates

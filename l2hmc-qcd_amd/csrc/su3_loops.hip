@@ -15,14 +15,6 @@
 
 namespace l2q {
 
-// site s moved n steps forward in a direction of stride st and extent ext, periodic; 0 <= n < ext
-__device__ __forceinline__ int shifted(int s, int st, int ext, int n) {
-  const int c = (s / st) % ext;
-  int c2 = c + n;
-  if (c2 >= ext) c2 -= ext;
-  return s + (c2 - c) * st;
-}
-
 // ------------------------------------------------------------------ one more link on every line
 // One thread per (chain, mu, site); mu comes from the block index, so it is wave-uniform.  lin may be lout: a
 // thread reads only its own entry of lin, and entry e of its result depends on entry e of what it read, so no
@@ -37,7 +29,7 @@ __global__ __launch_bounds__(kBlock) void su3_line_extend_kernel(const double2* 
   const int s = (int)blk * kBlock + threadIdx.x;
   if (s >= d.V) return;
   const int ext = extent_of(d, mu);
-  const int s2 = shifted(s, stride_of(d, mu), ext, n % ext);
+  const int s2 = site_shifted(s, stride_of(d, mu), ext, n % ext);
   const long off = f * 9L * d.V;
   M3 a, u, o;
   load_link(a, lin + off, d.V, s);
@@ -72,14 +64,14 @@ __global__ __launch_bounds__(kBlock, 2) void su3_loop_reduce_kernel(const double
 #pragma unroll 1
   for (int mu = 0; mu < 4; ++mu) {
     const int emu = extent_of(d, mu);
-    const int s_r = shifted(s, stride_of(d, mu), emu, r % emu);
+    const int s_r = site_shifted(s, stride_of(d, mu), emu, r % emu);
     M3 am;
     load_link(am, ac + mu * 9 * V, V, s);
 #pragma unroll 1
     for (int j = 0; j < 3; ++j) {
       const int nu = j + (j >= mu ? 1 : 0);
       const int enu = extent_of(d, nu);
-      const int s_t = shifted(s, stride_of(d, nu), enu, t % enu);
+      const int s_t = site_shifted(s, stride_of(d, nu), enu, t % enu);
       M3 p, q, y;
       load_link(p, bc + nu * 9 * V, V, s_r);
       m3_mul_nn(y, am, p);

@@ -23,14 +23,13 @@
 // only in which staple directions are summed (a 4-bit set) and where a direction's side and forward fields are
 // (smear_fields).
 // Every operand is a coalesced 16 B / lane plane load, the shifted ones re-read through L1 / L2 as in su3_loops.hip.
-// The staple loop is not unrolled and the neighbours come by division (hb_hop): live are the sum, one product and two
+// The staple loop is not unrolled and the neighbours come by division (site_hop): live are the sum, one product and two
 // operands; the link itself is loaded after the loop.  Left alone, the compiler hoists the plane addresses of the
 // loop-invariant operands out of the loop (18 VGPRs per link) and issues all six loads of a direction at once, and
 // spills at two waves per SIMD; so the site index of an iteration exists only once the sum of the one before does, and
 // the second staple's pair only once the first staple is summed (site_after): three link loads in flight, no scratch
 // (profiles/su3_smear.md).  All four entry points are out of place, so any extents do.
 #include "su3_launch.hpp"
-#include "su3_subgroup.hpp"
 
 namespace l2q {
 
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(kBlock, 2) void su3_smear_kernel(const double2* __r
     store_link(om, V, s, u);
     return;
   }
-  const int s_mu = hb_hop(s, stride_of(d, mu), extent_of(d, mu), +1);
+  const int s_mu = site_hop(s, stride_of(d, mu), extent_of(d, mu), +1);
   M3 acc;
   m3_zero(acc);
 #pragma unroll 1
@@ -115,16 +114,16 @@ __global__ __launch_bounds__(kBlock, 2) void su3_smear_kernel(const double2* __r
     const int sx = site_after(s, acc.im[8]), sx_mu = site_after(s_mu, acc.im[8]);
     // A(x) B(x+rho) A(x+mu)^H
     load_link(a, side, V, sx);
-    load_link(b, fwd, V, hb_hop(sx, st, ext, +1));
+    load_link(b, fwd, V, site_hop(sx, st, ext, +1));
     m3_mul_nn(p, a, b);
     load_link(a, side, V, sx_mu);
     m3_mac_na(acc, p, a);
     // A(x-rho)^H B(x-rho) A(x-rho+mu)
-    const int s_dn = site_after(hb_hop(sx, st, ext, -1), acc.im[8]);
+    const int s_dn = site_after(site_hop(sx, st, ext, -1), acc.im[8]);
     load_link(a, side, V, s_dn);
     load_link(b, fwd, V, s_dn);
     m3_mul_an(p, a, b);
-    load_link(a, side, V, hb_hop(sx_mu, st, ext, -1));
+    load_link(a, side, V, site_hop(sx_mu, st, ext, -1));
     m3_mac_nn(acc, p, a);
   }
   M3 u, r;
@@ -150,8 +149,6 @@ static int launch_smear(const char* name, const void* xn, const void* dec, int d
   return check_launch(name);
 }
 
-// 1..15 with at least two directions
-static bool smear_dirmask_ok(int m) { return m >= 1 && m <= 15 && (m & (m - 1)) != 0; }
 static bool smear_alpha_ok(double a) { return a >= 0.0 && a <= 1.0; }    // false for a NaN
 
 }  // namespace l2q
@@ -166,10 +163,9 @@ int l2q_su3_ape_smear(const void* xn, double alpha, int dirmask, void* out, int 
   L2Q_REQUIRE(out != xn, L2Q_EINVAL, "out must not alias xn");
   L2Q_REQUIRE(su3_dims_ok(nb, T, X, Y, Z), L2Q_EINVAL, "non-positive size");
   L2Q_REQUIRE(smear_alpha_ok(alpha), L2Q_EINVAL, "alpha must be finite and in [0, 1]");
-  L2Q_REQUIRE(smear_dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
-  const int nd = (dirmask & 1) + ((dirmask >> 1) & 1) + ((dirmask >> 2) & 1) + ((dirmask >> 3) & 1);
-  return launch_smear<kApe>("l2q_su3_ape_smear", xn, nullptr, dirmask, alpha, 2 * (nd - 1), out, nb, T, X, Y, Z,
-                            stream);
+  L2Q_REQUIRE(dirmask_ok(dirmask), L2Q_EINVAL, "dirmask must be 1..15 with at least two directions");
+  return launch_smear<kApe>("l2q_su3_ape_smear", xn, nullptr, dirmask, alpha, 2 * (dirmask_count(dirmask) - 1), out, nb,
+                            T, X, Y, Z, stream);
 }
 
 int l2q_su3_hyp_level1(const void* xn, double alpha3, void* b1, int nb, int T, int X, int Y, int Z, void* stream) {

@@ -1,21 +1,25 @@
-// su3_subgroup.hpp -- what the checkerboard kernels of su3_heatbath.hip and su3_gaugefix.hip share: the periodic hop by
-// division, and the quaternions that stand for the SU(2) subgroups of SU(3).
+// su3_subgroup.hpp -- what the checkerboard kernels of su3_heatbath.hip and su3_gaugefix.hip share: the site of a
+// half-site index, and the quaternions that stand for the SU(2) subgroups of SU(3).
 //   A quaternion a is the block [[a0 + i a3, a2 + i a1], [-a2 + i a1, a0 - i a3]] at rows / columns i, j of the
 //   identity (embed(a)); for a 3 x 3 matrix W,
 //     r = ( Re(W_ii + W_jj), Im(W_ij + W_ji), Re(W_ij - W_ji), Im(W_ii - W_jj) ) / 2
 //   is the part of W that the subgroup sees: Re tr(embed(a) W) = const + 2 (a r)_0.
-// (The extraction of r and the product embed(a) U are written out in each kernel: su3_link_update_kernel fuses them
-// with its U A entries, and its fused multiply-adds are left exactly as they are.)
+// su2_part_unit extracts r and su2_embed_mul forms embed(a) U; su3_gaugefix_kernel uses both.  su3_link_update_kernel
+// deliberately keeps its own text of the same lines (subgroup_update): it fuses the extraction with its U A entries,
+// and going through either function, alone or together, changes the instruction stream of both of its variants
+// (profiles/site_kernels_single_source/).
 #pragma once
 #include "su3_links.hpp"
 
 namespace l2q {
 
-// periodic neighbour of site s in a direction of stride st and extent ext; dir = +1 / -1
-__device__ __forceinline__ int hb_hop(int s, int st, int ext, int dir) {
-  const int c = (s / st) % ext;
-  if (dir > 0) return c + 1 == ext ? s - (ext - 1) * st : s + st;
-  return c == 0 ? s + (ext - 1) * st : s - st;
+// The site of parity `parity` in the pair (2h, 2h + 1), which differ in z only (Z is even): one thread per half-site.
+__device__ __forceinline__ int checkerboard_site(int h, int parity, int X, int Y, int Z) {
+  int s = 2 * h;
+  int q = s / Z;
+  const int y = q % Y; q /= Y;
+  const int x = q % X; q /= X;
+  return s + ((parity - q - x - y) & 1);
 }
 
 struct Quat {
@@ -33,5 +37,29 @@ __device__ __forceinline__ Quat q_mul(const Quat& a, const Quat& b) {
 }
 
 __device__ __forceinline__ Quat q_conj(const Quat& a) { return Quat{a.q0, -a.q1, -a.q2, -a.q3}; }
+
+// k = |r| and rh = r / k of the subgroup part r of a matrix, from its four entries (ii, ij, ji, jj); rh = (1, 0, 0, 0)
+// where k is zero or not finite
+__device__ __forceinline__ double su2_part_unit(Quat& rh, double iir, double iii, double ijr, double iji, double jir,
+                                                double jii, double jjr, double jji) {
+  const double r0 = 0.5 * (iir + jjr), r1 = 0.5 * (iji + jii), r2 = 0.5 * (ijr - jir), r3 = 0.5 * (iii - jji);
+  const double k = sqrt(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
+  rh = Quat{1.0, 0.0, 0.0, 0.0};
+  if (k > 0.0 && k <= 1.7976931348623157e308) { rh.q0 = r0 / k; rh.q1 = r1 / k; rh.q2 = r2 / k; rh.q3 = r3 / k; }
+  return k;
+}
+
+// u <- embed(g) u: rows I and J
+template <int I, int J>
+__device__ __forceinline__ void su2_embed_mul(M3& u, const Quat& g) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double xr = u.re[3 * I + c], xi = u.im[3 * I + c], yr = u.re[3 * J + c], yi = u.im[3 * J + c];
+    u.re[3 * I + c] = g.q0 * xr - g.q3 * xi + g.q2 * yr - g.q1 * yi;
+    u.im[3 * I + c] = g.q0 * xi + g.q3 * xr + g.q2 * yi + g.q1 * yr;
+    u.re[3 * J + c] = -g.q2 * xr - g.q1 * xi + g.q0 * yr + g.q3 * yi;
+    u.im[3 * J + c] = -g.q2 * xi + g.q1 * xr + g.q0 * yi - g.q3 * yr;
+  }
+}
 
 }  // namespace l2q

@@ -1,7 +1,8 @@
-// TEST INFRASTRUCTURE: stand-in for <hip/hip_runtime.h> that RUNS the kernels of csrc/su3_clover_bwd.hip on the host
-// (tests/test_clover_bwd_emu.py; the header of tests/native_host/loops_emu): a launch executes the workgroups one after the other, every thread of a workgroup as an OS
-// thread with real barriers, `__shfl_down` through a per-wavefront exchange, `__shared__` as a static.  Only what
-// that file and the headers it includes use is provided.
+// TEST INFRASTRUCTURE: stand-in for <hip/hip_runtime.h> that RUNS the kernels of a csrc/su3_*.hip on the host (the
+// drivers of tests/native_host/*_emu/, built by tests/host_emu.py): a launch executes the workgroups one after the
+// other, every thread of a workgroup as an OS thread with real barriers, `__shfl_down` through a per-wavefront
+// exchange, `__shared__` as a static.  Only what those files and the headers they include use is provided.  (The
+// math-only stand-in of the link-math tests is tests/native_host/hip/hip_runtime.h.)
 #pragma once
 #include <barrier>
 #include <cmath>

@@ -1,26 +1,17 @@
-// TEST INFRASTRUCTURE: csrc/su3_flow_adaptive.hip compiled for the host against the stand-in HIP header of
-// tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), with the error text of common.hip restated
-// plainly.  Only the step's last kernel and its finalize are run here (l2q::launch_flow_step_err); the entry points
+// TEST INFRASTRUCTURE: csrc/su3_flow_adaptive.hip compiled for the host against the stand-in HIP header and the host
+// side of tests/native_host/emu/ (every thread of a workgroup an OS thread; the error text of common.hip restated, the
+// rest of the host side unused).  Only the step's last kernel and its finalize are run here (l2q::launch_flow_step_err); the entry points
 // that the whole step calls in other files (forward stage, force kick) are refused: their composition is the business
 // of tests/test_flow_adaptive_gpu.py.
 //   flow_adaptive_emu nb V eps w0 w2 p1 p2 p3 out_x out_d
 // reads five native-layout fields [nb][4][9][V] complex (raw float64), writes W3 to out_x and d [nb] to out_d, and
 // fails if an input changed, if the exact workspace was overrun, or if an aliased output or a short workspace passes.
-#include <cstdarg>
-#include <cstring>
-#include <string>
 #include "su3_flow_adaptive.hip"
-namespace l2q {
-static char g_err[512];
-void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); }
-}
+#include "emu_host.hpp"
 extern "C" {
-const char* l2q_last_error() { return l2q::g_err; }
 int l2q_su3_flow_stage(const void*, const void*, double, double, void*, void*, int, int, int, int, int, void*) { return L2Q_EINVAL; }
 int l2q_su3_force_kick_to(const void*, double, double, const void*, void*, int, int, int, int, int, void*) { return L2Q_EINVAL; }
 }
-static std::vector<double> rd(const char* f) { FILE* p = fopen(f, "rb"); if (!p) exit(3); fseek(p, 0, SEEK_END); long n = ftell(p); fseek(p, 0, SEEK_SET); std::vector<double> v(n / 8); if (fread(v.data(), 8, v.size(), p) != v.size()) exit(3); fclose(p); return v; }
-static void wr(const char* f, const std::vector<double>& v) { FILE* p = fopen(f, "wb"); fwrite(v.data(), 8, v.size(), p); fclose(p); }
 int main(int argc, char** argv) {
   if (argc != 11) { fprintf(stderr, "usage: flow_adaptive_emu nb V eps w0 w2 p1 p2 p3 out_x out_d\n"); return 2; }
   const int nb = atoi(argv[1]);
@@ -39,7 +30,7 @@ int main(int argc, char** argv) {
   std::vector<double> ws(wsb / 8, -7.0), out((size_t)nb * 72 * V, -7.0), d(nb, -7.0);
   int rc = l2q::launch_flow_step_err(w0.data(), w2.data(), p1.data(), p2.data(), p3.data(), eps, out.data(), d.data(),
                                      nb, V, ws.data(), wsb, nullptr);
-  if (rc) { fprintf(stderr, "rc %d %s\n", rc, l2q_last_error()); return 1; }
+  if (rc) return fail(rc);
   const std::vector<double>* now[5] = {&w0, &w2, &p1, &p2, &p3};
   for (int i = 0; i < 5; ++i)
     if (memcmp(now[i]->data(), keep[i].data(), keep[i].size() * 8)) { fprintf(stderr, "input %d was written\n", i); return 1; }

@@ -1,6 +1,6 @@
-// TEST INFRASTRUCTURE: csrc/su3_gaugefix.hip compiled for the host against the stand-in HIP header of
-// tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), with the three things it takes from
-// common.hip (error text, tuning table, the second reduction stage) restated plainly.
+// TEST INFRASTRUCTURE: csrc/su3_gaugefix.hip compiled for the host against the stand-in HIP header and the host side of
+// tests/native_host/emu/ (every thread of a workgroup an OS thread; error text, tuning table and the second reduction
+// stage of common.hip restated).
 //   gaugefix_emu what nb T X Y Z xcd_swizzle dirmask omega with_g with_active in_x in_g out_x out_g out_cond out_apply
 // reads a native-layout field (raw float64) from in_x and a transformation G[nb][9][V] from in_g; `what` is a sum of
 //   1: for parity 0, 1 one l2q_su3_gaugefix_sweep from in_x again; with_active = 1: the odd chains inactive (active =
@@ -8,22 +8,8 @@
 //      the two G to out_g (with_g = 0: in_g unchanged);
 //   2: out_cond = l2q_su3_gauge_condition of in_x, [nb][2];
 //   4: out_apply = l2q_su3_gauge_apply of in_x with in_g.
-#include <cstdarg>
-#include <cstring>
-#include <string>
 #include "su3_gaugefix.hip"
-namespace l2q {
-static char g_err[512];
-void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); }
-Tuning& tuning() { static Tuning t; return t; }
-void launch_finalize(const double* partial, double* out, int nb, long nblk, int ncomp, double scale, double offset, hipStream_t) {
-  for (int c = 0; c < nb; ++c) for (int k = 0; k < ncomp; ++k) { double s = 0; for (long b = 0; b < nblk; ++b) s += partial[(c * nblk + b) * ncomp + k]; out[c * ncomp + k] = scale * s + offset; }
-}
-}
-extern "C" const char* l2q_last_error() { return l2q::g_err; }
-static std::vector<double> rd(const char* f) { FILE* p = fopen(f, "rb"); if (!p) exit(3); fseek(p, 0, SEEK_END); long n = ftell(p); fseek(p, 0, SEEK_SET); std::vector<double> v(n / 8); if (fread(v.data(), 8, v.size(), p) != v.size()) exit(3); fclose(p); return v; }
-static void wr(const char* f, const std::vector<double>& v) { FILE* p = fopen(f, "wb"); fwrite(v.data(), 8, v.size(), p); fclose(p); }
-static int fail(int rc) { fprintf(stderr, "rc %d %s\n", rc, l2q_last_error()); return 1; }
+#include "emu_host.hpp"
 int main(int argc, char** argv) {
   if (argc != 18) { fprintf(stderr, "usage: see the head of gaugefix_emu.cpp\n"); return 2; }
   const int what = atoi(argv[1]);

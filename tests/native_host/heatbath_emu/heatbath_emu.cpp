@@ -1,25 +1,12 @@
-// TEST INFRASTRUCTURE: csrc/su3_heatbath.hip compiled for the host against the stand-in HIP header of
-// tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), with the three things it takes from
-// common.hip (error text, tuning table, the second reduction stage) restated plainly.
+// TEST INFRASTRUCTURE: csrc/su3_heatbath.hip compiled for the host against the stand-in HIP header and the host side of
+// tests/native_host/emu/ (every thread of a workgroup an OS thread; error text, tuning table and the second reduction
+// stage of common.hip restated).
 //   heatbath_emu <hb|hb_nofails|or> nb T X Y Z xcd_swizzle beta ntry in_x in_u out_x out_fails
 // reads a native-layout field (raw float64) from in_x and, for hb, the uniforms of the 8 launches (mu 0..3, parity
 // 0, 1; u[8][nb][3][4 ntry + 2][V/2]) from in_u; every launch starts from in_x again.  Writes the 8 updated fields to
 // out_x and the 8 x nb failure counts to out_fails.
-#include <cstdarg>
-#include <cstring>
-#include <string>
 #include "su3_heatbath.hip"
-namespace l2q {
-static char g_err[512];
-void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); }
-Tuning& tuning() { static Tuning t; return t; }
-void launch_finalize(const double* partial, double* out, int nb, long nblk, int ncomp, double scale, double offset, hipStream_t) {
-  for (int c = 0; c < nb; ++c) for (int k = 0; k < ncomp; ++k) { double s = 0; for (long b = 0; b < nblk; ++b) s += partial[(c * nblk + b) * ncomp + k]; out[c * ncomp + k] = scale * s + offset; }
-}
-}
-extern "C" const char* l2q_last_error() { return l2q::g_err; }
-static std::vector<double> rd(const char* f) { FILE* p = fopen(f, "rb"); if (!p) exit(3); fseek(p, 0, SEEK_END); long n = ftell(p); fseek(p, 0, SEEK_SET); std::vector<double> v(n / 8); if (fread(v.data(), 8, v.size(), p) != v.size()) exit(3); fclose(p); return v; }
-static void wr(const char* f, const std::vector<double>& v) { FILE* p = fopen(f, "wb"); fwrite(v.data(), 8, v.size(), p); fclose(p); }
+#include "emu_host.hpp"
 int main(int argc, char** argv) {
   if (argc != 14) { fprintf(stderr, "usage: see the head of heatbath_emu.cpp\n"); return 2; }
   const std::string mode = argv[1];
@@ -42,7 +29,7 @@ int main(int argc, char** argv) {
       if (mode == "or") rc = l2q_su3_overrelax(f.data(), mu, parity, nb, T, X, Y, Z, nullptr);
       else if (mode == "hb_nofails") rc = l2q_su3_heatbath(f.data(), beta, mu, parity, u.data() + l * per_u, ntry, nullptr, nb, T, X, Y, Z, nullptr, 0, nullptr);
       else rc = l2q_su3_heatbath(f.data(), beta, mu, parity, u.data() + l * per_u, ntry, of.data() + l * nb, nb, T, X, Y, Z, ws.data(), ws.size() * 8, nullptr);
-      if (rc) { fprintf(stderr, "rc %d %s\n", rc, l2q_last_error()); return 1; }
+      if (rc) return fail(rc);
       ox.insert(ox.end(), f.begin(), f.end());
     }
   wr(argv[12], ox);

@@ -1,6 +1,6 @@
-// TEST INFRASTRUCTURE: csrc/su3_smear.hip compiled for the host against the stand-in HIP header of
-// tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), with the two things it takes from
-// common.hip (error text, tuning table) restated plainly.
+// TEST INFRASTRUCTURE: csrc/su3_smear.hip compiled for the host against the stand-in HIP header and the host side of
+// tests/native_host/emu/ (every thread of a workgroup an OS thread; error text and tuning table of common.hip
+// restated).
 //   smear_emu nb T X Y Z xcd_swizzle masks alphas alpha1 alpha2 alpha3 in_x in_b1 in_b2 out_ape out_b1 out_b2 out_v
 // reads a native-layout link field (raw float64) from in_x and two decorated fields [nb][4][3][9][V] from in_b1, in_b2:
 //   out_ape = for each mask of the comma-separated list `masks` and the alpha at its place in the list `alphas`,
@@ -9,19 +9,8 @@
 //   out_b2  = l2q_su3_hyp_level2(in_x, in_b1, alpha2);
 //   out_v   = l2q_su3_hyp_level3(in_x, in_b2, alpha1).
 // Every output starts as -7 in every entry, so an entry that no thread wrote shows.
-#include <cstdarg>
-#include <cstring>
-#include <string>
 #include "su3_smear.hip"
-namespace l2q {
-static char g_err[512];
-void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); }
-Tuning& tuning() { static Tuning t; return t; }
-}
-extern "C" const char* l2q_last_error() { return l2q::g_err; }
-static std::vector<double> rd(const char* f) { FILE* p = fopen(f, "rb"); if (!p) exit(3); fseek(p, 0, SEEK_END); long n = ftell(p); fseek(p, 0, SEEK_SET); std::vector<double> v(n / 8); if (fread(v.data(), 8, v.size(), p) != v.size()) exit(3); fclose(p); return v; }
-static void wr(const char* f, const std::vector<double>& v) { FILE* p = fopen(f, "wb"); fwrite(v.data(), 8, v.size(), p); fclose(p); }
-static int fail(int rc) { fprintf(stderr, "rc %d %s\n", rc, l2q_last_error()); return 1; }
+#include "emu_host.hpp"
 int main(int argc, char** argv) {
   if (argc != 19) { fprintf(stderr, "usage: see the head of smear_emu.cpp\n"); return 2; }
   const int nb = atoi(argv[1]), T = atoi(argv[2]), X = atoi(argv[3]), Y = atoi(argv[4]), Z = atoi(argv[5]);

@@ -1,21 +1,18 @@
 """CPU run of the kernels of csrc/su3_flow_adaptive.hip themselves: the file is compiled for the host with g++ against
-the stand-in HIP header of tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), under
+the stand-in HIP header of tests/host_emu.py (every thread of a workgroup an OS thread), under
 AddressSanitizer and UBSan as a stand-alone program run as a child process, and the step's last kernel (W3, and the
 distance d to the embedded second-order result) is compared with tests/flow_adaptive_restatement.py.  Catches indexing,
 reduction and out-of-bounds mistakes without a GPU: V = 16 and 30 are a partial wavefront, 210 a partial block, 256 one
 whole block, 384 one and a half."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import flow_adaptive_restatement as far
 import flow_restatement as fr
+import host_emu
+from native_layout import pack, unpack
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NH = os.path.join(ROOT, 'tests', 'native_host')
 NB = 3
 EPS = 0.02
 SIZES = [16, 30, 210, 256, 384]
@@ -23,31 +20,13 @@ SIZES = [16, 30, 210, 256, 384]
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('flow_adaptive_emu')
-    exe = tmp / 'flow_adaptive_emu'
-    subprocess.run(['g++', '-std=c++20', '-O1', '-g', '-pthread', '-fsanitize=address,undefined',
-                    '-fno-sanitize-recover=undefined', '-I', os.path.join(NH, 'loops_emu'),
-                    '-I', os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc'),
-                    os.path.join(NH, 'flow_adaptive_emu', 'flow_adaptive_emu.cpp'), '-o', str(exe)], check=True)
+    exe = host_emu.build(tmp_path_factory.mktemp('flow_adaptive_emu'), 'flow_adaptive_emu')
 
     def run(V, fields):
-        names = [str(tmp / f'in{i}.bin') for i in range(5)]
-        for n, f in zip(names, fields):
-            pack(f).view(np.float64).tofile(n)
-        fo, fd = str(tmp / 'x.bin'), str(tmp / 'd.bin')
-        subprocess.run([str(exe), str(NB), str(V), repr(EPS), *names, fo, fd], check=True)
-        return unpack(np.fromfile(fo).view(np.complex128).reshape(NB, 4, 9, V)), np.fromfile(fd)
+        """fields: five x[nb, 4, V, 3, 3] (torch); returns W3 in the same shape (numpy) and d [nb]"""
+        x, d = host_emu.run(exe, [NB, V, repr(EPS)], [pack(f) for f in fields], 2)
+        return unpack(x.view(np.complex128).reshape(NB, 4, 9, V), (V,)), d
     return run
-
-
-def pack(x):
-    """x[nb, 4, V, 3, 3] (torch) -> the native layout xn[nb, 4, 9, V] (numpy)"""
-    x = x.numpy()
-    return np.ascontiguousarray(x.reshape(x.shape[0], 4, -1, 9).transpose(0, 1, 3, 2))
-
-
-def unpack(xn):
-    return np.ascontiguousarray(xn.transpose(0, 1, 3, 2)).reshape(xn.shape[0], 4, -1, 3, 3)
 
 
 def fields(V, seed):

@@ -1,23 +1,19 @@
 """CPU run of the kernel of l2q_su3_force_vjp (csrc/su3_flow_bwd.hip) itself: the file is compiled for the host with
-g++ against the stand-in HIP header of tests/native_host/clover_bwd_emu/ (every thread of a workgroup an OS thread),
+g++ against the stand-in HIP header of tests/host_emu.py (every thread of a workgroup an OS thread),
 under AddressSanitizer and UBSan as a stand-alone program (tests/native_host/flow_bwd_emu/), and compared with
 torch.autograd of sum Re(conj(gf) F), F = (beta/3) tah(x @ staples(x)) of the restatement tests/flow_restatement.py.
 Catches wrong terms, signs, indexing, wrap-around and out-of-bounds mistakes without a GPU; the GPU's own arithmetic
 and the stage / step reverses built on the kernel are the business of tests/test_flow_bwd_gpu.py.  The kernel has one
 variant, so no lattice is needed to select another."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import flow_restatement as fr
+import host_emu
+from native_layout import pack
 from oracle import su3 as osu3
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, 'tests', 'native_host', 'flow_bwd_emu')
-HIP_STANDIN = os.path.join(ROOT, 'tests', 'native_host', 'clover_bwd_emu')
 NB = 2
 BETA = 2.7
 # extents 1 and 2 (the same link several times in one loop), a lattice that is no whole workgroup, and one of
@@ -27,27 +23,12 @@ LATTICES = [(1, 3, 2, 5), (3, 5, 2, 7), (2, 5, 8, 8)]
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('flow_bwd_emu')
-    exe = tmp / 'flow_bwd_emu'
-    subprocess.run(['g++', '-std=c++20', '-O1', '-g', '-pthread', '-fsanitize=address,undefined',
-                    '-fno-sanitize-recover=undefined', '-I', HIP_STANDIN,
-                    '-I', os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc'),
-                    os.path.join(EMU, 'flow_bwd_emu.cpp'), '-o', str(exe)], check=True)
+    exe = host_emu.build(tmp_path_factory.mktemp('flow_bwd_emu'), 'flow_bwd_emu')
 
     def run(L, swz, xn, gf, gx):
-        fx, ff, fg, fo = (str(tmp / n) for n in ('x.bin', 'f.bin', 'g.bin', 'o.bin'))
-        torch.view_as_real(xn).numpy().tofile(fx)
-        torch.view_as_real(gf).numpy().tofile(ff)
-        torch.view_as_real(gx).numpy().tofile(fg)
-        subprocess.run([str(exe), str(xn.shape[0]), *map(str, L), str(swz), repr(BETA), fx, ff, fg, fo], check=True)
-        return torch.view_as_complex(torch.from_numpy(np.fromfile(fo)).reshape(*gx.shape, 2))
+        (out,) = host_emu.run(exe, [xn.shape[0], *L, swz, repr(BETA)], [xn, gf, gx], 1)
+        return torch.view_as_complex(torch.from_numpy(out).reshape(*gx.shape, 2))
     return run
-
-
-def pack(x):
-    """x[nb, 4, T, X, Y, Z, 3, 3] -> the native layout xn[nb, 4, 9, V]"""
-    nb = x.shape[0]
-    return x.reshape(nb, 4, -1, 9).permute(0, 1, 3, 2).contiguous()
 
 
 def cnormal(rng, shape):

@@ -49,10 +49,6 @@ def cnormal(rng, shape):
     return torch.from_numpy(rng.normal(size=shape) + 1j * rng.normal(size=shape))
 
 
-def unpack(gn, L):
-    return gn.permute(0, 1, 3, 2).reshape(gn.shape[0], 4, *L, 3, 3)
-
-
 # ------------------------------------------------------------------ l2q_su3_force_vjp
 @functools.lru_cache(maxsize=None)
 def force_reference(L):

@@ -1,18 +1,15 @@
 """CPU run of the kernels of csrc/su3_gaugefix.hip themselves: the file is compiled for the host with g++ against the
-stand-in HIP header of tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), under AddressSanitizer
+stand-in HIP header of tests/host_emu.py (every thread of a workgroup an OS thread), under AddressSanitizer
 and UBSan as a stand-alone program run as a child process, and the three entry points are compared with the
 restatement tests/gaugefix_restatement.py.  Catches indexing, checkerboard, wrap-around and out-of-bounds mistakes
 without a GPU.  The update has no data-dependent accept decision: every link enters every comparison."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import gaugefix_restatement as gf
+import host_emu
+from native_layout import pack, pack_g, unpack, unpack_g
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NH = os.path.join(ROOT, 'tests', 'native_host')
 NB = 3
 # x + mu == x - mu; V/2 = 48: a partial wavefront, with the short extents in different places
 LATTICES = [(2, 2, 2, 2), (4, 2, 6, 2), (2, 4, 2, 6)]
@@ -21,43 +18,16 @@ OMEGAS = [1.0, 1.7]
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('gaugefix_emu')
-    exe = tmp / 'gaugefix_emu'
-    subprocess.run(['g++', '-std=c++20', '-O1', '-g', '-pthread', '-fsanitize=address,undefined',
-                    '-fno-sanitize-recover=undefined', '-I', os.path.join(NH, 'loops_emu'),
-                    '-I', os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc'),
-                    os.path.join(NH, 'gaugefix_emu', 'gaugefix_emu.cpp'), '-o', str(exe)], check=True)
+    exe = host_emu.build(tmp_path_factory.mktemp('gaugefix_emu'), 'gaugefix_emu')
 
     def run(what, L, swz, mask, omega, with_g, with_active, xn, gn):
         """what: 1 the two half-sweeps, 2 the condition, 4 the transformation (a sum of them)"""
-        fx, fg, ox, og, oc, oa = (str(tmp / n) for n in ('x.bin', 'g.bin', 'ox.bin', 'og.bin', 'oc.bin', 'oa.bin'))
-        xn.view(np.float64).tofile(fx)
-        gn.view(np.float64).tofile(fg)
-        subprocess.run([str(exe), str(what), str(NB), *map(str, L), str(swz), str(mask), repr(float(omega)),
-                        str(int(with_g)), str(int(with_active)), fx, fg, ox, og, oc, oa], check=True)
+        ox, og, oc, oa = host_emu.run(exe, [what, NB, *L, swz, mask, repr(float(omega)), int(with_g),
+                                            int(with_active)], [xn, gn], 4)
         V = int(np.prod(L))
-        return (np.fromfile(ox).view(np.complex128).reshape(-1, NB, 4, 9, V),
-                np.fromfile(og).view(np.complex128).reshape(-1, NB, 9, V), np.fromfile(oc).reshape(NB, 2),
-                np.fromfile(oa).view(np.complex128).reshape(NB, 4, 9, V))
+        return (ox.view(np.complex128).reshape(-1, NB, 4, 9, V), og.view(np.complex128).reshape(-1, NB, 9, V),
+                oc.reshape(NB, 2), oa.view(np.complex128).reshape(NB, 4, 9, V))
     return run
-
-
-def pack(x):
-    """x[nb, 4, T, X, Y, Z, 3, 3] -> the native layout xn[nb, 4, 9, V]"""
-    return np.ascontiguousarray(x.reshape(x.shape[0], 4, -1, 9).transpose(0, 1, 3, 2))
-
-
-def unpack(xn, L):
-    return np.ascontiguousarray(xn.transpose(0, 1, 3, 2)).reshape(xn.shape[0], 4, *L, 3, 3)
-
-
-def pack_g(g):
-    """g[nb, T, X, Y, Z, 3, 3] -> gn[nb, 9, V]"""
-    return np.ascontiguousarray(g.reshape(g.shape[0], -1, 9).transpose(0, 2, 1))
-
-
-def unpack_g(gn, L):
-    return np.ascontiguousarray(gn.transpose(0, 2, 1)).reshape(gn.shape[0], *L, 3, 3)
 
 
 @pytest.mark.parametrize('L', LATTICES)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import gaugefix_restatement as gf
+from native_layout import pack_g, unpack_g
 
 gpu = pytest.mark.gpu
 NB = 3
@@ -40,20 +41,12 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def pack_g(g):
-    return dev(g.reshape(g.shape[0], -1, 9).transpose(0, 2, 1))
-
-
-def unpack_g(gn, L):
-    return np.ascontiguousarray(host(gn).transpose(0, 2, 1)).reshape(gn.shape[0], *L, 3, 3)
-
-
 @gpu
 @pytest.mark.parametrize('L', LATTICES)
 def test_kernels_against_restatement(L):
     from l2hmc import _ops as ops
     x, g0, sweeps, conds, applied = reference(L)
-    xn0, gn0 = ops.su3_pack(dev(x)), pack_g(g0)
+    xn0, gn0 = ops.su3_pack(dev(x)), dev(pack_g(g0))
     active = torch.tensor([1, 0, 1], dtype=torch.int32, device='cuda')
     worst = [0.0, 0.0, 0.0, 0.0, 0.0]
     for mask in gf.MASKS:
@@ -69,7 +62,7 @@ def test_kernels_against_restatement(L):
                     assert dx <= 1e-11, (mask, omega, parity, dx)
                     worst[0] = max(worst[0], dx)
                     if with_g:
-                        dg = float(np.abs(unpack_g(gn, L)[0::2] - (wg @ g0)[0::2]).max())
+                        dg = float(np.abs(unpack_g(host(gn), L)[0::2] - (wg @ g0)[0::2]).max())
                         assert dg <= 1e-11, (mask, omega, parity, dg)
                         worst[1] = max(worst[1], dg)
                     else:

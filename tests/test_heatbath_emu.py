@@ -1,18 +1,15 @@
 """CPU run of the kernels of csrc/su3_heatbath.hip themselves: the file is compiled for the host with g++ against the
-stand-in HIP header of tests/native_host/loops_emu/ (every thread of a workgroup an OS thread), under AddressSanitizer
+stand-in HIP header of tests/host_emu.py (every thread of a workgroup an OS thread), under AddressSanitizer
 and UBSan as a stand-alone program run as a child process, and both entry points are compared with the restatement
 tests/heatbath_restatement.py from the same uniforms.  Catches indexing, checkerboard, wrap-around and out-of-bounds
 mistakes without a GPU; the argument checks are those of the real cross-compiled library."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import heatbath_restatement as hb
+import host_emu
+from native_layout import pack, unpack
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NH = os.path.join(ROOT, 'tests', 'native_host')
 NB = 3
 # x + nu == x - nu; V/2 = 48: a partial wavefront, with the short extents in different places
 LATTICES = [(2, 2, 2, 2), (4, 2, 6, 2), (2, 4, 2, 6)]
@@ -21,31 +18,13 @@ CASES = [(0.3, 1), (5.7, 4)]
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('heatbath_emu')
-    exe = tmp / 'heatbath_emu'
-    subprocess.run(['g++', '-std=c++20', '-O1', '-g', '-pthread', '-fsanitize=address,undefined',
-                    '-fno-sanitize-recover=undefined', '-I', os.path.join(NH, 'loops_emu'),
-                    '-I', os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc'),
-                    os.path.join(NH, 'heatbath_emu', 'heatbath_emu.cpp'), '-o', str(exe)], check=True)
+    exe = host_emu.build(tmp_path_factory.mktemp('heatbath_emu'), 'heatbath_emu')
 
     def run(mode, L, swz, beta, ntry, xn, u):
-        fx, fu, fo, ff = (str(tmp / n) for n in ('x.bin', 'u.bin', 'o.bin', 'f.bin'))
-        xn.view(np.float64).tofile(fx)
-        (u if u is not None else np.zeros(1)).tofile(fu)
-        subprocess.run([str(exe), mode, str(NB), *map(str, L), str(swz), repr(float(beta)), str(ntry), fx, fu, fo, ff],
-                       check=True)
-        V = int(np.prod(L))
-        return (np.fromfile(fo).view(np.complex128).reshape(8, NB, 4, 9, V), np.fromfile(ff).reshape(8, NB))
+        ox, of = host_emu.run(exe, [mode, NB, *L, swz, repr(float(beta)), ntry],
+                              [xn, u if u is not None else np.zeros(1)], 2)
+        return ox.view(np.complex128).reshape(8, NB, 4, 9, int(np.prod(L))), of.reshape(8, NB)
     return run
-
-
-def pack(x):
-    """x[nb, 4, T, X, Y, Z, 3, 3] -> the native layout xn[nb, 4, 9, V]"""
-    return np.ascontiguousarray(x.reshape(x.shape[0], 4, -1, 9).transpose(0, 1, 3, 2))
-
-
-def unpack(xn, L):
-    return np.ascontiguousarray(xn.transpose(0, 1, 3, 2)).reshape(xn.shape[0], 4, *L, 3, 3)
 
 
 def compare(got, want, x, mu, parity, L, skip=None):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import heatbath_restatement as hb
+from native_layout import pack, unpack
 from oracle import su3 as osu3
 
 gpu = pytest.mark.gpu
@@ -37,16 +38,6 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def pack_gpu(x):
-    from l2hmc import _ops as ops
-    return ops.su3_pack(dev(x))
-
-
-def unpack_host(xn, L):
-    from l2hmc import _ops as ops
-    return host(ops.su3_unpack(xn, L))
-
-
 def split(new, old, mu, parity, L):
     """(updated links of new, of old, every other link of new, of old)"""
     V = int(np.prod(L))
@@ -72,14 +63,14 @@ def test_heatbath_kernel_against_restatement(L, case):
     from l2hmc import _ops as ops
     beta, ntry = CASES[case]
     x, u, want = reference(L, case)
-    xn0 = pack_gpu(x)
+    xn0 = dev(pack(x))
     vh = int(np.prod(L)) // 2
     worst = 0.0
     for l in range(8):
         mu, parity = l // 2, l % 2
         xn = xn0.clone()
         fails = host(ops.su3_heatbath_(xn, beta, mu, parity, dev(u[l]), ntry, L))
-        got = unpack_host(xn, L)
+        got = unpack(host(xn), L)
         wx, wf, margin = want[l]
         skip = margin.min((1, 2)) < 1e-12
         LEFT_OUT[0] += int(skip.sum())
@@ -101,14 +92,14 @@ def test_heatbath_kernel_against_restatement(L, case):
 def test_overrelax_kernel(L):
     from l2hmc import _ops as ops
     x = reference(L, 0)[0]
-    xn0 = pack_gpu(x)
+    xn0 = dev(pack(x))
     s0 = osu3.action(x, 1.0)
     worst = [0.0, 0.0, 0.0]
     for l in range(8):
         mu, parity = l // 2, l % 2
         xn = xn0.clone()
         ops.su3_overrelax_(xn, mu, parity, L)
-        got = unpack_host(xn, L)
+        got = unpack(host(xn), L)
         g_upd, x_upd, g_rest, x_rest = split(got, x, mu, parity, L)
         assert np.array_equal(g_rest, x_rest), (mu, parity)
         assert (np.abs(g_upd - x_upd).max((-2, -1)) > 1e-6).all()

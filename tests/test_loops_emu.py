@@ -1,20 +1,17 @@
 """CPU run of the kernels of csrc/su3_loops.hip themselves: the file is compiled for the host with g++ against a
-stand-in HIP header that executes every thread of a workgroup as an OS thread (tests/native_host/loops_emu/), under
+stand-in HIP header that executes every thread of a workgroup as an OS thread (tests/host_emu.py), under
 AddressSanitizer and UBSan as a stand-alone program, and its three entry points are compared with the restatement
 tests/loops_restatement.py.  Catches indexing, wrap-around and out-of-bounds mistakes without a GPU; rounding of the
 GPU's own arithmetic is the business of tests/test_loops_gpu.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+import host_emu
 import loops_restatement as lr
+from native_layout import pack, unpack
 from oracle import su3 as osu3
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, 'tests', 'native_host', 'loops_emu')
 NB = 2
 # extents 1 and 2, a lattice that is no whole workgroup, and one of several workgroups per chain
 LATTICES = [(1, 3, 2, 5), (3, 5, 2, 7), (2, 5, 8, 8)]
@@ -22,30 +19,12 @@ LATTICES = [(1, 3, 2, 5), (3, 5, 2, 7), (2, 5, 8, 8)]
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp('loops_emu')
-    exe = tmp / 'loops_emu'
-    subprocess.run(['g++', '-std=c++20', '-O1', '-g', '-pthread', '-fsanitize=address,undefined',
-                    '-fno-sanitize-recover=undefined', '-I', EMU, '-I', os.path.join(ROOT, 'l2hmc-qcd_amd', 'csrc'),
-                    os.path.join(EMU, 'loops_emu.cpp'), '-o', str(exe)], check=True)
+    exe = host_emu.build(tmp_path_factory.mktemp('loops_emu'), 'loops_emu')
 
     def run(mode, L, p1, p2, swz, a, b):
-        fa, fb, fo = (str(tmp / n) for n in ('a.bin', 'b.bin', 'o.bin'))
-        torch.view_as_real(a).numpy().tofile(fa)
-        torch.view_as_real(b).numpy().tofile(fb)
-        subprocess.run([str(exe), mode, str(a.shape[0]), *map(str, L), str(p1), str(p2), str(swz), fa, fb, fo],
-                       check=True)
-        return torch.from_numpy(np.fromfile(fo))
+        (out,) = host_emu.run(exe, [mode, a.shape[0], *L, p1, p2, swz], [a, b], 1)
+        return torch.from_numpy(out)
     return run
-
-
-def pack(x):
-    """x[nb, 4, T, X, Y, Z, 3, 3] -> the native layout xn[nb, 4, 9, V]"""
-    nb = x.shape[0]
-    return x.reshape(nb, 4, -1, 9).permute(0, 1, 3, 2).contiguous()
-
-
-def unpack(xn, L):
-    return xn.permute(0, 1, 3, 2).reshape(xn.shape[0], 4, *L, 3, 3).contiguous()
 
 
 @pytest.mark.parametrize('L', LATTICES)

@@ -15,6 +15,7 @@ import torch
 import gaugefix_restatement as gf
 import loops_restatement as lr
 import smear_restatement as sm
+from native_layout import pack_dec, unpack_dec
 
 gpu = pytest.mark.gpu
 NB = 3
@@ -51,15 +52,6 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def pack_dec(b):
-    a = sm.dec_stack(b)
-    return dev(a.reshape(a.shape[0], 4, 3, -1, 9).transpose(0, 1, 2, 4, 3))
-
-
-def unpack_dec(bn, L):
-    return np.ascontiguousarray(host(bn).transpose(0, 1, 2, 4, 3)).reshape(bn.shape[0], 4, 3, *L, 3, 3)
-
-
 @gpu
 @pytest.mark.parametrize('L', sm.GPU_LATTICES)
 def test_kernels_against_restatement(L):
@@ -77,9 +69,10 @@ def test_kernels_against_restatement(L):
         d = float(np.abs(got - want).max())
         assert d <= sm.TOL['ape'], (alpha, D, d)
         worst['ape'] = max(worst['ape'], d)
-    b1n, b2n = pack_dec(b1), pack_dec(b2)
-    worst['level1'] = float(np.abs(unpack_dec(ops.su3_hyp_level1_n(xn, a3, L), L) - sm.dec_stack(b1)).max())
-    worst['level2'] = float(np.abs(unpack_dec(ops.su3_hyp_level2_n(xn, b1n, a2, L), L) - sm.dec_stack(b2)).max())
+    b1n, b2n = dev(pack_dec(sm.dec_stack(b1))), dev(pack_dec(sm.dec_stack(b2)))
+    worst['level1'] = float(np.abs(unpack_dec(host(ops.su3_hyp_level1_n(xn, a3, L)), L) - sm.dec_stack(b1)).max())
+    worst['level2'] = float(np.abs(unpack_dec(host(ops.su3_hyp_level2_n(xn, b1n, a2, L)), L)
+                                   - sm.dec_stack(b2)).max())
     worst['level3'] = float(np.abs(host(ops.su3_unpack(ops.su3_hyp_level3_n(xn, b2n, a1, L), L)) - v).max())
     print(f'{L}: worst deviation / tolerance: ' + ', '.join(f'{k} {worst[k] / sm.TOL[k]:.3g}' for k in worst))
     for k in ('level1', 'level2', 'level3'):
