@@ -399,6 +399,36 @@ int l2q_su3_hyp_level2(const void* xn, const void* b1, double alpha2, void* b2, 
 int l2q_su3_hyp_level3(const void* xn, const void* b2, double alpha1, void* out, int nb, int T, int X, int Y, int Z,
                        void* stream);
 
+/* ---------------------------------------------------------------- SU(3) Wilson fermions */
+/* csrc/su3_wilson.hip.  Spinor fields are psi[nb][nrhs][12][V] complex128, component 3 spin + colour, the site index of
+ * the links; a system is one (chain, rhs) pair.  The Wilson-Dirac operator on the links xn (thin or smeared):
+ *   M psi = psi - kappa H psi,
+ *   H psi(x) = sum_mu [(1 - gamma_mu) U_mu(x) psi(x+mu) + (1 + gamma_mu) U_mu(x-mu)^H psi(x-mu)].
+ * Gamma matrices: Hermitian, chiral, gamma_mu = [[0, B_mu], [B_mu^H, 0]] in 2 x 2 blocks with B_0 = 1 (direction 0 is T)
+ * and B_k = -i sigma_k for k = 1, 2, 3 (x, y, z); gamma5 = gamma_0 gamma_1 gamma_2 gamma_3 = diag(-1, -1, 1, 1).
+ * flags bit 0 (dagger): M^H = gamma5 M gamma5, the two projector signs swapped.  flags bit 1: antiperiodic in direction
+ * 0, every hop across the t = T-1 -> 0 seam, either way, takes a factor -1; otherwise periodic.  Any extents: with an
+ * extent of 1 or 2 the forward and the backward neighbour coincide and both terms are added (T = 1: both carry the sign).
+ * H does not depend on the gauge action.  Out of place.  One thread per (system, site), 1320 flops; algorithmic traffic
+ * per (system, site) 384 B of spinors (read once, written once; the eight neighbours come from cache) and 576 B of
+ * links, which the nrhs systems of a chain share.
+ * norm_part (may be null): [nb][nrhs][parts] partial sums of |out|^2, one per workgroup, parts =
+ * l2q_su3_wilson_norm_parts(T, X, Y, Z) = ceil(V / 256) (0 for extents the kernels refuse).  A workgroup belongs to one
+ * system and sums in a fixed order: a system's partials are the same bits whatever else the batch holds.
+ * L2Q_EINVAL, before any HIP call: a null xn, psi or out; out aliasing psi (or xn); a non-positive size; nb * nrhs *
+ * 12 * V of 2^31 or more; kappa not finite; flags outside 0..3. */
+long l2q_su3_wilson_norm_parts(int T, int X, int Y, int Z);
+int l2q_su3_wilson_apply(const void* xn, const void* psi, void* out, double* norm_part, double kappa, int flags, int nb,
+                         int nrhs, int T, int X, int Y, int Z, void* stream);
+/* One pass of a CG iteration over nsys systems of V sites: x += alpha[s] p, r -= alpha[s] q, and rr_part[nsys][ceil(V /
+ * 256)] = partial sums of |r|^2 of the new r, in the fixed order of the apply's.  alpha is a device array [nsys] of
+ * doubles.  alpha[s] = 0 leaves x and r of that system the same bits.  L2Q_EINVAL: a null pointer; x or r aliasing
+ * another field; a non-positive size or nsys * 12 * V of 2^31 or more. */
+int l2q_su3_spinor_cg_update(void* x, void* r, const void* p, const void* q, const double* alpha, double* rr_part,
+                             long nsys, long V, void* stream);
+/* p = z + beta[s] p, beta a device array [nsys] of doubles.  L2Q_EINVAL as above (p must not alias z). */
+int l2q_su3_spinor_xpay(void* p, const void* z, const double* beta, long nsys, long V, void* stream);
+
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:
  *   forward : v' = exp(eps s/2) v - (eps/2) (F exp(eps q) + t),  logdet[c] =  sum eps s/2

@@ -606,6 +606,102 @@ def su3_hyp_level3_n(xn: torch.Tensor, b2: torch.Tensor, alpha1: float, lat: Seq
     return out
 
 
+# ---------------------------------------------------------------------------- Wilson fermions
+def su3_spinor_pack(psi: torch.Tensor) -> torch.Tensor:
+    """psi[nb, nrhs, T, X, Y, Z, 4, 3] c128 -> psin[nb, nrhs, 12, V] (component 3 spin + colour); a new tensor"""
+    if psi.dim() != 8 or tuple(psi.shape[-2:]) != (4, 3):
+        raise ValueError(f'su3_spinor_pack: need [nb, nrhs, T, X, Y, Z, 4, 3], got {list(psi.shape)}')
+    nb, nrhs = psi.shape[:2]
+    return psi.to(C128).reshape(nb, nrhs, -1, 12).transpose(2, 3).contiguous()
+
+
+def su3_spinor_unpack(psin: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
+    nb, nrhs = psin.shape[:2]
+    return psin.transpose(2, 3).contiguous().reshape(nb, nrhs, *[int(i) for i in lat], 4, 3)
+
+
+def su3_wilson_norm_parts(lat: Sequence[int]) -> int:
+    """partial sums per system that the spinor kernels leave on this lattice"""
+    parts = int(N.load().l2q_su3_wilson_norm_parts(*(int(i) for i in lat)))
+    if parts <= 0:
+        raise N.L2QError(f'l2q_su3_wilson_norm_parts: bad extents {list(lat)}')
+    return parts
+
+
+def _spinor_check(what: str, name: str, t: torch.Tensor, shape) -> None:
+    if t.dtype != C128 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{what}: {name} must be contiguous complex128 {list(shape)}, got {t.dtype} {list(t.shape)}')
+
+
+def su3_wilson_apply_n(xn: torch.Tensor, psin: torch.Tensor, kappa: float, lat: Sequence[int], dagger: bool = False,
+                       antiperiodic_t: bool = True, out: Optional[torch.Tensor] = None, norm: bool = False):
+    """M psi (dagger: M^H psi) of the native spinor field psin[nb, nrhs, 12, V] on the native links xn (see l2q.h).  Out
+    of place: out None = a new field, never psin.  With norm=True returns (out, part), part[nb, nrhs, parts] the
+    per-workgroup partial sums of |out|^2 of each system; norm may also be the tensor to write them to."""
+    T, X, Y, Z = (int(i) for i in lat)
+    if psin.dim() != 4 or psin.shape[0] != xn.shape[0] or psin.shape[2] != 12 or psin.shape[3] != xn.shape[-1]:
+        raise ValueError(f'su3_wilson_apply_n: need psin [nb, nrhs, 12, V] on xn {list(xn.shape)}, got {list(psin.shape)}')
+    _spinor_check('su3_wilson_apply_n', 'psin', psin, psin.shape)
+    if out is None:
+        out = torch.empty_like(psin)
+    else:
+        _spinor_check('su3_wilson_apply_n', 'out', out, psin.shape)
+    nb, nrhs = psin.shape[:2]
+    part = None
+    if isinstance(norm, torch.Tensor):
+        part = norm
+        want = (nb, nrhs, su3_wilson_norm_parts(lat))
+        if part.dtype != torch.float64 or tuple(part.shape) != want or not part.is_contiguous():
+            raise ValueError(f'su3_wilson_apply_n: norm must be contiguous float64 {list(want)}, got {list(part.shape)}')
+    elif norm:
+        part = torch.empty((nb, nrhs, su3_wilson_norm_parts(lat)), dtype=torch.float64, device=psin.device)
+    N.call('l2q_su3_wilson_apply', xn, psin, out, part, float(kappa), int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1),
+           nb, nrhs, T, X, Y, Z)
+    return out if part is None else (out, part)
+
+
+def su3_spinor_cg_update_(x: torch.Tensor, r: torch.Tensor, p: torch.Tensor, q: torch.Tensor, alpha: torch.Tensor,
+                          part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x += alpha_s p, r -= alpha_s q in place on native spinor fields [nb, nrhs, 12, V], alpha[nb, nrhs] float64 on the
+    device; returns the partial sums [nb, nrhs, parts] of |r|^2 of the new r"""
+    for name, t in (('x', x), ('r', r), ('p', p), ('q', q)):
+        _spinor_check('su3_spinor_cg_update_', name, t, x.shape)
+    nb, nrhs, _, V = x.shape
+    if alpha.dtype != torch.float64 or alpha.numel() != nb * nrhs or not alpha.is_contiguous():
+        raise ValueError(f'su3_spinor_cg_update_: alpha must be contiguous float64 [{nb}, {nrhs}]')
+    parts = -(-V // 256)
+    if part is None:
+        part = torch.empty((nb, nrhs, parts), dtype=torch.float64, device=x.device)
+    elif part.dtype != torch.float64 or tuple(part.shape) != (nb, nrhs, parts) or not part.is_contiguous():
+        raise ValueError(f'su3_spinor_cg_update_: part must be contiguous float64 {[nb, nrhs, parts]}')
+    N.call('l2q_su3_spinor_cg_update', x, r, p, q, alpha, part, nb * nrhs, V)
+    return part
+
+
+def su3_spinor_xpay_(p: torch.Tensor, z: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """p = z + beta_s p in place, beta[nb, nrhs] float64 on the device"""
+    _spinor_check('su3_spinor_xpay_', 'p', p, p.shape)
+    _spinor_check('su3_spinor_xpay_', 'z', z, p.shape)
+    nb, nrhs, _, V = p.shape
+    if beta.dtype != torch.float64 or beta.numel() != nb * nrhs or not beta.is_contiguous():
+        raise ValueError(f'su3_spinor_xpay_: beta must be contiguous float64 [{nb}, {nrhs}]')
+    N.call('l2q_su3_spinor_xpay', p, z, beta, nb * nrhs, V)
+    return p
+
+
+def sum_parts(part: torch.Tensor) -> torch.Tensor:
+    """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
+    partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""
+    if part.shape[-1] == 1:
+        return part[..., 0].clone()
+    while part.shape[-1] > 1:
+        n = part.shape[-1]
+        h = n // 2
+        s = part[..., :h] + part[..., h:2 * h]
+        part = torch.cat((s, part[..., 2 * h:]), -1) if n & 1 else s
+    return part[..., 0]
+
+
 # ---------------------------------------------------------------------------- shared
 def v_update_(v: torch.Tensor, force: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
               q: torch.Tensor, eps: float, forward: bool) -> torch.Tensor:

@@ -98,6 +98,23 @@ def static_potential(w: Tensor) -> Tensor:
     return _log_positive(w[..., :, :-1] / w[..., :, 1:])
 
 
+def pion_correlator(S: Tensor, t_source: int = 0) -> Tensor:
+    """C(t) = sum_x sum_{spins, colours} |S(x, t_source + t)|^2 [nb, T] of a point-to-all propagator S[nb, T, X, Y, Z, 4,
+    3, 4, 3] (`LatticeSU3.quark_propagator`), t counted from the source's time slice (periodically).  By gamma5-
+    Hermiticity this is the pseudoscalar two-point function; it is positive."""
+    S = torch.as_tensor(S)
+    if S.dim() != 9 or tuple(S.shape[-4:]) != (4, 3, 4, 3):
+        raise ValueError(f'pion_correlator: need S [nb, T, X, Y, Z, 4, 3, 4, 3], got {list(S.shape)}')
+    c = (S.real ** 2 + S.imag ** 2).sum(tuple(range(2, 9)))
+    return torch.roll(c, -int(t_source), 1)
+
+
+def effective_mass(C: Tensor) -> Tensor:
+    """m_eff(t) = ln[C(t) / C(t+1)] from C[..., T]: [..., T-1].  NaN where the ratio is not positive; never raises."""
+    C = torch.as_tensor(C)
+    return _log_positive(C[..., :-1] / C[..., 1:])
+
+
 def _first_upward_crossing(t: Tensor, g: Tensor, target: float) -> Tensor:
     """[nb]: where g[k, nb] on the points t[k] first goes from below `target` to at or above it, linearly interpolated
     between the two points; NaN for a chain with no such pair"""
@@ -606,6 +623,166 @@ class LatticeSU3(Lattice):
         if xh is None:
             return self.wilson_loop_table(xa, rmax, tmax, time_dir)
         return self.wilson_loop_table_xt(xa, xh, rmax, tmax, time_dir)
+
+    # ------------------------------------------------------------ Wilson fermions
+    @staticmethod
+    def gamma_matrices() -> Tensor:
+        """[5, 4, 4] complex128 (CPU): gamma_0 (T), gamma_1, gamma_2, gamma_3 (x, y, z) and gamma5 = g0 g1 g2 g3 =
+        diag(-1, -1, 1, 1), the Hermitian chiral basis of csrc/su3_wilson.hip: gamma_mu = [[0, B_mu], [B_mu^H, 0]] with
+        B_0 = 1, B_k = -i sigma_k."""
+        sig = torch.tensor([[[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]], dtype=torch.complex128)
+        blocks = [torch.eye(2, dtype=torch.complex128)] + [-1j * s for s in sig]
+        gam = torch.zeros((5, 4, 4), dtype=torch.complex128)
+        for mu, b in enumerate(blocks):
+            gam[mu, :2, 2:] = b
+            gam[mu, 2:, :2] = b.conj().T
+        gam[4] = gam[0] @ gam[1] @ gam[2] @ gam[3]
+        return gam
+
+    def _wilson_checks(self, what: str, kappa, *tensors) -> float:
+        for t in tensors:
+            self._no_grad(t, what)
+        try:
+            k = float(kappa)
+        except (TypeError, ValueError):
+            k = float('nan')
+        if not np.isfinite(k):
+            raise ValueError(f'LatticeSU3.{what}: kappa must be a finite number, got {kappa!r}')
+        return k
+
+    def _spinor_native(self, what: str, xn: Tensor, psin: Tensor) -> tuple[Tensor, bool]:
+        """psin as [nb, nrhs, 12, V] and whether it came without the nrhs axis"""
+        single = psin.dim() == 3
+        p = psin[:, None] if single else psin
+        if p.dim() != 4 or tuple(p.shape[2:]) != (12, self.volume) or p.shape[0] != xn.shape[0]:
+            raise ValueError(f'LatticeSU3.{what}: need a native spinor field [nb, nrhs, 12, V] or [nb, 12, V] with '
+                             f'nb = {xn.shape[0]}, V = {self.volume}, got {list(psin.shape)}')
+        return p.to(torch.complex128).contiguous(), single
+
+    def _spinor_reference(self, what: str, x: Tensor, psi: Tensor) -> tuple[Tensor, bool]:
+        single = psi.dim() == 7
+        p = psi[:, None] if single else psi
+        if p.dim() != 8 or tuple(p.shape[2:]) != (*self._lattice_shape, 4, 3) or p.shape[0] != x.shape[0]:
+            raise ValueError(f'LatticeSU3.{what}: need a spinor field [nb, nrhs, T, X, Y, Z, 4, 3] or one without the nrhs '
+                             f'axis on this lattice, got {list(psi.shape)}')
+        return ops.su3_spinor_pack(p.to(DEVICE)), single
+
+    def wilson_dirac_n(self, xn: Tensor, psin: Tensor, kappa: float, dagger: bool = False,
+                       antiperiodic_t: bool = True) -> Tensor:
+        """M psi = psi - kappa H psi (dagger: M^H psi = gamma5 M gamma5 psi) of a native spinor field [nb, nrhs, 12, V]
+        (or [nb, 12, V]) on the native links xn, thin or smeared,
+            H psi(x) = sum_mu [(1 - gamma_mu) U_mu(x) psi(x+mu) + (1 + gamma_mu) U_mu(x-mu)^H psi(x-mu)],
+        periodic except that with antiperiodic_t every hop across the t = T-1 -> 0 seam takes a factor -1.  One
+        `l2q_su3_wilson_apply`; a new field, nothing is written.  Any extents; any gauge action; no autograd."""
+        k = self._wilson_checks('wilson_dirac', kappa, xn, psin)
+        p, single = self._spinor_native('wilson_dirac', xn, psin)
+        out = ops.su3_wilson_apply_n(xn, p, k, self._lattice_shape, dagger, antiperiodic_t)
+        return out[:, 0] if single else out
+
+    def wilson_dirac(self, x: Tensor, psi: Tensor, kappa: float, dagger: bool = False,
+                     antiperiodic_t: bool = True) -> Tensor:
+        """`wilson_dirac_n` in the reference layout: psi[nb, nrhs, T, X, Y, Z, 4, 3] (spin, then colour), with or
+        without the nrhs axis, which the result then lacks too."""
+        k = self._wilson_checks('wilson_dirac', kappa, x, psi)
+        p, single = self._spinor_reference('wilson_dirac', x, psi)
+        out = ops.su3_spinor_unpack(ops.su3_wilson_apply_n(self.pack(x), p, k, self._lattice_shape, dagger,
+                                                           antiperiodic_t), self._lattice_shape)
+        return out[:, 0] if single else out
+
+    def wilson_solve_n(self, xn: Tensor, bn: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                       check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
+        """M psi = b for every system (chain, rhs) of the native field bn at once, by CG on M^H M (CGNR) from psi = 0,
+        with the true residual r = b - M psi carried along: per iteration two `l2q_su3_wilson_apply` (q = M p and
+        z = M^H r, each with its fused norm), one `l2q_su3_spinor_cg_update` and one `l2q_su3_spinor_xpay`;
+        alpha = |z|^2 / |M p|^2 and beta are formed per system on the device.  The host looks at |r|^2 <= tol^2 |b|^2
+        every check_every iterations (and after the last); a system found converged takes alpha = beta = 0 from then
+        on, so it no longer changes while the others go on, and a system's solution is the same bits whatever else is in
+        the batch.  Returns (psi, info): info['iters'] (the check at which a system was found converged, max_iter if
+        never), info['residual'] (|b - M psi| / |b| recomputed after the loop, 0 for b = 0), info['converged'], each
+        [nb, nrhs].  Never raises on non-convergence; b = 0 gives psi = 0.  Workspace: six spinor fields."""
+        k = self._wilson_checks('wilson_solve', kappa, xn, bn)
+        if not (float(tol) > 0.0) or isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 0 \
+                or isinstance(check_every, bool) or int(check_every) != check_every or int(check_every) < 1:
+            raise ValueError(f'LatticeSU3.wilson_solve: need tol > 0, an integer max_iter >= 0 and check_every >= 1, got '
+                             f'{tol!r}, {max_iter!r}, {check_every!r}')
+        b, single = self._spinor_native('wilson_solve', xn, bn)
+        L, tol2 = self._lattice_shape, float(tol) ** 2
+        max_iter, check_every = int(max_iter), int(check_every)
+        nb, nrhs = b.shape[:2]
+
+        def apply(src, dst, part, dagger):
+            ops.su3_wilson_apply_n(xn, src, k, L, dagger, antiperiodic_t, out=dst, norm=part)
+            return ops.sum_parts(part)
+
+        def ratio(live, num, den):
+            ok = live & (den > 0)
+            return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
+
+        psi, r, q, z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
+        part = torch.empty((nb, nrhs, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=b.device)
+        rpart = torch.empty_like(part)
+        zero = torch.zeros((nb, nrhs), dtype=torch.float64, device=b.device)
+        bb = ops.sum_parts(ops.su3_spinor_cg_update_(psi, r, b, b, zero, rpart))        # alpha = 0: |r|^2 = |b|^2
+        zz = apply(r, z, part, True)
+        p = z.clone()
+        active = ~(bb <= tol2 * bb)
+        iters = torch.where(active, max_iter, 0)
+        it = 0
+        while it < max_iter and bool(active.any()):
+            for _ in range(min(check_every, max_iter - it)):
+                qq = apply(p, q, part, False)
+                ops.su3_spinor_cg_update_(psi, r, p, q, ratio(active, zz, qq), rpart)
+                zn = apply(r, z, part, True)
+                ops.su3_spinor_xpay_(p, z, ratio(active, zn, zz))
+                zz = zn
+                it += 1
+            now = active & (ops.sum_parts(rpart) <= tol2 * bb)
+            iters = torch.where(now, it, iters)
+            active = active & ~now
+        # the residual, recomputed: r = b - 1 * (M psi), z and p serving as the update's other pair
+        apply(psi, q, part, False)
+        r.copy_(b)
+        rr = ops.sum_parts(ops.su3_spinor_cg_update_(z, r, p, q, torch.ones_like(zero), rpart))
+        res = torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
+        info = {'iters': iters, 'residual': res, 'converged': ~active}
+        return (psi[:, 0] if single else psi), info
+
+    def wilson_solve(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                     check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
+        """`wilson_solve_n` in the reference layout; x may be thin or smeared links, e.g.
+        `wilson_solve(lat.hyp_smear(x), b, kappa)`."""
+        self._wilson_checks('wilson_solve', kappa, x, b)
+        bn, single = self._spinor_reference('wilson_solve', x, b)
+        psin, info = self.wilson_solve_n(self.pack(x), bn, kappa, tol, max_iter, check_every, antiperiodic_t)
+        psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
+        return (psi[:, 0] if single else psi), info
+
+    def quark_propagator_n(self, xn: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
+        """The point-to-all propagator from the site `source` = (t, x, y, z): the twelve unit sources (spin, colour) at
+        that site solved as one nrhs = 12 batch of `wilson_solve_n`.  Returns (S, info), S[nb, 12, 12, V] native:
+        source component 3 spin + colour, then sink component, then site."""
+        self._wilson_checks('quark_propagator', kappa, xn)
+        L = self._lattice_shape
+        try:
+            src = [int(c) for c in source]
+            ok = len(src) == 4 and all(int(c) == c and 0 <= int(c) < n for c, n in zip(source, L))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f'LatticeSU3.quark_propagator: source must be a site (t, x, y, z) of {list(L)}, got {source!r}')
+        s = ((src[0] * L[1] + src[1]) * L[2] + src[2]) * L[3] + src[3]
+        bn = torch.zeros((xn.shape[0], 12, 12, self.volume), dtype=torch.complex128, device=xn.device)
+        j = torch.arange(12, device=xn.device)
+        bn[:, j, j, s] = 1.0
+        return self.wilson_solve_n(xn, bn, kappa, **solve_kwargs)
+
+    def quark_propagator(self, x: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
+        """`quark_propagator_n` in the reference layout: S[nb, T, X, Y, Z, 4, 3, 4, 3] (sink spin, sink colour, source
+        spin, source colour), for `pion_correlator`."""
+        self._wilson_checks('quark_propagator', kappa, x)
+        sn, info = self.quark_propagator_n(self.pack(x), kappa, source, **solve_kwargs)
+        S = ops.su3_spinor_unpack(sn, self._lattice_shape).movedim(1, -1).contiguous()
+        return S.reshape(*S.shape[:-1], 4, 3), info
 
     # ------------------------------------------------------------ heatbath and overrelaxation sweeps
     def _local_update_checks(self, xn: Tensor, what: str, nsweeps: int, nover: int = 0) -> None:

@@ -1,0 +1,187 @@
+#!/usr/bin/env python3
+"""Measurements of the Wilson fermions (csrc/su3_wilson.hip) for profiles/su3_wilson.md, SU(3) 8^4, complex128:
+  --kernels     `l2q_su3_wilson_apply` with and without the fused norm at --nb chains (256) and each --nrhs (1 and 12) by
+                HIP events: --repeats windows of --iters calls after a warm-up, median and spread, with the algorithmic
+                bytes (spinor read once and written once; links counted once per chain and, beside it, once per system),
+                the rate they give and its share of the HBM figure DESIGN.md uses; then the four launches of one CG
+                iteration (two applies with norm, the update, the xpay) one by one and the iteration as a whole (with
+                the per-system alpha / beta arithmetic in between), and a spinor field copy;
+  --torch       the same operator composed from torch `roll` / `einsum` on the GPU at --torch-nb chains: the only
+                "before" there is;
+  --propagator  one 12-column `quark_propagator` at kappa = 0.10 on --physics-nb chains thermalised with `heatbath` at
+                beta = 6 (nover = 3), with the pion correlator and its effective mass."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'l2hmc-qcd_amd'))
+from l2hmc import _ops as ops  # noqa: E402
+from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3, effective_mass, pion_correlator  # noqa: E402
+
+HBM_PEAK = 8.0e12       # B/s, the spec figure that DESIGN.md's fractions are taken against
+SPINOR = 192            # bytes of one complex128 spinor (12 components)
+LINKS = 4 * 144         # bytes of the four links of a site
+FLOPS = 1320            # per (system, site) of one application
+
+
+def windows(fn, iters, repeats, warm=3):
+    """seconds per call in each of `repeats` windows of `iters` calls, by device events"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / iters * 1e-3)
+    return out
+
+
+def show(name, ts, nbytes=None, sites=0, alt=None):
+    t = statistics.median(ts)
+    line = f'{name:44s} {t * 1e3:8.3f} ms (min {min(ts) * 1e3:.3f}, max {max(ts) * 1e3:.3f})'
+    if nbytes is not None:
+        rate = nbytes * sites / t
+        line += f'  {nbytes:6.0f} B/site  {rate / 1e12:5.2f} TB/s  {rate / HBM_PEAK:.3f} of 8 TB/s'
+        if alt is not None:
+            line += f'  (links per system: {alt:.0f} B/site, {alt * sites / t / HBM_PEAK:.3f})'
+        line += f'  {FLOPS * sites / t / 1e12:5.2f} Tflop/s' if alt is not None else ''
+    print(line)
+    return t
+
+
+def kernels(nb, L, nrhs_list, iters, repeats):
+    V = L[0] * L[1] * L[2] * L[3]
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    xn = ops.su3_project_su_n(torch.randn((nb, 4, 9, V), dtype=torch.complex128, device=dev))
+    kappa = 0.10
+    for nrhs in nrhs_list:
+        psi = torch.randn((nb, nrhs, 12, V), dtype=torch.complex128, device=dev)
+        out, q, z, x = (torch.empty_like(psi) for _ in range(4))
+        r, p = torch.randn_like(psi), torch.randn_like(psi)
+        part = torch.empty((nb, nrhs, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=dev)
+        rpart = torch.empty_like(part)
+        coef = torch.full((nb, nrhs), 1e-3, dtype=torch.float64, device=dev)
+        x.zero_()
+        sites = nb * nrhs * V
+        once, per_sys = 2 * SPINOR + LINKS / nrhs, 2 * SPINOR + LINKS
+        print(f'lattice {L} x {nb} chains x {nrhs} right-hand sides: {psi.numel() * 16 / 1e6:.0f} MB per spinor field, '
+              f'{xn.numel() * 16 / 1e6:.0f} MB of links, {iters} calls per window, {repeats} windows')
+        show('apply', windows(lambda: ops.su3_wilson_apply_n(xn, psi, kappa, L, out=out), iters, repeats), once, sites, per_sys)
+        show('apply, dagger', windows(lambda: ops.su3_wilson_apply_n(xn, psi, kappa, L, True, out=out), iters, repeats),
+             once, sites, per_sys)
+        ta = show('apply + fused norm', windows(lambda: ops.su3_wilson_apply_n(xn, psi, kappa, L, out=out, norm=part),
+                                                iters, repeats), once, sites, per_sys)
+        tu = show('cg_update (x, r, p, q; |r|^2)', windows(lambda: ops.su3_spinor_cg_update_(x, r, p, q, coef, rpart),
+                                                         iters, repeats), 6 * SPINOR, sites)
+        tx = show('xpay (p, z)', windows(lambda: ops.su3_spinor_xpay_(p, z, coef), iters, repeats), 3 * SPINOR, sites)
+        show('spinor field copy (copy_)', windows(lambda: out.copy_(psi), iters, repeats), 2 * SPINOR, sites)
+        show('sum_parts (tree over the partials)', windows(lambda: ops.sum_parts(part), iters, repeats))
+
+        def iteration():
+            ops.su3_wilson_apply_n(xn, p, kappa, L, False, out=q, norm=part)
+            qq = ops.sum_parts(part)
+            ops.su3_spinor_cg_update_(x, r, p, q, (coef / (qq + 1.0)).contiguous(), rpart)
+            ops.su3_wilson_apply_n(xn, r, kappa, L, True, out=z, norm=part)
+            zn = ops.sum_parts(part)
+            ops.su3_spinor_xpay_(p, z, (coef / (zn + 1.0)).contiguous())
+
+        ti = show('one CG iteration, as launched', windows(iteration, iters, repeats))
+        print(f'  four launches by themselves: 2 x {ta * 1e3:.3f} + {tu * 1e3:.3f} + {tx * 1e3:.3f} = '
+              f'{(2 * ta + tu + tx) * 1e3:.3f} ms; the rest of {ti * 1e3:.3f} ms is the per-system arithmetic between them')
+        del psi, out, q, z, x, r, p
+
+
+def torch_apply(x, psi, kappa, gam):
+    """M psi from roll / einsum on reference-layout tensors (antiperiodic in t)"""
+    eye = torch.eye(4, dtype=psi.dtype, device=psi.device)
+    acc = torch.zeros_like(psi)
+    for mu in range(4):
+        f = torch.roll(psi, -1, 2 + mu)
+        w = torch.roll(torch.einsum('btxyzji,brtxyzaj->brtxyzai', x[:, mu].conj(), psi), 1, 2 + mu)
+        if mu == 0:
+            f[:, :, -1] *= -1
+            w[:, :, 0] *= -1
+        acc += torch.einsum('ad,brtxyzdc->brtxyzac', eye - gam[mu], torch.einsum('btxyzij,brtxyzaj->brtxyzai', x[:, mu], f))
+        acc += torch.einsum('ad,brtxyzdc->brtxyzac', eye + gam[mu], w)
+    return psi - kappa * acc
+
+
+def torch_compose(nb, L, nrhs_list, iters, repeats):
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    lat = LatticeSU3(nb, L)
+    V = lat.volume
+    x = lat.unpack(ops.su3_project_su_n(torch.randn((nb, 4, 9, V), dtype=torch.complex128, device=dev)))
+    gam = LatticeSU3.gamma_matrices().to(dev)
+    for nrhs in nrhs_list:
+        psi = torch.randn((nb, nrhs, *L, 4, 3), dtype=torch.complex128, device=dev)
+        d = float((torch_apply(x, psi, 0.1, gam) - lat.wilson_dirac(x, psi, 0.1)).abs().max())
+        print(f'lattice {L} x {nb} chains x {nrhs} right-hand sides, |torch - kernel| = {d:.3g}')
+        tt = show('torch roll / einsum', windows(lambda: torch_apply(x, psi, 0.1, gam), iters, repeats))
+        pn = ops.su3_spinor_pack(psi)
+        out = torch.empty_like(pn)
+        xn = lat.pack(x)
+        tk = show('l2q_su3_wilson_apply', windows(lambda: ops.su3_wilson_apply_n(xn, pn, 0.1, L, out=out), iters, repeats))
+        print(f'  ratio {tt / tk:.1f}')
+
+
+def propagator(nb, L, therm, kappa):
+    dev = torch.device('cuda:0')
+    torch.manual_seed(1)
+    lat = LatticeSU3(nb, L)
+    x = lat.heatbath(lat.random().to(dev), 6.0, nsweeps=therm, nover=3)[0]
+    print(f'{L} x {nb} chains, beta 6.0 after {therm} heatbath sweeps (nover 3): plaquette '
+          f'{float(lat.plaqs(x).mean()):.5f}')
+    for name, links in (('thin links', x), ('one HYP step', lat.hyp_smear(x))):
+        lat.quark_propagator(links, kappa)                      # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        S, info = lat.quark_propagator(links, kappa)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        C = pion_correlator(S)
+        print(f'{name}: kappa {kappa}: {dt * 1e3:.1f} ms for {nb} x 12 systems, iterations {int(info["iters"].min())} .. '
+              f'{int(info["iters"].max())}, residual <= {float(info["residual"].max()):.3g}, all converged '
+              f'{bool(info["converged"].all())}')
+        print('  C(t)     = ' + ' '.join(f'{float(v):.4e}' for v in C.mean(0)))
+        print('  m_eff(t) = ' + ' '.join(f'{float(v):.4f}' for v in effective_mass(C.mean(0))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--nb', type=int, default=256)
+    ap.add_argument('--L', type=int, nargs=4, default=[8, 8, 8, 8])
+    ap.add_argument('--nrhs', type=int, nargs='+', default=[1, 12])
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--kernels', action='store_true')
+    ap.add_argument('--torch', action='store_true')
+    ap.add_argument('--torch-nb', type=int, default=32)
+    ap.add_argument('--propagator', action='store_true')
+    ap.add_argument('--physics-nb', type=int, default=16)
+    ap.add_argument('--therm', type=int, default=50)
+    ap.add_argument('--kappa', type=float, default=0.10)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs the GPU'
+    torch.set_default_dtype(torch.float64)
+    if args.kernels:
+        kernels(args.nb, args.L, args.nrhs, args.iters, args.repeats)
+    if args.torch:
+        torch_compose(args.torch_nb, args.L, args.nrhs, max(2, args.iters // 4), args.repeats)
+    if args.propagator:
+        propagator(args.physics_nb, args.L, args.therm, args.kappa)
+
+
+if __name__ == '__main__':
+    main()
