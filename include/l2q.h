@@ -428,6 +428,24 @@ int l2q_su3_spinor_cg_update(void* x, void* r, const void* p, const void* q, con
                              long nsys, long V, void* stream);
 /* p = z + beta[s] p, beta a device array [nsys] of doubles.  L2Q_EINVAL as above (p must not alias z). */
 int l2q_su3_spinor_xpay(void* p, const void* z, const double* beta, long nsys, long V, void* stream);
+/* csrc/su3_wilson_force.hip.  The force of npf two-flavour pseudofermion fields, S_f = sum_r phi_r^H (M^H M)^-1 phi_r,
+ * from the solutions X_r = (M^H M)^-1 phi_r and Y_r = M X_r, both [nb][npf][12][V]: the TAH field F_f with dS_f/dt =
+ * sum_links <p, F_f>, <a, b> = Re tr(a^H b), under dU/dt = p U (the convention of l2q_su3_force).  With s the seam sign
+ * of l2q_su3_wilson_apply (-1 on a hop across t = T-1 -> 0 with flags bit 1, mu = 0; else +1), X' = s X(x+mu), Y' =
+ * s Y(x+mu) and a b^H the colour outer product summed over spin, (a b^H)_ij = sum_spin a_(spin,i) conj(b_(spin,j)):
+ *   W_mu(x) = U_mu(x) sum_r [(1 - gamma_mu) X'_r] Y_r(x)^H - sum_r X_r(x) [(1 + gamma_mu) Y'_r]^H U_mu(x)^H,
+ *   F_f,mu(x) = -2 kappa TAH(W_mu(x)),   TAH(W) = (W - W^H)/2 - (tr/3) 1.
+ * f_out = (f_in ? f_in : 0) + coef F_f in the native link layout [nb][4][9][V]: coef = 1 with f_in = NULL is the force,
+ * f_in == f_out = v with coef = -eps/2 the in-place kick (as l2q_su3_force_kick), another f_in the kick out of place (as
+ * l2q_su3_force_kick_to).  flags bit 1: antiperiodic in t, the bit of l2q_su3_wilson_apply; no other bit.  Any extents,
+ * 1 and 2 included (T = 1: every hop in t carries the sign).  One thread per link, no atomics, the sum over r in its
+ * order: a chain's force is the same bits alone and in a batch, and from run to run.  F_f is stored exactly
+ * anti-Hermitian: plane (j, i) is (-re, im) of plane (i, j), the diagonal has no real part (with f_in: if f_in is).
+ * Algorithmic traffic per (chain, site): links 576 B, output 576 B (+ 576 B of f_in), spinors npf * 384 B.
+ * L2Q_EINVAL, before any HIP call: a null xn, X, Y or f_out; f_out aliasing xn, X or Y; kappa or coef not finite;
+ * npf <= 0 or another non-positive size; nb * npf * 12 * V of 2^31 or more; flags other than 0 or 2. */
+int l2q_su3_wilson_force(const void* xn, const void* X, const void* Y, const void* f_in, void* f_out, double kappa,
+                         double coef, int flags, int nb, int npf, int T, int X_, int Y_, int Z, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

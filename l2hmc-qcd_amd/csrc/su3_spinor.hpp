@@ -1,0 +1,79 @@
+// su3_spinor.hpp -- what the kernels over spinor fields share (su3_wilson.hip: the Wilson-Dirac operator;
+// su3_wilson_force.hip: the pseudofermion force): the half spinor of a rank-2 projector 1 -+ gamma_mu, its
+// projection from a field in the layout psi[system][12][V], its product with a link, and the size check.
+//
+// Gamma matrices: Hermitian, chiral, gamma_mu = [[0, B_mu], [B_mu^H, 0]] in 2 x 2 blocks with
+//   B_0 = 1 (direction 0 is T),  B_k = -i sigma_k (k = 1, 2, 3 = x, y, z),  gamma5 = g0 g1 g2 g3 = diag(-1, -1, 1, 1).
+// 1 - s gamma_mu has rank 2: with h = psi_u - s B psi_l (the upper two spin components), (1 - s gamma_mu) psi =
+// (h, -s B^H h).
+#pragma once
+#include "su3_launch.hpp"
+
+namespace l2q {
+
+struct HalfSpinor {
+  double re[6], im[6];          // [3 spin + colour], spin 0, 1
+};
+
+// h = bs (psi_u - sg B_mu psi_l) of the spinor at site s of field f: the upper half of bs (1 - sg gamma_mu) psi.
+// mu is wave-uniform (the loop counter), sg and bs are +-1.
+__device__ __forceinline__ void wilson_project(HalfSpinor& h, const double2* __restrict__ f, int V, int s, int mu,
+                                               double sg, double bs) {
+  double ur[6], ui[6], lr[6], li[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double2 a = f[k * V + s], b = f[(6 + k) * V + s];
+    ur[k] = a.x; ui[k] = a.y; lr[k] = b.x; li[k] = b.y;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double r0, i0, r1, i1;
+    switch (mu) {
+      case 0:            // B = 1: h0 = psi0 - sg psi2, h1 = psi1 - sg psi3
+        r0 = fma(-sg, lr[c], ur[c]); i0 = fma(-sg, li[c], ui[c]);
+        r1 = fma(-sg, lr[3 + c], ur[3 + c]); i1 = fma(-sg, li[3 + c], ui[3 + c]);
+        break;
+      case 1:            // B = -i sigma_1: h0 = psi0 + i sg psi3, h1 = psi1 + i sg psi2
+        r0 = fma(-sg, li[3 + c], ur[c]); i0 = fma(sg, lr[3 + c], ui[c]);
+        r1 = fma(-sg, li[c], ur[3 + c]); i1 = fma(sg, lr[c], ui[3 + c]);
+        break;
+      case 2:            // B = -i sigma_2: h0 = psi0 + sg psi3, h1 = psi1 - sg psi2
+        r0 = fma(sg, lr[3 + c], ur[c]); i0 = fma(sg, li[3 + c], ui[c]);
+        r1 = fma(-sg, lr[c], ur[3 + c]); i1 = fma(-sg, li[c], ui[3 + c]);
+        break;
+      default:           // B = -i sigma_3: h0 = psi0 + i sg psi2, h1 = psi1 - i sg psi3
+        r0 = fma(-sg, li[c], ur[c]); i0 = fma(sg, lr[c], ui[c]);
+        r1 = fma(sg, li[3 + c], ur[3 + c]); i1 = fma(-sg, lr[3 + c], ui[3 + c]);
+        break;
+    }
+    h.re[c] = bs * r0; h.im[c] = bs * i0;
+    h.re[3 + c] = bs * r1; h.im[3 + c] = bs * i1;
+  }
+}
+
+// chi = U h (ADJ: U^H h) for both colour vectors of the half spinor
+template <bool ADJ>
+__device__ __forceinline__ void wilson_colour_mul(HalfSpinor& chi, const M3& u, const HalfSpinor& h) {
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double re = 0.0, im = 0.0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double mr = ADJ ? u.re[3 * j + i] : u.re[3 * i + j];
+        const double mi = ADJ ? -u.im[3 * j + i] : u.im[3 * i + j];
+        const double hr = h.re[3 * a + j], hi = h.im[3 * a + j];
+        re = fma(mr, hr, re); re = fma(-mi, hi, re);
+        im = fma(mr, hi, im); im = fma(mi, hr, im);
+      }
+      chi.re[3 * a + i] = re; chi.im[3 * a + i] = im;
+    }
+}
+
+// nsys systems of 12 V complex entries: positive sizes, and every entry's index fits an int (in double: no overflow)
+inline bool spinor_dims_ok(long nsys, long V) {
+  return nsys > 0 && V > 0 && (double)nsys * 12.0 * (double)V < 2147483648.0;
+}
+
+}  // namespace l2q

@@ -689,6 +689,29 @@ def su3_spinor_xpay_(p: torch.Tensor, z: torch.Tensor, beta: torch.Tensor) -> to
     return p
 
 
+def su3_wilson_force_n(xn: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, kappa: float, lat: Sequence[int],
+                       antiperiodic_t: bool = True, coef: float = 1.0, f_in: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (f_in or 0) + coef F_f: the pseudofermion force of the native fields X = (M^H M)^-1 phi, Y = M X, both
+    [nb, npf, 12, V], on the native links xn (see l2q.h).  coef = 1 and f_in None give the force; f_in = out = vn the
+    kick in place; out None = a new field."""
+    T, X_, Y_, Z = (int(i) for i in lat)
+    if X.dim() != 4 or X.shape[0] != xn.shape[0] or X.shape[1] < 1 or X.shape[2] != 12 or X.shape[3] != xn.shape[-1]:
+        raise ValueError(f'su3_wilson_force_n: need X [nb, npf, 12, V] on xn {list(xn.shape)}, got {list(X.shape)}')
+    _spinor_check('su3_wilson_force_n', 'X', X, X.shape)
+    _spinor_check('su3_wilson_force_n', 'Y', Y, X.shape)
+    for name, t in (('xn', xn), ('f_in', f_in), ('out', out)):
+        if t is not None and (t.dtype != C128 or tuple(t.shape) != (xn.shape[0], 4, 9, T * X_ * Y_ * Z)
+                              or not t.is_contiguous()):
+            raise ValueError(f'su3_wilson_force_n: {name} must be contiguous complex128 [nb, 4, 9, V] on {list(lat)}, '
+                             f'got {t.dtype} {list(t.shape)}')
+    if out is None:
+        out = torch.empty_like(xn)
+    N.call('l2q_su3_wilson_force', xn, X, Y, f_in, out, float(kappa), float(coef), int(bool(antiperiodic_t)) << 1,
+           xn.shape[0], X.shape[1], T, X_, Y_, Z)
+    return out
+
+
 def sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
     partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""

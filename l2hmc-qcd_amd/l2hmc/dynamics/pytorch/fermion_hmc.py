@@ -1,0 +1,130 @@
+"""HMC with two flavours of dynamical Wilson quarks (Duane et al. 1987; Gottlieb et al. 1987): the gauge action plus
+the pseudofermion action S_f = sum_r phi_r^H (M^H M)^-1 phi_r, which puts det(M^H M)^npf into the ensemble.  Built from
+the lattice's kernels: the gauge force kick, `l2q_su3_wilson_force` behind a CG on M^H M, the expm link update, the
+kinetic-energy reduction and the accept step.  Plain leapfrog, every solve from zero (a chronological guess would break
+reversibility at a finite solver tolerance).  Not wired into `Dynamics`, the trainer or the CLI; see INTEGRATION.md,
+"Dynamical Wilson fermions", for what is deliberately left out."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from l2hmc import _ops as ops
+from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
+
+Tensor = torch.Tensor
+
+
+class WilsonHMC:
+    """One trajectory: momentum and pseudofermion refresh, `nleapfrog` leapfrog steps of size `eps` under the force of
+    S_g(beta) + S_f(kappa), accept / reject per chain.  The solves of the molecular dynamics stop at `tol_md`, those
+    of the Hamiltonian at `tol_h`; a solve that reaches `max_iter` is counted (metrics['unconverged']), not raised."""
+
+    def __init__(self, lattice: LatticeSU3, beta: float, kappa: float, eps: float, nleapfrog: int, npf: int = 1,
+                 tol_md: float = 1e-8, tol_h: float = 1e-12, max_iter: int = 2000, antiperiodic_t: bool = True) -> None:
+        if not isinstance(lattice, LatticeSU3):
+            raise ValueError('WilsonHMC: needs a LatticeSU3')
+        vals = dict(beta=beta, kappa=kappa, eps=eps, tol_md=tol_md, tol_h=tol_h)
+        for name, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v):
+                raise ValueError(f'WilsonHMC: {name} must be a finite number, got {v!r}')
+        if not (tol_md > 0 and tol_h > 0):
+            raise ValueError(f'WilsonHMC: tol_md and tol_h must be > 0, got {tol_md!r}, {tol_h!r}')
+        for name, v, lo in (('nleapfrog', nleapfrog, 1), ('npf', npf, 1), ('max_iter', max_iter, 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                raise ValueError(f'WilsonHMC: {name} must be an integer >= {lo}, got {v!r}')
+        self.lattice = lattice
+        self.beta, self.kappa, self.eps = float(beta), float(kappa), float(eps)
+        self.nleapfrog, self.npf, self.max_iter = int(nleapfrog), int(npf), int(max_iter)
+        self.tol_md, self.tol_h = float(tol_md), float(tol_h)
+        self.antiperiodic_t = bool(antiperiodic_t)
+
+    # ------------------------------------------------------------ the pieces
+    def _solve_kw(self, tol: float) -> dict:
+        return dict(tol=tol, max_iter=self.max_iter, antiperiodic_t=self.antiperiodic_t)
+
+    def _kick_(self, xn: Tensor, vn: Tensor, phin: Tensor, step: float, infos: list) -> None:
+        """vn -= step * (F_g + F_f), in place: the gauge kick, then the fermion kick into the same momentum"""
+        lat, L = self.lattice, self.lattice._lattice_shape
+        if lat.c1 == 0:
+            ops.su3_force_kick_n(xn, self.beta, -step, vn, L)
+        else:
+            ops.axpy_(vn, lat.grad_action_n(xn, self.beta), -step)
+        X, Y, info = lat.wilson_solve_normal_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
+        ops.su3_wilson_force_n(xn, X, Y, self.kappa, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
+        infos.append(info)
+
+    def leapfrog_n(self, xn: Tensor, vn: Tensor, phin: Tensor) -> tuple[Tensor, Tensor, dict]:
+        """The deterministic part, no random numbers: half kick, `nleapfrog` link updates U <- exp(eps p) U with full
+        kicks between them, half kick.  Returns (x', v', info); xn, vn are not written.  info: 'cg_iters' [solves, nb,
+        npf] and 'unconverged', the number of systems that reached max_iter."""
+        xn, vn = xn.detach(), vn.detach().clone()
+        infos: list = []
+        self._kick_(xn, vn, phin, 0.5 * self.eps, infos)
+        for k in range(self.nleapfrog):
+            xn = ops.su3_expm_mul_n(xn, vn, self.eps)
+            self._kick_(xn, vn, phin, (1.0 if k + 1 < self.nleapfrog else 0.5) * self.eps, infos)
+        iters = torch.stack([i['iters'] for i in infos])
+        unconv = sum(int((~i['converged']).sum()) for i in infos)
+        return xn, vn, {'cg_iters': iters, 'unconverged': unconv}
+
+    def hamiltonian_n(self, xn: Tensor, vn: Tensor, phin: Tensor, info: Optional[dict] = None) -> Tensor:
+        """H [nb] = kinetic + S_g + S_f, the solve at tol_h; `info`, if given, receives the solve's info"""
+        sf, sinfo = self.lattice.pseudofermion_action_n(xn, phin, self.kappa, **self._solve_kw(self.tol_h))
+        if info is not None:
+            info.update(sinfo)
+        return ops.su3_kinetic_n(vn) + self.lattice.action_n(xn, self.beta) + sf
+
+    # ------------------------------------------------------------ the trajectory
+    def _draw(self, shape, generator, device, uniform=False) -> Tensor:
+        fn = torch.rand if uniform else torch.randn
+        if generator is None or generator.device.type == device.type:
+            return fn(shape, dtype=torch.float64, device=device, generator=generator)
+        return fn(shape, dtype=torch.float64, generator=generator).to(device)
+
+    def trajectory_n(self, xn: Tensor, generator: Optional[torch.Generator] = None) -> tuple[Tensor, dict]:
+        """One trajectory on a native field: (x_out, metrics).  Draws, in this order: the momentum normals
+        randn((8, nb, 4, V)), the pseudofermion noise (`pseudofermion_refresh_n`), the accept uniforms rand(nb)."""
+        lat = self.lattice
+        nb = xn.shape[0]
+        xn = xn.detach().contiguous()
+        vn = ops.su3_assemble_tah_n(self._draw((8, nb, 4, lat.volume), generator, xn.device))
+        phin, s0 = lat.pseudofermion_refresh_n(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
+        h0 = ops.su3_kinetic_n(vn) + lat.action_n(xn, self.beta) + s0             # S_f(phi) = |eta|^2: no solve
+        x1, v1, info = self.leapfrog_n(xn, vn, phin)
+        hinfo: dict = {}
+        h1 = self.hamiltonian_n(x1, v1, phin, hinfo)
+        u = self._draw((nb,), generator, xn.device, uniform=True)
+        acc, mask = ops.accept(h0, h1, torch.zeros_like(h0), u)
+        xo = ops.select_rows(x1.reshape(nb, -1), xn.reshape(nb, -1), mask).reshape(xn.shape)
+        it = info['cg_iters'].to(torch.float64)
+        metrics = {'acc': acc, 'acc_mask': mask, 'dH': h1 - h0,
+                   'plaq': lat.plaq_sums_n(xo)[:, 0] / (18.0 * lat.volume),
+                   'cg_iters_md': {'mean': float(it.mean()), 'max': int(it.max())},
+                   'cg_iters_h': {'mean': float(hinfo['iters'].to(torch.float64).mean()),
+                                  'max': int(hinfo['iters'].max())},
+                   'unconverged': info['unconverged'] + int((~hinfo['converged']).sum())}
+        return xo, metrics
+
+    def trajectory(self, x: Tensor, generator: Optional[torch.Generator] = None) -> tuple[Tensor, dict]:
+        """`trajectory_n` in the reference layout x[nb, 4, T, X, Y, Z, 3, 3]: momentum refresh (the `assemble_tah`
+        path), pseudofermion refresh, H0 (its S_f is the refresh's |eta|^2), leapfrog, H1, accept / reject per chain.
+        metrics: 'acc', 'acc_mask', 'dH', 'plaq' [nb]; 'cg_iters_md', 'cg_iters_h' (mean and max per solve);
+        'unconverged', the systems that hit max_iter -- the chain is still accepted or rejected on the H it got."""
+        if x.requires_grad:
+            raise ValueError('WilsonHMC.trajectory: no autograd through a trajectory; detach x')
+        xo, metrics = self.trajectory_n(self.lattice.pack(x), generator)
+        return self.lattice.unpack(xo), metrics
+
+    def thermalize(self, x: Tensor, ntraj: int, generator: Optional[torch.Generator] = None) -> tuple[Tensor, list]:
+        """`ntraj` trajectories in a row: (x, history), history the list of their metrics"""
+        if x.requires_grad:
+            raise ValueError('WilsonHMC.thermalize: no autograd through a trajectory; detach x')
+        xn = self.lattice.pack(x)
+        history = []
+        for _ in range(int(ntraj)):
+            xn, m = self.trajectory_n(xn, generator)
+            history.append(m)
+        return self.lattice.unpack(xn), history

@@ -784,6 +784,148 @@ class LatticeSU3(Lattice):
         S = ops.su3_spinor_unpack(sn, self._lattice_shape).movedim(1, -1).contiguous()
         return S.reshape(*S.shape[:-1], 4, 3), info
 
+    # ------------------------------------------------------------ dynamical Wilson fermions: pseudofermions
+    def _pf_checks(self, what: str, kappa, *tensors) -> float:
+        for t in tensors:
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError(f'LatticeSU3.{what}: no autograd through the pseudofermion action; detach the fields')
+        return self._wilson_checks(what, kappa, *tensors)
+
+    @staticmethod
+    def _sum_fields(a: Tensor) -> Tensor:
+        """[nb, npf] -> [nb], the fields added in their order (a chain's bits do not depend on the batch)"""
+        s = a[:, 0].clone()
+        for r in range(1, a.shape[1]):
+            s = s + a[:, r]
+        return s
+
+    def wilson_solve_normal_n(self, xn: Tensor, phin: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                              check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
+        """M^H M X = phi for every system (chain, field) of the native field phin at once, by CG from X = 0, and
+        Y = M X: what the pseudofermion action |Y|^2 and its force need.  Per iteration q = M p with its fused norm
+        (<p, M^H M p> = |M p|^2), z = M^H q, one `l2q_su3_spinor_cg_update` (X += alpha p, r -= alpha z, |r|^2 fused)
+        and one `l2q_su3_spinor_xpay` (p = r + beta p); alpha = |r|^2 / |M p|^2 and beta are formed per system on the
+        device.  (X from two `wilson_solve_n` would cost twice the operator applications.)  The host looks at |r|^2 <=
+        tol^2 |phi|^2 every check_every iterations; a system found converged takes alpha = beta = 0 from then on, so a
+        system's bits do not depend on the batch.  Never raises on non-convergence; phi = 0 gives X = 0.  Returns (X,
+        Y, info): info['iters'], info['converged'], info['residual'] (|phi - M^H M X| / |phi| recomputed) and
+        info['action'] (|Y|^2 from the fused norm of the last apply), each [nb, npf].  Workspace: seven spinor fields."""
+        k = self._pf_checks('wilson_solve_normal', kappa, xn, phin)
+        if not (float(tol) > 0.0) or isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 0 \
+                or isinstance(check_every, bool) or int(check_every) != check_every or int(check_every) < 1:
+            raise ValueError(f'LatticeSU3.wilson_solve_normal: need tol > 0, an integer max_iter >= 0 and check_every '
+                             f'>= 1, got {tol!r}, {max_iter!r}, {check_every!r}')
+        b, single = self._spinor_native('wilson_solve_normal', xn, phin)
+        L, tol2 = self._lattice_shape, float(tol) ** 2
+        max_iter, check_every = int(max_iter), int(check_every)
+        nb, npf = b.shape[:2]
+
+        def ratio(live, num, den):
+            ok = live & (den > 0)
+            return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
+
+        X, r, q, z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
+        part = torch.empty((nb, npf, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=b.device)
+        rpart = torch.empty_like(part)
+        zero = torch.zeros((nb, npf), dtype=torch.float64, device=b.device)
+        bb = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, b, b, zero, rpart))          # alpha = 0: |r|^2 = |phi|^2
+        p = b.clone()
+        rr = bb
+        active = ~(bb <= tol2 * bb)
+        iters = torch.where(active, max_iter, 0)
+        it = 0
+        while it < max_iter and bool(active.any()):
+            for _ in range(min(check_every, max_iter - it)):
+                ops.su3_wilson_apply_n(xn, p, k, L, False, antiperiodic_t, out=q, norm=part)
+                qq = ops.sum_parts(part)
+                ops.su3_wilson_apply_n(xn, q, k, L, True, antiperiodic_t, out=z)
+                rn = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, p, z, ratio(active, rr, qq), rpart))
+                ops.su3_spinor_xpay_(p, r, ratio(active, rn, rr))
+                rr = rn
+                it += 1
+            now = active & (rr <= tol2 * bb)
+            iters = torch.where(now, it, iters)
+            active = active & ~now
+        Y = torch.empty_like(b)
+        ops.su3_wilson_apply_n(xn, X, k, L, False, antiperiodic_t, out=Y, norm=part)
+        action = ops.sum_parts(part)
+        # the residual, recomputed: r = phi - 1 * (M^H Y), q and p serving as the update's other pair
+        ops.su3_wilson_apply_n(xn, Y, k, L, True, antiperiodic_t, out=z)
+        r.copy_(b)
+        res2 = ops.sum_parts(ops.su3_spinor_cg_update_(q, r, p, z, torch.ones_like(zero), rpart))
+        res = torch.sqrt(res2 / torch.where(bb > 0, bb, torch.ones_like(bb)))
+        info = {'iters': iters, 'converged': ~active, 'residual': res, 'action': action}
+        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
+
+    def wilson_solve_normal(self, x: Tensor, phi: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                            check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
+        """`wilson_solve_normal_n` in the reference layout"""
+        self._pf_checks('wilson_solve_normal', kappa, x, phi)
+        pn, single = self._spinor_reference('wilson_solve_normal', x, phi)
+        X, Y, info = self.wilson_solve_normal_n(self.pack(x), pn, kappa, tol, max_iter, check_every, antiperiodic_t)
+        X, Y = (ops.su3_spinor_unpack(f, self._lattice_shape) for f in (X, Y))
+        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
+
+    def pseudofermion_refresh_n(self, xn: Tensor, kappa: float, npf: int = 1,
+                                generator: Optional[torch.Generator] = None,
+                                antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
+        """The pseudofermion heatbath: eta complex Gaussian with density exp(-eta^H eta) (variance 1/2 per real
+        component; `torch.randn((nb, npf, 12, V, 2), dtype=float64)` on the device, or on the host with a CPU
+        generator: the same numbers on any machine), phi = M^H eta, which is distributed as exp(-S_f).  Returns (phi
+        [nb, npf, 12, V], S0 [nb]): S0 = |eta|^2 is S_f(phi) on these links without a solve."""
+        k = self._pf_checks('pseudofermion_refresh', kappa, xn)
+        if isinstance(npf, bool) or not isinstance(npf, (int, np.integer)) or int(npf) < 1:
+            raise ValueError(f'LatticeSU3.pseudofermion_refresh: npf must be an integer >= 1, got {npf!r}')
+        shape = (xn.shape[0], int(npf), 12, self.volume, 2)
+        if generator is None or generator.device.type == xn.device.type:
+            g = torch.randn(shape, dtype=torch.float64, device=xn.device, generator=generator)
+        else:
+            g = torch.randn(shape, dtype=torch.float64, generator=generator).to(xn.device)
+        eta = torch.view_as_complex(g * float(np.sqrt(0.5))).contiguous()
+        phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
+        zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
+        part = ops.su3_spinor_cg_update_(torch.zeros_like(eta), eta, phi, phi, zero)     # alpha = 0: |eta|^2
+        return phi, self._sum_fields(ops.sum_parts(part))
+
+    def pseudofermion_refresh(self, x: Tensor, kappa: float, npf: int = 1, generator: Optional[torch.Generator] = None,
+                              antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
+        """`pseudofermion_refresh_n` in the reference layout: phi[nb, npf, T, X, Y, Z, 4, 3]"""
+        self._pf_checks('pseudofermion_refresh', kappa, x)
+        phi, s0 = self.pseudofermion_refresh_n(self.pack(x), kappa, npf, generator, antiperiodic_t)
+        return ops.su3_spinor_unpack(phi, self._lattice_shape), s0
+
+    def pseudofermion_action_n(self, xn: Tensor, phin: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
+        """S_f = sum_r phi_r^H (M^H M)^-1 phi_r = sum_r |Y_r|^2 per chain, by one `wilson_solve_normal_n` (whose
+        keywords these are): (S_f [nb], info)."""
+        self._pf_checks('pseudofermion_action', kappa, xn, phin)
+        b, _ = self._spinor_native('pseudofermion_action', xn, phin)
+        _, _, info = self.wilson_solve_normal_n(xn, b, kappa, **solve_kwargs)
+        return self._sum_fields(info['action']), info
+
+    def pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
+        """`pseudofermion_action_n` in the reference layout"""
+        self._pf_checks('pseudofermion_action', kappa, x, phi)
+        pn, _ = self._spinor_reference('pseudofermion_action', x, phi)
+        return self.pseudofermion_action_n(self.pack(x), pn, kappa, **solve_kwargs)
+
+    def pseudofermion_force_n(self, xn: Tensor, phin: Tensor, kappa: float,
+                              **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """The force of S_f on the links, in the convention of `grad_action_n` (dS_f/dt = sum <p, F> under dU/dt =
+        p U; the kick is p <- p - eps F): one `wilson_solve_normal_n` and one `l2q_su3_wilson_force` (see l2q.h).
+        Returns (F [nb, 4, 9, V], S_f [nb], info)."""
+        k = self._pf_checks('pseudofermion_force', kappa, xn, phin)
+        b, _ = self._spinor_native('pseudofermion_force', xn, phin)
+        X, Y, info = self.wilson_solve_normal_n(xn, b, k, **solve_kwargs)
+        F = ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True))
+        return F, self._sum_fields(info['action']), info
+
+    def pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """`pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]"""
+        self._pf_checks('pseudofermion_force', kappa, x, phi)
+        pn, _ = self._spinor_reference('pseudofermion_force', x, phi)
+        F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, **solve_kwargs)
+        return self.unpack(F), s, info
+
     # ------------------------------------------------------------ heatbath and overrelaxation sweeps
     def _local_update_checks(self, xn: Tensor, what: str, nsweeps: int, nover: int = 0) -> None:
         if isinstance(xn, torch.Tensor) and xn.requires_grad:
