@@ -13,6 +13,7 @@ import torch
 
 from l2hmc import _ops as ops
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
+from l2hmc.lattice.su3.pytorch.wilson import draw
 
 Tensor = torch.Tensor
 
@@ -78,25 +79,19 @@ class WilsonHMC:
         return ops.su3_kinetic_n(vn) + self.lattice.action_n(xn, self.beta) + sf
 
     # ------------------------------------------------------------ the trajectory
-    def _draw(self, shape, generator, device, uniform=False) -> Tensor:
-        fn = torch.rand if uniform else torch.randn
-        if generator is None or generator.device.type == device.type:
-            return fn(shape, dtype=torch.float64, device=device, generator=generator)
-        return fn(shape, dtype=torch.float64, generator=generator).to(device)
-
     def trajectory_n(self, xn: Tensor, generator: Optional[torch.Generator] = None) -> tuple[Tensor, dict]:
         """One trajectory on a native field: (x_out, metrics).  Draws, in this order: the momentum normals
         randn((8, nb, 4, V)), the pseudofermion noise (`pseudofermion_refresh_n`), the accept uniforms rand(nb)."""
         lat = self.lattice
         nb = xn.shape[0]
         xn = xn.detach().contiguous()
-        vn = ops.su3_assemble_tah_n(self._draw((8, nb, 4, lat.volume), generator, xn.device))
+        vn = ops.su3_assemble_tah_n(draw((8, nb, 4, lat.volume), generator, xn.device))
         phin, s0 = lat.pseudofermion_refresh_n(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
         h0 = ops.su3_kinetic_n(vn) + lat.action_n(xn, self.beta) + s0             # S_f(phi) = |eta|^2: no solve
         x1, v1, info = self.leapfrog_n(xn, vn, phin)
         hinfo: dict = {}
         h1 = self.hamiltonian_n(x1, v1, phin, hinfo)
-        u = self._draw((nb,), generator, xn.device, uniform=True)
+        u = draw((nb,), generator, xn.device, uniform=True)
         acc, mask = ops.accept(h0, h1, torch.zeros_like(h0), u)
         xo = ops.select_rows(x1.reshape(nb, -1), xn.reshape(nb, -1), mask).reshape(xn.shape)
         it = info['cg_iters'].to(torch.float64)

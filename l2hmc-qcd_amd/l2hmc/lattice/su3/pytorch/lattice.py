@@ -20,6 +20,7 @@ from l2hmc import _autograd as AG
 from l2hmc import _ops as ops
 from l2hmc.configs import Charges
 from l2hmc.lattice.lattice import Lattice
+from l2hmc.lattice.su3.pytorch.wilson import WilsonFermions, _log_positive, effective_mass, pion_correlator  # noqa: F401
 
 log = logging.getLogger(__name__)
 Tensor = torch.Tensor
@@ -77,12 +78,6 @@ def _site_sum(w: Tensor) -> Tensor:
     return w.sum(tuple(range(2, len(w.shape)))).sum(0)
 
 
-def _log_positive(arg: Tensor) -> Tensor:
-    """ln(arg) where arg is positive and finite, NaN elsewhere"""
-    ok = (arg > 0) & torch.isfinite(arg)
-    return torch.where(ok, torch.log(torch.where(ok, arg, torch.ones_like(arg))), torch.full_like(arg, float('nan')))
-
-
 def creutz_ratios(w: Tensor) -> Tensor:
     """chi(R, T) = -ln[W(R, T) W(R-1, T-1) / (W(R, T-1) W(R-1, T))] for R, T >= 2 from a table w[..., rmax, tmax] with
     w[..., R-1, T-1] = W(R, T): [..., rmax-1, tmax-1], entry [R-2, T-2].  An area law W = exp(-sigma R T - m (R + T) - c)
@@ -96,23 +91,6 @@ def static_potential(w: Tensor) -> Tensor:
     static potential is its plateau at large T.  NaN where the ratio is not positive; never raises."""
     w = torch.as_tensor(w)
     return _log_positive(w[..., :, :-1] / w[..., :, 1:])
-
-
-def pion_correlator(S: Tensor, t_source: int = 0) -> Tensor:
-    """C(t) = sum_x sum_{spins, colours} |S(x, t_source + t)|^2 [nb, T] of a point-to-all propagator S[nb, T, X, Y, Z, 4,
-    3, 4, 3] (`LatticeSU3.quark_propagator`), t counted from the source's time slice (periodically).  By gamma5-
-    Hermiticity this is the pseudoscalar two-point function; it is positive."""
-    S = torch.as_tensor(S)
-    if S.dim() != 9 or tuple(S.shape[-4:]) != (4, 3, 4, 3):
-        raise ValueError(f'pion_correlator: need S [nb, T, X, Y, Z, 4, 3, 4, 3], got {list(S.shape)}')
-    c = (S.real ** 2 + S.imag ** 2).sum(tuple(range(2, 9)))
-    return torch.roll(c, -int(t_source), 1)
-
-
-def effective_mass(C: Tensor) -> Tensor:
-    """m_eff(t) = ln[C(t) / C(t+1)] from C[..., T]: [..., T-1].  NaN where the ratio is not positive; never raises."""
-    C = torch.as_tensor(C)
-    return _log_positive(C[..., :-1] / C[..., 1:])
 
 
 def _first_upward_crossing(t: Tensor, g: Tensor, target: float) -> Tensor:
@@ -154,7 +132,7 @@ def scales_from_flow(t: Tensor, E: Tensor, target: float = 0.3) -> dict[str, Ten
     return {'t0': _first_upward_crossing(t, F, target), 'w0': torch.sqrt(tstar)}
 
 
-class LatticeSU3(Lattice):
+class LatticeSU3(Lattice, WilsonFermions):
     """4D lattice with SU(3) links: x.shape = [nb, 4, nt, nx, ny, nz, 3, 3] complex128."""
     dim = 4
 
@@ -623,308 +601,6 @@ class LatticeSU3(Lattice):
         if xh is None:
             return self.wilson_loop_table(xa, rmax, tmax, time_dir)
         return self.wilson_loop_table_xt(xa, xh, rmax, tmax, time_dir)
-
-    # ------------------------------------------------------------ Wilson fermions
-    @staticmethod
-    def gamma_matrices() -> Tensor:
-        """[5, 4, 4] complex128 (CPU): gamma_0 (T), gamma_1, gamma_2, gamma_3 (x, y, z) and gamma5 = g0 g1 g2 g3 =
-        diag(-1, -1, 1, 1), the Hermitian chiral basis of csrc/su3_wilson.hip: gamma_mu = [[0, B_mu], [B_mu^H, 0]] with
-        B_0 = 1, B_k = -i sigma_k."""
-        sig = torch.tensor([[[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]], dtype=torch.complex128)
-        blocks = [torch.eye(2, dtype=torch.complex128)] + [-1j * s for s in sig]
-        gam = torch.zeros((5, 4, 4), dtype=torch.complex128)
-        for mu, b in enumerate(blocks):
-            gam[mu, :2, 2:] = b
-            gam[mu, 2:, :2] = b.conj().T
-        gam[4] = gam[0] @ gam[1] @ gam[2] @ gam[3]
-        return gam
-
-    def _wilson_checks(self, what: str, kappa, *tensors) -> float:
-        for t in tensors:
-            self._no_grad(t, what)
-        try:
-            k = float(kappa)
-        except (TypeError, ValueError):
-            k = float('nan')
-        if not np.isfinite(k):
-            raise ValueError(f'LatticeSU3.{what}: kappa must be a finite number, got {kappa!r}')
-        return k
-
-    def _spinor_native(self, what: str, xn: Tensor, psin: Tensor) -> tuple[Tensor, bool]:
-        """psin as [nb, nrhs, 12, V] and whether it came without the nrhs axis"""
-        single = psin.dim() == 3
-        p = psin[:, None] if single else psin
-        if p.dim() != 4 or tuple(p.shape[2:]) != (12, self.volume) or p.shape[0] != xn.shape[0]:
-            raise ValueError(f'LatticeSU3.{what}: need a native spinor field [nb, nrhs, 12, V] or [nb, 12, V] with '
-                             f'nb = {xn.shape[0]}, V = {self.volume}, got {list(psin.shape)}')
-        return p.to(torch.complex128).contiguous(), single
-
-    def _spinor_reference(self, what: str, x: Tensor, psi: Tensor) -> tuple[Tensor, bool]:
-        single = psi.dim() == 7
-        p = psi[:, None] if single else psi
-        if p.dim() != 8 or tuple(p.shape[2:]) != (*self._lattice_shape, 4, 3) or p.shape[0] != x.shape[0]:
-            raise ValueError(f'LatticeSU3.{what}: need a spinor field [nb, nrhs, T, X, Y, Z, 4, 3] or one without the nrhs '
-                             f'axis on this lattice, got {list(psi.shape)}')
-        return ops.su3_spinor_pack(p.to(DEVICE)), single
-
-    def wilson_dirac_n(self, xn: Tensor, psin: Tensor, kappa: float, dagger: bool = False,
-                       antiperiodic_t: bool = True) -> Tensor:
-        """M psi = psi - kappa H psi (dagger: M^H psi = gamma5 M gamma5 psi) of a native spinor field [nb, nrhs, 12, V]
-        (or [nb, 12, V]) on the native links xn, thin or smeared,
-            H psi(x) = sum_mu [(1 - gamma_mu) U_mu(x) psi(x+mu) + (1 + gamma_mu) U_mu(x-mu)^H psi(x-mu)],
-        periodic except that with antiperiodic_t every hop across the t = T-1 -> 0 seam takes a factor -1.  One
-        `l2q_su3_wilson_apply`; a new field, nothing is written.  Any extents; any gauge action; no autograd."""
-        k = self._wilson_checks('wilson_dirac', kappa, xn, psin)
-        p, single = self._spinor_native('wilson_dirac', xn, psin)
-        out = ops.su3_wilson_apply_n(xn, p, k, self._lattice_shape, dagger, antiperiodic_t)
-        return out[:, 0] if single else out
-
-    def wilson_dirac(self, x: Tensor, psi: Tensor, kappa: float, dagger: bool = False,
-                     antiperiodic_t: bool = True) -> Tensor:
-        """`wilson_dirac_n` in the reference layout: psi[nb, nrhs, T, X, Y, Z, 4, 3] (spin, then colour), with or
-        without the nrhs axis, which the result then lacks too."""
-        k = self._wilson_checks('wilson_dirac', kappa, x, psi)
-        p, single = self._spinor_reference('wilson_dirac', x, psi)
-        out = ops.su3_spinor_unpack(ops.su3_wilson_apply_n(self.pack(x), p, k, self._lattice_shape, dagger,
-                                                           antiperiodic_t), self._lattice_shape)
-        return out[:, 0] if single else out
-
-    def wilson_solve_n(self, xn: Tensor, bn: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
-                       check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
-        """M psi = b for every system (chain, rhs) of the native field bn at once, by CG on M^H M (CGNR) from psi = 0,
-        with the true residual r = b - M psi carried along: per iteration two `l2q_su3_wilson_apply` (q = M p and
-        z = M^H r, each with its fused norm), one `l2q_su3_spinor_cg_update` and one `l2q_su3_spinor_xpay`;
-        alpha = |z|^2 / |M p|^2 and beta are formed per system on the device.  The host looks at |r|^2 <= tol^2 |b|^2
-        every check_every iterations (and after the last); a system found converged takes alpha = beta = 0 from then
-        on, so it no longer changes while the others go on, and a system's solution is the same bits whatever else is in
-        the batch.  Returns (psi, info): info['iters'] (the check at which a system was found converged, max_iter if
-        never), info['residual'] (|b - M psi| / |b| recomputed after the loop, 0 for b = 0), info['converged'], each
-        [nb, nrhs].  Never raises on non-convergence; b = 0 gives psi = 0.  Workspace: six spinor fields."""
-        k = self._wilson_checks('wilson_solve', kappa, xn, bn)
-        if not (float(tol) > 0.0) or isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 0 \
-                or isinstance(check_every, bool) or int(check_every) != check_every or int(check_every) < 1:
-            raise ValueError(f'LatticeSU3.wilson_solve: need tol > 0, an integer max_iter >= 0 and check_every >= 1, got '
-                             f'{tol!r}, {max_iter!r}, {check_every!r}')
-        b, single = self._spinor_native('wilson_solve', xn, bn)
-        L, tol2 = self._lattice_shape, float(tol) ** 2
-        max_iter, check_every = int(max_iter), int(check_every)
-        nb, nrhs = b.shape[:2]
-
-        def apply(src, dst, part, dagger):
-            ops.su3_wilson_apply_n(xn, src, k, L, dagger, antiperiodic_t, out=dst, norm=part)
-            return ops.sum_parts(part)
-
-        def ratio(live, num, den):
-            ok = live & (den > 0)
-            return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
-
-        psi, r, q, z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
-        part = torch.empty((nb, nrhs, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=b.device)
-        rpart = torch.empty_like(part)
-        zero = torch.zeros((nb, nrhs), dtype=torch.float64, device=b.device)
-        bb = ops.sum_parts(ops.su3_spinor_cg_update_(psi, r, b, b, zero, rpart))        # alpha = 0: |r|^2 = |b|^2
-        zz = apply(r, z, part, True)
-        p = z.clone()
-        active = ~(bb <= tol2 * bb)
-        iters = torch.where(active, max_iter, 0)
-        it = 0
-        while it < max_iter and bool(active.any()):
-            for _ in range(min(check_every, max_iter - it)):
-                qq = apply(p, q, part, False)
-                ops.su3_spinor_cg_update_(psi, r, p, q, ratio(active, zz, qq), rpart)
-                zn = apply(r, z, part, True)
-                ops.su3_spinor_xpay_(p, z, ratio(active, zn, zz))
-                zz = zn
-                it += 1
-            now = active & (ops.sum_parts(rpart) <= tol2 * bb)
-            iters = torch.where(now, it, iters)
-            active = active & ~now
-        # the residual, recomputed: r = b - 1 * (M psi), z and p serving as the update's other pair
-        apply(psi, q, part, False)
-        r.copy_(b)
-        rr = ops.sum_parts(ops.su3_spinor_cg_update_(z, r, p, q, torch.ones_like(zero), rpart))
-        res = torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
-        info = {'iters': iters, 'residual': res, 'converged': ~active}
-        return (psi[:, 0] if single else psi), info
-
-    def wilson_solve(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
-                     check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
-        """`wilson_solve_n` in the reference layout; x may be thin or smeared links, e.g.
-        `wilson_solve(lat.hyp_smear(x), b, kappa)`."""
-        self._wilson_checks('wilson_solve', kappa, x, b)
-        bn, single = self._spinor_reference('wilson_solve', x, b)
-        psin, info = self.wilson_solve_n(self.pack(x), bn, kappa, tol, max_iter, check_every, antiperiodic_t)
-        psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
-        return (psi[:, 0] if single else psi), info
-
-    def quark_propagator_n(self, xn: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
-        """The point-to-all propagator from the site `source` = (t, x, y, z): the twelve unit sources (spin, colour) at
-        that site solved as one nrhs = 12 batch of `wilson_solve_n`.  Returns (S, info), S[nb, 12, 12, V] native:
-        source component 3 spin + colour, then sink component, then site."""
-        self._wilson_checks('quark_propagator', kappa, xn)
-        L = self._lattice_shape
-        try:
-            src = [int(c) for c in source]
-            ok = len(src) == 4 and all(int(c) == c and 0 <= int(c) < n for c, n in zip(source, L))
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f'LatticeSU3.quark_propagator: source must be a site (t, x, y, z) of {list(L)}, got {source!r}')
-        s = ((src[0] * L[1] + src[1]) * L[2] + src[2]) * L[3] + src[3]
-        bn = torch.zeros((xn.shape[0], 12, 12, self.volume), dtype=torch.complex128, device=xn.device)
-        j = torch.arange(12, device=xn.device)
-        bn[:, j, j, s] = 1.0
-        return self.wilson_solve_n(xn, bn, kappa, **solve_kwargs)
-
-    def quark_propagator(self, x: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
-        """`quark_propagator_n` in the reference layout: S[nb, T, X, Y, Z, 4, 3, 4, 3] (sink spin, sink colour, source
-        spin, source colour), for `pion_correlator`."""
-        self._wilson_checks('quark_propagator', kappa, x)
-        sn, info = self.quark_propagator_n(self.pack(x), kappa, source, **solve_kwargs)
-        S = ops.su3_spinor_unpack(sn, self._lattice_shape).movedim(1, -1).contiguous()
-        return S.reshape(*S.shape[:-1], 4, 3), info
-
-    # ------------------------------------------------------------ dynamical Wilson fermions: pseudofermions
-    def _pf_checks(self, what: str, kappa, *tensors) -> float:
-        for t in tensors:
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise ValueError(f'LatticeSU3.{what}: no autograd through the pseudofermion action; detach the fields')
-        return self._wilson_checks(what, kappa, *tensors)
-
-    @staticmethod
-    def _sum_fields(a: Tensor) -> Tensor:
-        """[nb, npf] -> [nb], the fields added in their order (a chain's bits do not depend on the batch)"""
-        s = a[:, 0].clone()
-        for r in range(1, a.shape[1]):
-            s = s + a[:, r]
-        return s
-
-    def wilson_solve_normal_n(self, xn: Tensor, phin: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
-                              check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
-        """M^H M X = phi for every system (chain, field) of the native field phin at once, by CG from X = 0, and
-        Y = M X: what the pseudofermion action |Y|^2 and its force need.  Per iteration q = M p with its fused norm
-        (<p, M^H M p> = |M p|^2), z = M^H q, one `l2q_su3_spinor_cg_update` (X += alpha p, r -= alpha z, |r|^2 fused)
-        and one `l2q_su3_spinor_xpay` (p = r + beta p); alpha = |r|^2 / |M p|^2 and beta are formed per system on the
-        device.  (X from two `wilson_solve_n` would cost twice the operator applications.)  The host looks at |r|^2 <=
-        tol^2 |phi|^2 every check_every iterations; a system found converged takes alpha = beta = 0 from then on, so a
-        system's bits do not depend on the batch.  Never raises on non-convergence; phi = 0 gives X = 0.  Returns (X,
-        Y, info): info['iters'], info['converged'], info['residual'] (|phi - M^H M X| / |phi| recomputed) and
-        info['action'] (|Y|^2 from the fused norm of the last apply), each [nb, npf].  Workspace: seven spinor fields."""
-        k = self._pf_checks('wilson_solve_normal', kappa, xn, phin)
-        if not (float(tol) > 0.0) or isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 0 \
-                or isinstance(check_every, bool) or int(check_every) != check_every or int(check_every) < 1:
-            raise ValueError(f'LatticeSU3.wilson_solve_normal: need tol > 0, an integer max_iter >= 0 and check_every '
-                             f'>= 1, got {tol!r}, {max_iter!r}, {check_every!r}')
-        b, single = self._spinor_native('wilson_solve_normal', xn, phin)
-        L, tol2 = self._lattice_shape, float(tol) ** 2
-        max_iter, check_every = int(max_iter), int(check_every)
-        nb, npf = b.shape[:2]
-
-        def ratio(live, num, den):
-            ok = live & (den > 0)
-            return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
-
-        X, r, q, z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
-        part = torch.empty((nb, npf, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=b.device)
-        rpart = torch.empty_like(part)
-        zero = torch.zeros((nb, npf), dtype=torch.float64, device=b.device)
-        bb = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, b, b, zero, rpart))          # alpha = 0: |r|^2 = |phi|^2
-        p = b.clone()
-        rr = bb
-        active = ~(bb <= tol2 * bb)
-        iters = torch.where(active, max_iter, 0)
-        it = 0
-        while it < max_iter and bool(active.any()):
-            for _ in range(min(check_every, max_iter - it)):
-                ops.su3_wilson_apply_n(xn, p, k, L, False, antiperiodic_t, out=q, norm=part)
-                qq = ops.sum_parts(part)
-                ops.su3_wilson_apply_n(xn, q, k, L, True, antiperiodic_t, out=z)
-                rn = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, p, z, ratio(active, rr, qq), rpart))
-                ops.su3_spinor_xpay_(p, r, ratio(active, rn, rr))
-                rr = rn
-                it += 1
-            now = active & (rr <= tol2 * bb)
-            iters = torch.where(now, it, iters)
-            active = active & ~now
-        Y = torch.empty_like(b)
-        ops.su3_wilson_apply_n(xn, X, k, L, False, antiperiodic_t, out=Y, norm=part)
-        action = ops.sum_parts(part)
-        # the residual, recomputed: r = phi - 1 * (M^H Y), q and p serving as the update's other pair
-        ops.su3_wilson_apply_n(xn, Y, k, L, True, antiperiodic_t, out=z)
-        r.copy_(b)
-        res2 = ops.sum_parts(ops.su3_spinor_cg_update_(q, r, p, z, torch.ones_like(zero), rpart))
-        res = torch.sqrt(res2 / torch.where(bb > 0, bb, torch.ones_like(bb)))
-        info = {'iters': iters, 'converged': ~active, 'residual': res, 'action': action}
-        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
-
-    def wilson_solve_normal(self, x: Tensor, phi: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
-                            check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
-        """`wilson_solve_normal_n` in the reference layout"""
-        self._pf_checks('wilson_solve_normal', kappa, x, phi)
-        pn, single = self._spinor_reference('wilson_solve_normal', x, phi)
-        X, Y, info = self.wilson_solve_normal_n(self.pack(x), pn, kappa, tol, max_iter, check_every, antiperiodic_t)
-        X, Y = (ops.su3_spinor_unpack(f, self._lattice_shape) for f in (X, Y))
-        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
-
-    def pseudofermion_refresh_n(self, xn: Tensor, kappa: float, npf: int = 1,
-                                generator: Optional[torch.Generator] = None,
-                                antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
-        """The pseudofermion heatbath: eta complex Gaussian with density exp(-eta^H eta) (variance 1/2 per real
-        component; `torch.randn((nb, npf, 12, V, 2), dtype=float64)` on the device, or on the host with a CPU
-        generator: the same numbers on any machine), phi = M^H eta, which is distributed as exp(-S_f).  Returns (phi
-        [nb, npf, 12, V], S0 [nb]): S0 = |eta|^2 is S_f(phi) on these links without a solve."""
-        k = self._pf_checks('pseudofermion_refresh', kappa, xn)
-        if isinstance(npf, bool) or not isinstance(npf, (int, np.integer)) or int(npf) < 1:
-            raise ValueError(f'LatticeSU3.pseudofermion_refresh: npf must be an integer >= 1, got {npf!r}')
-        shape = (xn.shape[0], int(npf), 12, self.volume, 2)
-        if generator is None or generator.device.type == xn.device.type:
-            g = torch.randn(shape, dtype=torch.float64, device=xn.device, generator=generator)
-        else:
-            g = torch.randn(shape, dtype=torch.float64, generator=generator).to(xn.device)
-        eta = torch.view_as_complex(g * float(np.sqrt(0.5))).contiguous()
-        phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
-        zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
-        part = ops.su3_spinor_cg_update_(torch.zeros_like(eta), eta, phi, phi, zero)     # alpha = 0: |eta|^2
-        return phi, self._sum_fields(ops.sum_parts(part))
-
-    def pseudofermion_refresh(self, x: Tensor, kappa: float, npf: int = 1, generator: Optional[torch.Generator] = None,
-                              antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
-        """`pseudofermion_refresh_n` in the reference layout: phi[nb, npf, T, X, Y, Z, 4, 3]"""
-        self._pf_checks('pseudofermion_refresh', kappa, x)
-        phi, s0 = self.pseudofermion_refresh_n(self.pack(x), kappa, npf, generator, antiperiodic_t)
-        return ops.su3_spinor_unpack(phi, self._lattice_shape), s0
-
-    def pseudofermion_action_n(self, xn: Tensor, phin: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
-        """S_f = sum_r phi_r^H (M^H M)^-1 phi_r = sum_r |Y_r|^2 per chain, by one `wilson_solve_normal_n` (whose
-        keywords these are): (S_f [nb], info)."""
-        self._pf_checks('pseudofermion_action', kappa, xn, phin)
-        b, _ = self._spinor_native('pseudofermion_action', xn, phin)
-        _, _, info = self.wilson_solve_normal_n(xn, b, kappa, **solve_kwargs)
-        return self._sum_fields(info['action']), info
-
-    def pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
-        """`pseudofermion_action_n` in the reference layout"""
-        self._pf_checks('pseudofermion_action', kappa, x, phi)
-        pn, _ = self._spinor_reference('pseudofermion_action', x, phi)
-        return self.pseudofermion_action_n(self.pack(x), pn, kappa, **solve_kwargs)
-
-    def pseudofermion_force_n(self, xn: Tensor, phin: Tensor, kappa: float,
-                              **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
-        """The force of S_f on the links, in the convention of `grad_action_n` (dS_f/dt = sum <p, F> under dU/dt =
-        p U; the kick is p <- p - eps F): one `wilson_solve_normal_n` and one `l2q_su3_wilson_force` (see l2q.h).
-        Returns (F [nb, 4, 9, V], S_f [nb], info)."""
-        k = self._pf_checks('pseudofermion_force', kappa, xn, phin)
-        b, _ = self._spinor_native('pseudofermion_force', xn, phin)
-        X, Y, info = self.wilson_solve_normal_n(xn, b, k, **solve_kwargs)
-        F = ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True))
-        return F, self._sum_fields(info['action']), info
-
-    def pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
-        """`pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]"""
-        self._pf_checks('pseudofermion_force', kappa, x, phi)
-        pn, _ = self._spinor_reference('pseudofermion_force', x, phi)
-        F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, **solve_kwargs)
-        return self.unpack(F), s, info
 
     # ------------------------------------------------------------ heatbath and overrelaxation sweeps
     def _local_update_checks(self, xn: Tensor, what: str, nsweeps: int, nover: int = 0) -> None:
