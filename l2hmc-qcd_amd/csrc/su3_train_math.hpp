@@ -352,14 +352,25 @@ __device__ __forceinline__ void m3_projsu_vec8_vjp(M3& g, const M3& m, const dou
     // (same bits): links that are already unitary -- the x of every v-net call -- stop after one or two
     if (!l2q_wave_any(live)) break;
   }
-  const double ev[3] = {sqrt(fabs(a2.re[0])), sqrt(fabs(a2.re[4])), sqrt(fabs(a2.re[8]))};   // eig(H)
-  const double iev[3] = {1.0 / ev[0], 1.0 / ev[1], 1.0 / ev[2]};
   // Everything after the decomposition stays in the eigenbasis (round 4: six 3x3 products instead of nine):
   //   P = U V = M V diag(1/h);   theta from det M (det H > 0, so arg det U = arg det M);
   //   G' = g_W V;   c = Re tr(g_W^H i W) = -Im(phi tr(G'^H P));   Q = g_U V = conj(phi) G' - (c/3) i P;
   //   V^H (U^H g_U) V = P^H Q;   Kt_ij = (P^H Q)_ij / (h_i + h_j);   g_M = U (K - K^H) = P (Kt - Kt^H) V^H.
   M3 pm;
   m3_mul_nn(pm, m, vm);                                // M V
+  // eig(H) as the column norms h_j = |M v_j|, not as the square roots of the diagonal the sweeps left: an
+  // eigenvalue of the SQUARED matrix M^H M is known to u sigma_max^2 only, which for sigma_j = sigma_max / 100
+  // is 1e4 u of itself (35 units of u |g_y| cond / sigma_min in g_M at singular values (1, 0.1, 0.01)); the norm
+  // of M v_j has sigma_j to rounding, the error of v_j entering in second order
+  double ev[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    double n2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) n2 += pm.re[3 * i + j] * pm.re[3 * i + j] + pm.im[3 * i + j] * pm.im[3 * i + j];
+    ev[j] = sqrt(n2);
+  }
+  const double iev[3] = {1.0 / ev[0], 1.0 / ev[1], 1.0 / ev[2]};
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
