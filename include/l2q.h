@@ -446,6 +446,29 @@ int l2q_su3_spinor_xpay(void* p, const void* z, const double* beta, long nsys, l
  * npf <= 0 or another non-positive size; nb * npf * 12 * V of 2^31 or more; flags other than 0 or 2. */
 int l2q_su3_wilson_force(const void* xn, const void* X, const void* Y, const void* f_in, void* f_out, double kappa,
                          double coef, int flags, int nb, int npf, int T, int X_, int Y_, int Z, void* stream);
+/* csrc/su3_wilson_eo.hip.  The half-lattice hop of even-odd preconditioning.  H couples sites of opposite parity only
+ * (parity of a site: (t + x + y + z) & 1, 0 even), so M psi = b reduces to the Schur system on the even sites,
+ *   Mhat psi_e = b_e + kappa H_eo b_o,   Mhat = 1 - kappa^2 H_eo H_oe,   psi_o = b_o + kappa H_oe psi_e.
+ * A half field is psi_h[nb][nrhs][12][V/2] complex128: the sites of one parity in lexicographic order; with Z even the
+ * sites 2h and 2h + 1 have opposite parity, so site s of either parity has the half index s >> 1.  The links xn stay in
+ * the full native layout [nb][4][9][V].  For every system and every site x of parity `parity`:
+ *   out(x) = b aux(x) + a (H src)(x),
+ * src a half field on the other parity, aux and out half fields on `parity`; aux may be null, then the b term is absent.
+ * H, the gamma basis, the seam sign and flags (bit 0 dagger: the projector signs swapped, gamma5 H gamma5; bit 1
+ * antiperiodic in t) are those of l2q_su3_wilson_apply; the dagger bit on both hops gives Mhat^H.  Uses: H_oe or H_eo
+ * alone (a = 1, b = 0, aux null); the second half of Mhat (a = -kappa^2, b = 1, aux = psi_e); the source b_e + kappa
+ * H_eo b_o and the reconstruction b_o + kappa H_oe psi_e (a = kappa, b = 1).  All four extents even; an extent of 2 is
+ * legal: the forward and the backward neighbour coincide and both terms are added.  out may be aux; it must not be src
+ * or xn.  One thread per (system, half-site), 1320 flops (+ 48 with aux); algorithmic traffic per (system, half-site)
+ * 192 B of output, 192 B of aux if given, 192 B of src (each entry read once; the eight neighbours come from cache) and
+ * 1152 B of links, the eight links at and behind the site, which the nrhs systems of a chain share -- each link load
+ * reads every second site of a link plane and so uses half of every cache line it touches.
+ * norm_part (may be null): [nb][nrhs][ceil((V/2) / 256)] partial sums of |out|^2, one per workgroup, in the fixed order
+ * of l2q_su3_wilson_apply's: a system's partials are the same bits whatever else the batch holds.
+ * L2Q_EINVAL, before any HIP call: a null xn, src or out; out aliasing src or xn; a non-positive size; nb * nrhs * 12 *
+ * V of 2^31 or more; a or b not finite; flags outside 0..3; parity not 0 or 1.  L2Q_ESHAPE: an odd extent. */
+int l2q_su3_wilson_hop_eo(const void* xn, const void* src, const void* aux, void* out, double* norm_part, double a,
+                          double b, int flags, int parity, int nb, int nrhs, int T, int X, int Y, int Z, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

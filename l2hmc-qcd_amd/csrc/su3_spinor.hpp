@@ -1,6 +1,7 @@
 // su3_spinor.hpp -- what the kernels over spinor fields share (su3_wilson.hip: the Wilson-Dirac operator;
-// su3_wilson_force.hip: the pseudofermion force): the half spinor of a rank-2 projector 1 -+ gamma_mu, its
-// projection from a field in the layout psi[system][12][V], its product with a link, and the size check.
+// su3_wilson_eo.hip: its half-lattice hop; su3_wilson_force.hip: the pseudofermion force): the half spinor of a rank-2
+// projector 1 -+ gamma_mu, its projection from a field in the layout psi[system][12][V], its product with a link, its
+// reconstruction into the sum of a site, the workgroup order of the operator kernels, and the size check.
 //
 // Gamma matrices: Hermitian, chiral, gamma_mu = [[0, B_mu], [B_mu^H, 0]] in 2 x 2 blocks with
 //   B_0 = 1 (direction 0 is T),  B_k = -i sigma_k (k = 1, 2, 3 = x, y, z),  gamma5 = g0 g1 g2 g3 = diag(-1, -1, 1, 1).
@@ -69,6 +70,45 @@ __device__ __forceinline__ void wilson_colour_mul(HalfSpinor& chi, const M3& u, 
       }
       chi.re[3 * a + i] = re; chi.im[3 * a + i] = im;
     }
+}
+
+// acc += (chi, -sg B_mu^H chi)
+__device__ __forceinline__ void wilson_reconstruct(double (&ar)[12], double (&ai)[12], const HalfSpinor& chi, int mu,
+                                                   double sg) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { ar[k] += chi.re[k]; ai[k] += chi.im[k]; }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double r0 = chi.re[c], i0 = chi.im[c], r1 = chi.re[3 + c], i1 = chi.im[3 + c];
+    switch (mu) {
+      case 0:            // (-sg chi0, -sg chi1)
+        ar[6 + c] = fma(-sg, r0, ar[6 + c]); ai[6 + c] = fma(-sg, i0, ai[6 + c]);
+        ar[9 + c] = fma(-sg, r1, ar[9 + c]); ai[9 + c] = fma(-sg, i1, ai[9 + c]);
+        break;
+      case 1:            // (-i sg chi1, -i sg chi0)
+        ar[6 + c] = fma(sg, i1, ar[6 + c]); ai[6 + c] = fma(-sg, r1, ai[6 + c]);
+        ar[9 + c] = fma(sg, i0, ar[9 + c]); ai[9 + c] = fma(-sg, r0, ai[9 + c]);
+        break;
+      case 2:            // (-sg chi1, sg chi0)
+        ar[6 + c] = fma(-sg, r1, ar[6 + c]); ai[6 + c] = fma(-sg, i1, ai[6 + c]);
+        ar[9 + c] = fma(sg, r0, ar[9 + c]); ai[9 + c] = fma(sg, i0, ai[9 + c]);
+        break;
+      default:           // (-i sg chi0, i sg chi1)
+        ar[6 + c] = fma(sg, i0, ar[6 + c]); ai[6 + c] = fma(-sg, r0, ai[6 + c]);
+        ar[9 + c] = fma(-sg, i1, ar[9 + c]); ai[9 + c] = fma(sg, r1, ai[9 + c]);
+        break;
+    }
+  }
+}
+
+// the system and the site block of workgroup w: chain, site block, right-hand side (the fastest)
+struct WilsonBlock {
+  long c, sys;
+  int blk;
+};
+__device__ __forceinline__ WilsonBlock wilson_block(long w, int nrhs, long nblk) {
+  const long c = w / (nblk * nrhs), rest = w % (nblk * nrhs);
+  return WilsonBlock{c, c * nrhs + rest % nrhs, (int)(rest / nrhs)};
 }
 
 // nsys systems of 12 V complex entries: positive sizes, and every entry's index fits an int (in double: no overflow)

@@ -22,49 +22,11 @@
 // Block order: chain, site block, right-hand side -- consecutive workgroups read the same links (profiles/su3_wilson.md).
 // su3_spinor_cg_update_kernel, su3_spinor_xpay_kernel: one thread per (system, site), the 12 components in turn; the
 // coefficients come from a device array, one per system.
-// HalfSpinor, wilson_project, wilson_colour_mul and spinor_dims_ok: su3_spinor.hpp, shared with su3_wilson_force.hip.
+// HalfSpinor, wilson_project, wilson_colour_mul, wilson_reconstruct, wilson_block and spinor_dims_ok: su3_spinor.hpp,
+// shared with su3_wilson_eo.hip (the half-lattice hop) and su3_wilson_force.hip.
 #include "su3_spinor.hpp"
 
 namespace l2q {
-
-// acc += (chi, -sg B_mu^H chi)
-__device__ __forceinline__ void wilson_reconstruct(double (&ar)[12], double (&ai)[12], const HalfSpinor& chi, int mu,
-                                                   double sg) {
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { ar[k] += chi.re[k]; ai[k] += chi.im[k]; }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double r0 = chi.re[c], i0 = chi.im[c], r1 = chi.re[3 + c], i1 = chi.im[3 + c];
-    switch (mu) {
-      case 0:            // (-sg chi0, -sg chi1)
-        ar[6 + c] = fma(-sg, r0, ar[6 + c]); ai[6 + c] = fma(-sg, i0, ai[6 + c]);
-        ar[9 + c] = fma(-sg, r1, ar[9 + c]); ai[9 + c] = fma(-sg, i1, ai[9 + c]);
-        break;
-      case 1:            // (-i sg chi1, -i sg chi0)
-        ar[6 + c] = fma(sg, i1, ar[6 + c]); ai[6 + c] = fma(-sg, r1, ai[6 + c]);
-        ar[9 + c] = fma(sg, i0, ar[9 + c]); ai[9 + c] = fma(-sg, r0, ai[9 + c]);
-        break;
-      case 2:            // (-sg chi1, sg chi0)
-        ar[6 + c] = fma(-sg, r1, ar[6 + c]); ai[6 + c] = fma(-sg, i1, ai[6 + c]);
-        ar[9 + c] = fma(sg, r0, ar[9 + c]); ai[9 + c] = fma(sg, i0, ai[9 + c]);
-        break;
-      default:           // (-i sg chi0, i sg chi1)
-        ar[6 + c] = fma(sg, i0, ar[6 + c]); ai[6 + c] = fma(-sg, r0, ai[6 + c]);
-        ar[9 + c] = fma(-sg, i1, ar[9 + c]); ai[9 + c] = fma(sg, r1, ai[9 + c]);
-        break;
-    }
-  }
-}
-
-// the system and the site block of workgroup w: chain, site block, right-hand side (the fastest)
-struct WilsonBlock {
-  long c, sys;
-  int blk;
-};
-__device__ __forceinline__ WilsonBlock wilson_block(long w, int nrhs, long nblk) {
-  const long c = w / (nblk * nrhs), rest = w % (nblk * nrhs);
-  return WilsonBlock{c, c * nrhs + rest % nrhs, (int)(rest / nrhs)};
-}
 
 // sgn: +1 for M, -1 for M^H; apbc: the seam of direction 0 carries -1.  part (may be null): [system][nblk].
 // The kernel has a barrier where part is given: threads past the last site run along on site 0 and write nothing.

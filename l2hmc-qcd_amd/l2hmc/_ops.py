@@ -712,6 +712,88 @@ def su3_wilson_force_n(xn: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, kappa
     return out
 
 
+def _even_lattice(what: str, lat: Sequence[int]) -> tuple:
+    L = tuple(int(i) for i in lat)
+    if len(L) != 4 or any(e < 2 or e & 1 for e in L):
+        raise ValueError(f'{what}: even-odd preconditioning needs even extents, got the lattice {list(L)}')
+    return L
+
+
+_EO_SITES: dict = {}
+
+
+def su3_eo_sites(lat: Sequence[int], device) -> tuple[torch.Tensor, torch.Tensor]:
+    """(even, odd): the sites of each parity (t + x + y + z) & 1 in lexicographic order, int64 [V/2] each, cached per
+    (lattice, device); entry h of either is the site 2h or 2h + 1"""
+    L = _even_lattice('su3_eo_sites', lat)
+    key = (L, str(torch.device(device)))
+    if key not in _EO_SITES:
+        t, x, y, z = torch.meshgrid(*[torch.arange(e) for e in L], indexing='ij')
+        par = ((t + x + y + z) & 1).reshape(-1)
+        _EO_SITES[key] = tuple(torch.nonzero(par == p).reshape(-1).to(device) for p in (0, 1))
+    return _EO_SITES[key]
+
+
+def su3_spinor_split_eo(pn: torch.Tensor, lat: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    """pn[nb, nrhs, 12, V] -> (even, odd) half fields [nb, nrhs, 12, V/2]: new tensors, by a gather"""
+    L = _even_lattice('su3_spinor_split_eo', lat)
+    if pn.dim() != 4 or pn.shape[2] != 12 or pn.shape[3] != L[0] * L[1] * L[2] * L[3]:
+        raise ValueError(f'su3_spinor_split_eo: need pn [nb, nrhs, 12, V] on {list(L)}, got {list(pn.shape)}')
+    e, o = su3_eo_sites(L, pn.device)
+    return pn.index_select(3, e), pn.index_select(3, o)
+
+
+def su3_spinor_merge_eo(even: torch.Tensor, odd: torch.Tensor, lat: Sequence[int]) -> torch.Tensor:
+    """the inverse of `su3_spinor_split_eo`: a new full field [nb, nrhs, 12, V]"""
+    L = _even_lattice('su3_spinor_merge_eo', lat)
+    Vh = L[0] * L[1] * L[2] * L[3] // 2
+    if even.dim() != 4 or tuple(even.shape[2:]) != (12, Vh) or odd.shape != even.shape or odd.dtype != even.dtype:
+        raise ValueError(f'su3_spinor_merge_eo: need two half fields [nb, nrhs, 12, {Vh}] on {list(L)}, got '
+                         f'{list(even.shape)} and {list(odd.shape)}')
+    e, o = su3_eo_sites(L, even.device)
+    pn = torch.empty((*even.shape[:3], 2 * Vh), dtype=even.dtype, device=even.device)
+    pn.index_copy_(3, e, even)
+    pn.index_copy_(3, o, odd)
+    return pn
+
+
+def su3_wilson_hop_eo_n(xn: torch.Tensor, src: torch.Tensor, lat: Sequence[int], parity: int, dagger: bool = False,
+                        antiperiodic_t: bool = True, a: float = 1.0, aux: Optional[torch.Tensor] = None, b: float = 0.0,
+                        out: Optional[torch.Tensor] = None, norm: bool = False):
+    """out = b aux + a H src on the sites of `parity` (0 even, 1 odd): src[nb, nrhs, 12, V/2] a half field on the other
+    parity, aux (None: no b term) and out half fields on this one, on the full native links xn (see l2q.h).  out None =
+    a new field; out may be aux, never src.  norm as in `su3_wilson_apply_n`: True returns (out, part), part[nb, nrhs,
+    ceil((V/2) / 256)] the partial sums of |out|^2; or the tensor to write them to."""
+    T, X, Y, Z = _even_lattice('su3_wilson_hop_eo_n', lat)
+    Vh = T * X * Y * Z // 2
+    if parity not in (0, 1):
+        raise ValueError(f'su3_wilson_hop_eo_n: parity must be 0 or 1, got {parity!r}')
+    if src.dim() != 4 or src.shape[0] != xn.shape[0] or src.shape[2] != 12 or src.shape[3] != Vh \
+            or xn.shape[-1] != 2 * Vh:
+        raise ValueError(f'su3_wilson_hop_eo_n: need a half field src [nb, nrhs, 12, V/2] on xn {list(xn.shape)}, got '
+                         f'{list(src.shape)}')
+    _spinor_check('su3_wilson_hop_eo_n', 'src', src, src.shape)
+    if aux is not None:
+        _spinor_check('su3_wilson_hop_eo_n', 'aux', aux, src.shape)
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _spinor_check('su3_wilson_hop_eo_n', 'out', out, src.shape)
+    nb, nrhs = src.shape[:2]
+    parts = -(-Vh // 256)
+    part = None
+    if isinstance(norm, torch.Tensor):
+        part = norm
+        if part.dtype != torch.float64 or tuple(part.shape) != (nb, nrhs, parts) or not part.is_contiguous():
+            raise ValueError(f'su3_wilson_hop_eo_n: norm must be contiguous float64 {[nb, nrhs, parts]}, got '
+                             f'{list(part.shape)}')
+    elif norm:
+        part = torch.empty((nb, nrhs, parts), dtype=torch.float64, device=src.device)
+    N.call('l2q_su3_wilson_hop_eo', xn, src, aux, out, part, float(a), float(b),
+           int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1), int(parity), nb, nrhs, T, X, Y, Z)
+    return out if part is None else (out, part)
+
+
 def sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
     partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""

@@ -21,7 +21,10 @@ Tensor = torch.Tensor
 class WilsonHMC:
     """One trajectory: momentum and pseudofermion refresh, `nleapfrog` leapfrog steps of size `eps` under the force of
     S_g(beta) + S_f(kappa), accept / reject per chain.  The solves of the molecular dynamics stop at `tol_md`, those
-    of the Hamiltonian at `tol_h`; a solve that reaches `max_iter` is counted (metrics['unconverged']), not raised."""
+    of the Hamiltonian at `tol_h`; a solve that reaches `max_iter` is counted (metrics['unconverged']), not raised.
+    `even_odd` is False here and True in `WilsonHMCEvenOdd`, which runs the same trajectory on the Schur complement."""
+
+    even_odd = False
 
     def __init__(self, lattice: LatticeSU3, beta: float, kappa: float, eps: float, nleapfrog: int, npf: int = 1,
                  tol_md: float = 1e-8, tol_h: float = 1e-12, max_iter: int = 2000, antiperiodic_t: bool = True) -> None:
@@ -41,6 +44,8 @@ class WilsonHMC:
         self.nleapfrog, self.npf, self.max_iter = int(nleapfrog), int(npf), int(max_iter)
         self.tol_md, self.tol_h = float(tol_md), float(tol_h)
         self.antiperiodic_t = bool(antiperiodic_t)
+        if self.even_odd:
+            lattice._eo_lattice('WilsonHMCEvenOdd')
 
     # ------------------------------------------------------------ the pieces
     def _solve_kw(self, tol: float) -> dict:
@@ -53,7 +58,10 @@ class WilsonHMC:
             ops.su3_force_kick_n(xn, self.beta, -step, vn, L)
         else:
             ops.axpy_(vn, lat.grad_action_n(xn, self.beta), -step)
-        X, Y, info = lat.wilson_solve_normal_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
+        if self.even_odd:                    # the full fields whose force is the even-odd one
+            X, Y, info = lat._schur_force_fields_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
+        else:
+            X, Y, info = lat.wilson_solve_normal_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
         ops.su3_wilson_force_n(xn, X, Y, self.kappa, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
         infos.append(info)
 
@@ -73,7 +81,8 @@ class WilsonHMC:
 
     def hamiltonian_n(self, xn: Tensor, vn: Tensor, phin: Tensor, info: Optional[dict] = None) -> Tensor:
         """H [nb] = kinetic + S_g + S_f, the solve at tol_h; `info`, if given, receives the solve's info"""
-        sf, sinfo = self.lattice.pseudofermion_action_n(xn, phin, self.kappa, **self._solve_kw(self.tol_h))
+        sf, sinfo = self.lattice.pseudofermion_action_n(xn, phin, self.kappa, even_odd=self.even_odd,
+                                                        **self._solve_kw(self.tol_h))
         if info is not None:
             info.update(sinfo)
         return ops.su3_kinetic_n(vn) + self.lattice.action_n(xn, self.beta) + sf
@@ -81,12 +90,14 @@ class WilsonHMC:
     # ------------------------------------------------------------ the trajectory
     def trajectory_n(self, xn: Tensor, generator: Optional[torch.Generator] = None) -> tuple[Tensor, dict]:
         """One trajectory on a native field: (x_out, metrics).  Draws, in this order: the momentum normals
-        randn((8, nb, 4, V)), the pseudofermion noise (`pseudofermion_refresh_n`), the accept uniforms rand(nb)."""
+        randn((8, nb, 4, V)), the pseudofermion noise (`pseudofermion_refresh_n`; with even_odd
+        `pseudofermion_refresh_eo_n`: the half shape), the accept uniforms rand(nb)."""
         lat = self.lattice
         nb = xn.shape[0]
         xn = xn.detach().contiguous()
         vn = ops.su3_assemble_tah_n(draw((8, nb, 4, lat.volume), generator, xn.device))
-        phin, s0 = lat.pseudofermion_refresh_n(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
+        refresh = lat.pseudofermion_refresh_eo_n if self.even_odd else lat.pseudofermion_refresh_n
+        phin, s0 = refresh(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
         h0 = ops.su3_kinetic_n(vn) + lat.action_n(xn, self.beta) + s0             # S_f(phi) = |eta|^2: no solve
         x1, v1, info = self.leapfrog_n(xn, vn, phin)
         hinfo: dict = {}
@@ -123,3 +134,13 @@ class WilsonHMC:
             xn, m = self.trajectory_n(xn, generator)
             history.append(m)
         return self.lattice.unpack(xn), history
+
+
+class WilsonHMCEvenOdd(WilsonHMC):
+    """`WilsonHMC` with even-odd preconditioning (even extents; same arguments, same draw order, same metrics): the
+    pseudofermion lives on the even sites, S_f = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r on the Schur complement Mhat =
+    1 - kappa^2 H_eo H_oe -- the same ensemble, det Mhat = det M.  The refresh, every solve of the molecular dynamics,
+    the force and `hamiltonian_n` use the Schur forms; `phin` is a half field [nb, npf, 12, V/2] and the pseudofermion
+    noise is drawn with that shape."""
+
+    even_odd = True

@@ -52,30 +52,92 @@ def ratio(live: Tensor, num: Tensor, den: Tensor) -> Tensor:
     return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
 
 
-class _CG:
-    """What `wilson_solve_n` and `wilson_solve_normal_n` share: a batched CG from x = 0 for every system (chain, rhs) of
-    the native field bn at once.  It owns the argument checks, the workspace (x, r, q, z, the partial sums rpart of the
-    updates, bb = |b|^2), the loop with its look at |r|^2 <= tol^2 |b|^2 every check_every iterations (and after the
-    last), and the recomputed residual; a solver adds its start, the body of the loop and its last applies."""
+class _WilsonOp:
+    """M on full fields [nb, nrhs, 12, V] as the operator of a `_CG`: apply(src, dst, dagger, norm) writes dst = M src
+    (dagger: M^H src) and, with norm, returns the fused |dst|^2 [nb, nrhs]; `sites` is the site count of its fields."""
 
-    def __init__(self, lat, what: str, xn: Tensor, bn: Tensor, k: float, tol, max_iter, check_every, antiperiodic_t):
+    def __init__(self, xn: Tensor, k: float, L, antiperiodic_t, like: Tensor):
+        self.sites = like.shape[3]
+        part = torch.empty((*like.shape[:2], ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=like.device)
+
+        def apply(src, dst, dagger, norm=True):
+            ops.su3_wilson_apply_n(xn, src, k, L, dagger, antiperiodic_t, out=dst, norm=part if norm else False)
+            return ops.sum_parts(part) if norm else None
+        self.apply = apply
+
+
+class _SchurOp:
+    """Mhat = 1 - kappa^2 H_eo H_oe on even half fields [nb, nrhs, 12, V/2] as the operator of a `_CG`: two
+    `su3_wilson_hop_eo_n` through one scratch odd half field, the fused norm from the second.  The dagger bit on both
+    hops gives Mhat^H.  dst must not be src."""
+
+    def __init__(self, xn: Tensor, k: float, L, antiperiodic_t, like: Tensor):
+        self.sites = like.shape[3]
+        part = torch.empty((*like.shape[:2], -(-self.sites // 256)), dtype=torch.float64, device=like.device)
+        odd = torch.empty_like(like)
+
+        def apply(src, dst, dagger, norm=True):
+            ops.su3_wilson_hop_eo_n(xn, src, L, 1, dagger, antiperiodic_t, out=odd)
+            ops.su3_wilson_hop_eo_n(xn, odd, L, 0, dagger, antiperiodic_t, a=-k * k, aux=src, b=1.0, out=dst,
+                                    norm=part if norm else False)
+            return ops.sum_parts(part) if norm else None
+        self.apply = apply
+
+
+class _CG:
+    """What the solvers share: a batched CG from x = 0 for every system (chain, rhs) of the field b [nb, nrhs, 12,
+    sites] at once, on the operator `op` (`_WilsonOp` on full fields, `_SchurOp` on even half fields: its apply(src,
+    dst, dagger, norm) and the site count of its fields).  It owns the argument checks, the workspace (x, r, q, z, the
+    partial sums rpart of the updates), the loop with its look at |r|^2 <= tol^2 bb every check_every iterations (and
+    after the last), and the recomputed residual; bb, the reference norm of the stopping test, is |b|^2 unless given (the
+    even-odd solve gives |b|^2 of the full right-hand side).  `cgnr` and `normal` are the two loop bodies."""
+
+    @staticmethod
+    def check_args(what: str, tol, max_iter, check_every) -> None:
         if not (float(tol) > 0.0) or isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 0 \
                 or isinstance(check_every, bool) or int(check_every) != check_every or int(check_every) < 1:
             raise ValueError(f'LatticeSU3.{what}: need tol > 0, an integer max_iter >= 0 and check_every >= 1, got '
                              f'{tol!r}, {max_iter!r}, {check_every!r}')
-        self.b, self.single = lat._spinor_native(what, xn, bn)
-        b, L = self.b, lat._lattice_shape
+
+    def __init__(self, what: str, b: Tensor, single: bool, op, tol, max_iter, check_every, bb: Optional[Tensor] = None):
+        self.check_args(what, tol, max_iter, check_every)
+        assert b.shape[3] == op.sites
+        self.b, self.single, self.apply = b, single, op.apply
         self.tol2, self.max_iter, self.check_every = float(tol) ** 2, int(max_iter), int(check_every)
         self.x, self.r, self.q, self.z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
-        part = torch.empty((*b.shape[:2], ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=b.device)
-        self.rpart = torch.empty_like(part)
+        self.rpart = torch.empty((*b.shape[:2], -(-op.sites // 256)), dtype=torch.float64, device=b.device)
         self.zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
+        self.bb0 = ops.sum_parts(ops.su3_spinor_cg_update_(self.x, self.r, b, b, self.zero, self.rpart))   # alpha = 0: |b|^2
+        self.bb = self.bb0 if bb is None else bb
 
-        def apply(src, dst, dagger, norm=True):            # dst = M src (dagger: M^H src); with norm, the fused |dst|^2
-            ops.su3_wilson_apply_n(xn, src, k, L, dagger, antiperiodic_t, out=dst, norm=part if norm else False)
-            return ops.sum_parts(part) if norm else None
-        self.apply = apply
-        self.bb = ops.sum_parts(ops.su3_spinor_cg_update_(self.x, self.r, b, b, self.zero, self.rpart))   # alpha = 0: |b|^2
+    def cgnr(self) -> None:
+        """A x = b by CG on A^H A with the true residual r = b - A x carried along; leaves x, and A x in q"""
+        psi, r, q, z, apply = self.x, self.r, self.q, self.z, self.apply
+        zz = apply(r, z, True)
+        self.p = p = z.clone()
+        for active in self.iterations(lambda: ops.sum_parts(self.rpart)):      # |r|^2 is summed at a check only
+            qq = apply(p, q, False)
+            ops.su3_spinor_cg_update_(psi, r, p, q, ratio(active, zz, qq), self.rpart)
+            zn = apply(r, z, True)
+            ops.su3_spinor_xpay_(p, z, ratio(active, zn, zz))
+            zz = zn
+        apply(psi, q, False)
+
+    def normal(self) -> tuple[Tensor, Tensor]:
+        """A^H A X = b by CG: (Y = A X, |Y|^2 from the fused norm); leaves X in x and A^H A X in z"""
+        X, r, q, z, apply = self.x, self.r, self.q, self.z, self.apply
+        self.p = p = self.b.clone()
+        rr = self.bb0
+        for active in self.iterations(lambda: rr):                             # |r|^2 is carried from every update
+            qq = apply(p, q, False)
+            apply(q, z, True, norm=False)
+            rn = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, p, z, ratio(active, rr, qq), self.rpart))
+            ops.su3_spinor_xpay_(p, r, ratio(active, rn, rr))
+            rr = rn
+        Y = torch.empty_like(X)
+        action = apply(X, Y, False)
+        apply(Y, z, True, norm=False)
+        return Y, action
 
     def iterations(self, rnorm):
         """`active` [nb, nrhs] once per iteration, for `ratio`.  At a check a system with rnorm() <= tol^2 |b|^2 leaves
@@ -178,20 +240,46 @@ class WilsonFermions:
         on, so it no longer changes while the others go on, and a system's solution is the same bits whatever else is in
         the batch.  Returns (psi, info): info['iters'] (the check at which a system was found converged, max_iter if
         never), info['residual'] (|b - M psi| / |b| recomputed after the loop, 0 for b = 0), info['converged'], each
-        [nb, nrhs].  Never raises on non-convergence; b = 0 gives psi = 0.  Workspace: six spinor fields."""
+        [nb, nrhs].  Never raises on non-convergence; b = 0 gives psi = 0.  Workspace: six spinor fields.
+        `wilson_solve_eo_n` is the same solve through the even-odd Schur complement."""
         k = self._wilson_checks('wilson_solve', kappa, xn, bn)
-        cg = _CG(self, 'wilson_solve', xn, bn, k, tol, max_iter, check_every, antiperiodic_t)
-        psi, r, q, z, apply = cg.x, cg.r, cg.q, cg.z, cg.apply
-        zz = apply(r, z, True)
-        p = z.clone()
-        for active in cg.iterations(lambda: ops.sum_parts(cg.rpart)):      # |r|^2 is summed at a check only
-            qq = apply(p, q, False)
-            ops.su3_spinor_cg_update_(psi, r, p, q, ratio(active, zz, qq), cg.rpart)
-            zn = apply(r, z, True)
-            ops.su3_spinor_xpay_(p, z, ratio(active, zn, zz))
-            zz = zn
-        apply(psi, q, False)
-        return (psi[:, 0] if cg.single else psi), cg.info(z, p, q)
+        _CG.check_args('wilson_solve', tol, max_iter, check_every)
+        b, single = self._spinor_native('wilson_solve', xn, bn)
+        op = _WilsonOp(xn, k, self._lattice_shape, antiperiodic_t, b)
+        cg = _CG('wilson_solve', b, single, op, tol, max_iter, check_every)
+        cg.cgnr()
+        return (cg.x[:, 0] if single else cg.x), cg.info(cg.z, cg.p, cg.q)
+
+    def wilson_solve_eo_n(self, xn: Tensor, bn: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                          check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
+        """`wilson_solve_n` with even-odd preconditioning (even extents): the same system M psi = b through its Schur
+        complement on the even sites -- split b, form bhat_e = b_e + kappa H_eo b_o, the same CGNR loop on Mhat = 1 -
+        kappa^2 H_eo H_oe from zero with the same stopping test |rhat|^2 <= tol^2 |b|^2 (|b|^2 of the full right-hand
+        side: with psi_o reconstructed, b - M psi is rhat on the even sites and zero on the odd ones, so tol means what
+        it means there), psi_o = b_o + kappa H_oe psi_e, merge.  Same arguments, same freezing, same independence of a
+        system's bits from the batch, same info keys; info['residual'] is the full |b - M psi| / |b| recomputed with one
+        `l2q_su3_wilson_apply` after the reconstruction.  b = 0 gives psi = 0.  `quark_propagator(_n)` takes it with
+        even_odd=True."""
+        k = self._wilson_checks('wilson_solve_eo', kappa, xn, bn)
+        _CG.check_args('wilson_solve_eo', tol, max_iter, check_every)
+        L = self._eo_lattice('wilson_solve_eo')
+        b, single = self._spinor_native('wilson_solve_eo', xn, bn)
+        be, bo = ops.su3_spinor_split_eo(b, L)
+        zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
+        spare = torch.zeros_like(be)
+        bb = ops.sum_parts(ops.su3_spinor_cg_update_(spare, be, bo, bo, zero)) \
+            + ops.sum_parts(ops.su3_spinor_cg_update_(spare, bo, be, be, zero))        # alpha = 0: |b_e|^2 + |b_o|^2
+        bhat = ops.su3_wilson_hop_eo_n(xn, bo, L, 0, False, antiperiodic_t, a=k, aux=be, b=1.0)
+        cg = _CG('wilson_solve_eo', bhat, single, _SchurOp(xn, k, L, antiperiodic_t, bhat), tol, max_iter, check_every, bb=bb)
+        cg.cgnr()
+        psio = ops.su3_wilson_hop_eo_n(xn, cg.x, L, 1, False, antiperiodic_t, a=k, aux=bo, b=1.0)
+        psi = ops.su3_spinor_merge_eo(cg.x, psio, L)
+        # the residual of the full system: r = b - 1 * (M psi), by the update kernel as in `_CG.info`
+        mpsi = ops.su3_wilson_apply_n(xn, psi, k, L, False, antiperiodic_t)
+        r = b.clone()
+        rr = ops.sum_parts(ops.su3_spinor_cg_update_(torch.zeros_like(b), r, mpsi, mpsi, torch.ones_like(zero)))
+        res = torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
+        return (psi[:, 0] if single else psi), {'iters': cg.iters, 'converged': ~cg.active, 'residual': res}
 
     def wilson_solve(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
                      check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
@@ -203,11 +291,25 @@ class WilsonFermions:
         psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
         return (psi[:, 0] if single else psi), info
 
+    def wilson_solve_eo(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                        check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
+        """`wilson_solve_eo_n` in the reference layout"""
+        self._wilson_checks('wilson_solve_eo', kappa, x, b)
+        self._eo_lattice('wilson_solve_eo')
+        bn, single = self._spinor_reference('wilson_solve_eo', x, b)
+        psin, info = self.wilson_solve_eo_n(self.pack(x), bn, kappa, tol, max_iter, check_every, antiperiodic_t)
+        psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
+        return (psi[:, 0] if single else psi), info
+
     def quark_propagator_n(self, xn: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
         """The point-to-all propagator from the site `source` = (t, x, y, z): the twelve unit sources (spin, colour) at
         that site solved as one nrhs = 12 batch of `wilson_solve_n`.  Returns (S, info), S[nb, 12, 12, V] native:
-        source component 3 spin + colour, then sink component, then site."""
+        source component 3 spin + colour, then sink component, then site.  even_odd=True among the keywords: by
+        `wilson_solve_eo_n`."""
         self._wilson_checks('quark_propagator', kappa, xn)
+        solve = self.wilson_solve_eo_n if solve_kwargs.pop('even_odd', False) else self.wilson_solve_n
+        if solve == self.wilson_solve_eo_n:
+            self._eo_lattice('quark_propagator')
         L = self._lattice_shape
         try:
             src = [int(c) for c in source]
@@ -220,7 +322,7 @@ class WilsonFermions:
         bn = torch.zeros((xn.shape[0], 12, 12, self.volume), dtype=torch.complex128, device=xn.device)
         j = torch.arange(12, device=xn.device)
         bn[:, j, j, s] = 1.0
-        return self.wilson_solve_n(xn, bn, kappa, **solve_kwargs)
+        return solve(xn, bn, kappa, **solve_kwargs)
 
     def quark_propagator(self, x: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
         """`quark_propagator_n` in the reference layout: S[nb, T, X, Y, Z, 4, 3, 4, 3] (sink spin, sink colour, source
@@ -234,7 +336,8 @@ class WilsonFermions:
     def _pf_checks(self, what: str, kappa, *tensors) -> float:
         for t in tensors:
             if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise ValueError(f'LatticeSU3.{what}: no autograd through the pseudofermion action; detach the fields')
+                raise ValueError(f'LatticeSU3.{what}: no autograd through the pseudofermion action or the even-odd '
+                                 f'operator; detach the fields')
         return self._wilson_checks(what, kappa, *tensors)
 
     @staticmethod
@@ -257,20 +360,89 @@ class WilsonFermions:
         Y, info): info['iters'], info['converged'], info['residual'] (|phi - M^H M X| / |phi| recomputed) and
         info['action'] (|Y|^2 from the fused norm of the last apply), each [nb, npf].  Workspace: seven spinor fields."""
         k = self._pf_checks('wilson_solve_normal', kappa, xn, phin)
-        cg = _CG(self, 'wilson_solve_normal', xn, phin, k, tol, max_iter, check_every, antiperiodic_t)
-        X, r, q, z, apply = cg.x, cg.r, cg.q, cg.z, cg.apply
-        p, rr = cg.b.clone(), cg.bb
-        for active in cg.iterations(lambda: rr):                           # |r|^2 is carried from every update
-            qq = apply(p, q, False)
-            apply(q, z, True, norm=False)
-            rn = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, p, z, ratio(active, rr, qq), cg.rpart))
-            ops.su3_spinor_xpay_(p, r, ratio(active, rn, rr))
-            rr = rn
-        Y = torch.empty_like(X)
-        action = apply(X, Y, False)
-        apply(Y, z, True, norm=False)
-        info = {**cg.info(q, p, z), 'action': action}
+        _CG.check_args('wilson_solve_normal', tol, max_iter, check_every)
+        b, single = self._spinor_native('wilson_solve_normal', xn, phin)
+        op = _WilsonOp(xn, k, self._lattice_shape, antiperiodic_t, b)
+        return self._solve_normal(_CG('wilson_solve_normal', b, single, op, tol, max_iter, check_every))
+
+    @staticmethod
+    def _solve_normal(cg: _CG) -> tuple[Tensor, Tensor, dict]:
+        Y, action = cg.normal()
+        X = cg.x
+        info = {**cg.info(cg.q, cg.p, cg.z), 'action': action}
         return (X[:, 0], Y[:, 0], info) if cg.single else (X, Y, info)
+
+    # ------------------------------------------------------------ even-odd preconditioning: the Schur complement
+    def _eo_lattice(self, what: str):
+        """the lattice, or ValueError naming it if an extent is odd"""
+        return ops._even_lattice(f'LatticeSU3.{what}', self._lattice_shape)
+
+    def _half_native(self, what: str, xn: Tensor, fn: Tensor) -> tuple[Tensor, bool]:
+        """a half field as [nb, nrhs, 12, V/2] and whether it came without the nrhs axis"""
+        single = fn.dim() == 3
+        p = fn[:, None] if single else fn
+        if p.dim() != 4 or tuple(p.shape[2:]) != (12, self.volume // 2) or p.shape[0] != xn.shape[0]:
+            raise ValueError(f'LatticeSU3.{what}: need a native half field [nb, nrhs, 12, V/2] or [nb, 12, V/2] with '
+                             f'nb = {xn.shape[0]}, V/2 = {self.volume // 2}, got {list(fn.shape)}')
+        return p.to(torch.complex128).contiguous(), single
+
+    def _half_reference(self, what: str, x: Tensor, psi: Tensor) -> tuple[Tensor, bool]:
+        """the even half field of a full-shape field in the reference layout: its odd sites are not read"""
+        pn, single = self._spinor_reference(what, x, psi)
+        return ops.su3_spinor_split_eo(pn, self._lattice_shape)[0].contiguous(), single
+
+    def _half_to_reference(self, he: Tensor) -> Tensor:
+        """an even half field [nb, nrhs, 12, V/2] as a full-shape field in the reference layout, zero on the odd sites"""
+        L = self._lattice_shape
+        return ops.su3_spinor_unpack(ops.su3_spinor_merge_eo(he, torch.zeros_like(he), L), L)
+
+    def wilson_schur_n(self, xn: Tensor, psi_e: Tensor, kappa: float, dagger: bool = False,
+                       antiperiodic_t: bool = True) -> Tensor:
+        """Mhat psi_e = psi_e - kappa^2 H_eo H_oe psi_e (dagger: Mhat^H psi_e) of an even half field [nb, nrhs, 12,
+        V/2] (or [nb, 12, V/2]): the Schur complement of M = 1 - kappa H on the even sites, det M = det Mhat.  Two
+        `l2q_su3_wilson_hop_eo`; a new field.  Even extents only."""
+        k = self._pf_checks('wilson_schur', kappa, xn, psi_e)
+        L = self._eo_lattice('wilson_schur')
+        p, single = self._half_native('wilson_schur', xn, psi_e)
+        out = torch.empty_like(p)
+        _SchurOp(xn, k, L, antiperiodic_t, p).apply(p, out, dagger, norm=False)
+        return out[:, 0] if single else out
+
+    def wilson_schur(self, x: Tensor, psi: Tensor, kappa: float, dagger: bool = False,
+                     antiperiodic_t: bool = True) -> Tensor:
+        """`wilson_schur_n` in the reference layout: psi is a full-shape field of which only the even sites are read;
+        the odd sites of the result are zero."""
+        self._pf_checks('wilson_schur', kappa, x, psi)
+        self._eo_lattice('wilson_schur')
+        pe, single = self._half_reference('wilson_schur', x, psi)
+        out = self._half_to_reference(self.wilson_schur_n(self.pack(x), pe, kappa, dagger, antiperiodic_t))
+        return out[:, 0] if single else out
+
+    def wilson_solve_schur_normal_n(self, xn: Tensor, phi_e: Tensor, kappa: float, tol: float = 1e-10,
+                                    max_iter: int = 1000, check_every: int = 10,
+                                    antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
+        """Mhat^H Mhat X_e = phi_e for every system of the even half field phi_e at once, and Y_e = Mhat X_e:
+        `wilson_solve_normal_n` on the Schur complement, the same loop on half fields.  Returns (X_e, Y_e, info), info
+        as there with info['action'] = |Y_e|^2."""
+        k = self._pf_checks('wilson_solve_schur_normal', kappa, xn, phi_e)
+        _CG.check_args('wilson_solve_schur_normal', tol, max_iter, check_every)
+        L = self._eo_lattice('wilson_solve_schur_normal')
+        b, single = self._half_native('wilson_solve_schur_normal', xn, phi_e)
+        op = _SchurOp(xn, k, L, antiperiodic_t, b)
+        return self._solve_normal(_CG('wilson_solve_schur_normal', b, single, op, tol, max_iter, check_every))
+
+    def _schur_force_fields_n(self, xn: Tensor, phi_e: Tensor, k: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """The full fields (X, Y) whose `l2q_su3_wilson_force` is the force of the even-odd action phi_e^H (Mhat^H
+        Mhat)^-1 phi_e: X_e, Y_e from `wilson_solve_schur_normal_n`, X_o = kappa H_oe X_e, Y_o = kappa (H^H)_oe Y_e.
+        Exact: dS_f = 2 kappa Re[Y_e^H dH_eo X_o + Y_o^H dH_oe X_e], the full-lattice expression."""
+        L = self._eo_lattice('pseudofermion_force')
+        ap = solve_kwargs.get('antiperiodic_t', True)
+        Xe, Ye, info = self.wilson_solve_schur_normal_n(xn, phi_e, k, **solve_kwargs)
+        if Xe.dim() == 3:
+            Xe, Ye = Xe[:, None].contiguous(), Ye[:, None].contiguous()
+        Xo = ops.su3_wilson_hop_eo_n(xn, Xe, L, 1, False, ap, a=k)
+        Yo = ops.su3_wilson_hop_eo_n(xn, Ye, L, 1, True, ap, a=k)
+        return ops.su3_spinor_merge_eo(Xe, Xo, L), ops.su3_spinor_merge_eo(Ye, Yo, L), info
 
     def wilson_solve_normal(self, x: Tensor, phi: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
                             check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, Tensor, dict]:
@@ -288,12 +460,29 @@ class WilsonFermions:
         component; `torch.randn((nb, npf, 12, V, 2), dtype=float64)` on the device, or on the host with a CPU
         generator: the same numbers on any machine), phi = M^H eta, which is distributed as exp(-S_f).  Returns (phi
         [nb, npf, 12, V], S0 [nb]): S0 = |eta|^2 is S_f(phi) on these links without a solve."""
-        k = self._pf_checks('pseudofermion_refresh', kappa, xn)
+        return self._pf_refresh_n('pseudofermion_refresh', xn, kappa, npf, generator, antiperiodic_t, False)
+
+    def pseudofermion_refresh_eo_n(self, xn: Tensor, kappa: float, npf: int = 1,
+                                   generator: Optional[torch.Generator] = None,
+                                   antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
+        """The heatbath of the even-odd pseudofermion action phi_e^H (Mhat^H Mhat)^-1 phi_e, which puts det(Mhat^H Mhat) =
+        det(M^H M) into the ensemble: eta_e drawn by the rule of `pseudofermion_refresh_n` with the half shape (nb, npf,
+        12, V/2, 2), phi_e = Mhat^H eta_e.  Returns (phi_e [nb, npf, 12, V/2], S0 [nb]), S0 = |eta_e|^2."""
+        return self._pf_refresh_n('pseudofermion_refresh_eo', xn, kappa, npf, generator, antiperiodic_t, True)
+
+    def _pf_refresh_n(self, what: str, xn: Tensor, kappa, npf, generator, antiperiodic_t, even_odd: bool):
+        k = self._pf_checks(what, kappa, xn)
         if isinstance(npf, bool) or not isinstance(npf, (int, np.integer)) or int(npf) < 1:
-            raise ValueError(f'LatticeSU3.pseudofermion_refresh: npf must be an integer >= 1, got {npf!r}')
-        shape = (xn.shape[0], int(npf), 12, self.volume, 2)
+            raise ValueError(f'LatticeSU3.{what}: npf must be an integer >= 1, got {npf!r}')
+        if even_odd:
+            L = self._eo_lattice(what)
+        shape = (xn.shape[0], int(npf), 12, self.volume // 2 if even_odd else self.volume, 2)
         eta = torch.view_as_complex(draw(shape, generator, xn.device) * float(np.sqrt(0.5))).contiguous()
-        phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
+        if even_odd:
+            phi = torch.empty_like(eta)
+            _SchurOp(xn, k, L, antiperiodic_t, eta).apply(eta, phi, True, norm=False)
+        else:
+            phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
         zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
         part = ops.su3_spinor_cg_update_(torch.zeros_like(eta), eta, phi, phi, zero)     # alpha = 0: |eta|^2
         return phi, self._sum_fields(ops.sum_parts(part))
@@ -305,34 +494,68 @@ class WilsonFermions:
         phi, s0 = self.pseudofermion_refresh_n(self.pack(x), kappa, npf, generator, antiperiodic_t)
         return ops.su3_spinor_unpack(phi, self._lattice_shape), s0
 
+    def pseudofermion_refresh_eo(self, x: Tensor, kappa: float, npf: int = 1,
+                                 generator: Optional[torch.Generator] = None,
+                                 antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
+        """`pseudofermion_refresh_eo_n` in the reference layout: the full shape phi[nb, npf, T, X, Y, Z, 4, 3], phi_e on
+        the even sites and zero on the odd ones"""
+        self._pf_checks('pseudofermion_refresh_eo', kappa, x)
+        self._eo_lattice('pseudofermion_refresh_eo')
+        phi, s0 = self.pseudofermion_refresh_eo_n(self.pack(x), kappa, npf, generator, antiperiodic_t)
+        return self._half_to_reference(phi), s0
+
     def pseudofermion_action_n(self, xn: Tensor, phin: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
         """S_f = sum_r phi_r^H (M^H M)^-1 phi_r = sum_r |Y_r|^2 per chain, by one `wilson_solve_normal_n` (whose
-        keywords these are): (S_f [nb], info)."""
+        keywords these are): (S_f [nb], info).  One more keyword, even_odd (default False): with True phin is the half
+        field phi_e and S_f = sum_r |Y_e,r|^2 by one `wilson_solve_schur_normal_n`."""
         self._pf_checks('pseudofermion_action', kappa, xn, phin)
-        b, _ = self._spinor_native('pseudofermion_action', xn, phin)
-        _, _, info = self.wilson_solve_normal_n(xn, b, kappa, **solve_kwargs)
+        if solve_kwargs.pop('even_odd', False):
+            self._eo_lattice('pseudofermion_action')
+            b, _ = self._half_native('pseudofermion_action', xn, phin)
+            _, _, info = self.wilson_solve_schur_normal_n(xn, b, kappa, **solve_kwargs)
+        else:
+            b, _ = self._spinor_native('pseudofermion_action', xn, phin)
+            _, _, info = self.wilson_solve_normal_n(xn, b, kappa, **solve_kwargs)
         return self._sum_fields(info['action']), info
 
     def pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
-        """`pseudofermion_action_n` in the reference layout"""
+        """`pseudofermion_action_n` in the reference layout; with even_odd only the even sites of phi are read"""
         self._pf_checks('pseudofermion_action', kappa, x, phi)
-        pn, _ = self._spinor_reference('pseudofermion_action', x, phi)
-        return self.pseudofermion_action_n(self.pack(x), pn, kappa, **solve_kwargs)
+        even_odd = bool(solve_kwargs.pop('even_odd', False))
+        if even_odd:
+            self._eo_lattice('pseudofermion_action')
+            pn, _ = self._half_reference('pseudofermion_action', x, phi)
+        else:
+            pn, _ = self._spinor_reference('pseudofermion_action', x, phi)
+        return self.pseudofermion_action_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
 
     def pseudofermion_force_n(self, xn: Tensor, phin: Tensor, kappa: float,
                               **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
         """The force of S_f on the links, in the convention of `grad_action_n` (dS_f/dt = sum <p, F> under dU/dt =
         p U; the kick is p <- p - eps F): one `wilson_solve_normal_n` and one `l2q_su3_wilson_force` (see l2q.h).
-        Returns (F [nb, 4, 9, V], S_f [nb], info)."""
+        Returns (F [nb, 4, 9, V], S_f [nb], info).  even_odd=True among the keywords: phin is the half field phi_e and
+        the force is that of phi_e^H (Mhat^H Mhat)^-1 phi_e: one `wilson_solve_schur_normal_n`, the odd halves X_o = kappa H_oe X_e and
+        Y_o = kappa (H^H)_oe Y_e by one hop each, and the same `l2q_su3_wilson_force` on the merged fields (exact)."""
         k = self._pf_checks('pseudofermion_force', kappa, xn, phin)
-        b, _ = self._spinor_native('pseudofermion_force', xn, phin)
-        X, Y, info = self.wilson_solve_normal_n(xn, b, k, **solve_kwargs)
+        if solve_kwargs.pop('even_odd', False):
+            self._eo_lattice('pseudofermion_force')
+            b, _ = self._half_native('pseudofermion_force', xn, phin)
+            X, Y, info = self._schur_force_fields_n(xn, b, k, **solve_kwargs)
+        else:
+            b, _ = self._spinor_native('pseudofermion_force', xn, phin)
+            X, Y, info = self.wilson_solve_normal_n(xn, b, k, **solve_kwargs)
         F = ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True))
         return F, self._sum_fields(info['action']), info
 
     def pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
-        """`pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]"""
+        """`pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]; with even_odd only the even
+        sites of phi are read"""
         self._pf_checks('pseudofermion_force', kappa, x, phi)
-        pn, _ = self._spinor_reference('pseudofermion_force', x, phi)
-        F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, **solve_kwargs)
+        even_odd = bool(solve_kwargs.pop('even_odd', False))
+        if even_odd:
+            self._eo_lattice('pseudofermion_force')
+            pn, _ = self._half_reference('pseudofermion_force', x, phi)
+        else:
+            pn, _ = self._spinor_reference('pseudofermion_force', x, phi)
+        F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
         return self.unpack(F), s, info

@@ -86,6 +86,7 @@ SIGNATURES = {
     'l2q_su3_spinor_cg_update': (I, [P, P, P, P, P, P, L, L, P]),
     'l2q_su3_spinor_xpay': (I, [P, P, P, L, L, P]),
     'l2q_su3_wilson_force': (I, [P, P, P, P, P, D, D, I, I, I, I, I, I, I, P]),
+    'l2q_su3_wilson_hop_eo': (I, [P, P, P, P, P, D, D, I, I, I, I, I, I, I, I, P]),
     'l2q_v_update': (I, [P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_v_update_to': (I, [P, P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_accept': (I, [P, P, P, P, P, P, I, I, P]),

@@ -9,7 +9,12 @@
   --torch       the same operator composed from torch `roll` / `einsum` on the GPU at --torch-nb chains: the only
                 "before" there is;
   --propagator  one 12-column `quark_propagator` at kappa = 0.10 on --physics-nb chains thermalised with `heatbath` at
-                beta = 6 (nover = 3), with the pion correlator and its effective mass."""
+                beta = 6 (nover = 3), with the pion correlator and its effective mass;
+  --eo          even-odd preconditioning (csrc/su3_wilson_eo.hip, profiles/su3_wilson_eo.md) at each --nrhs: the half-lattice
+                hop `l2q_su3_wilson_hop_eo` beside the full apply; one CGNR iteration on M beside one on Mhat (four hops,
+                the update and the xpay on half fields); and the time to solution of `wilson_solve_n` / `wilson_solve_eo_n`
+                and `wilson_solve_normal_n` / `wilson_solve_schur_normal_n` at --eo-kappa, --eo-tol on --nb chains
+                thermalised with --eo-therm heatbath sweeps at beta = 6, Gaussian right-hand sides."""
 import argparse
 import os
 import statistics
@@ -102,6 +107,97 @@ def kernels(nb, L, nrhs_list, iters, repeats):
         del psi, out, q, z, x, r, p
 
 
+def even_odd(nb, L, nrhs_list, iters, repeats, therm, kappa, tol):
+    V = L[0] * L[1] * L[2] * L[3]
+    Vh = V // 2
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    lat = LatticeSU3(nb, L)
+    xn = lat.pack(lat.heatbath(lat.random().to(dev), 6.0, nsweeps=therm, nover=3)[0])
+    print(f'{L} x {nb} chains, beta 6.0 after {therm} heatbath sweeps (nover 3): plaquette '
+          f'{float(lat.plaq_sums_n(xn)[:, 0].mean()) / (18.0 * V):.5f}; kappa {kappa}, tol {tol}')
+    for nrhs in nrhs_list:
+        psi = torch.randn((nb, nrhs, 12, V), dtype=torch.complex128, device=dev)
+        out, q, z, x = (torch.empty_like(psi) for _ in range(4))
+        r, p = torch.randn_like(psi), torch.randn_like(psi)
+        part = torch.empty((nb, nrhs, ops.su3_wilson_norm_parts(L)), dtype=torch.float64, device=dev)
+        rpart = torch.empty_like(part)
+        coef = torch.full((nb, nrhs), 1e-3, dtype=torch.float64, device=dev)
+        x.zero_()
+        sites, hsites = nb * nrhs * V, nb * nrhs * Vh
+        print(f'lattice {L} x {nb} chains x {nrhs} right-hand sides, {iters} calls per window, {repeats} windows')
+        # the kernels: a full apply is V sites, a hop V/2; bytes per (system, site of the launch), links once per chain
+        ta = show('full apply + fused norm', windows(lambda: ops.su3_wilson_apply_n(xn, psi, kappa, L, out=out, norm=part),
+                                                     iters, repeats), 2 * SPINOR + LINKS / nrhs, sites, 2 * SPINOR + LINKS)
+        he, ho, hq, hz, hx = (torch.empty((nb, nrhs, 12, Vh), dtype=torch.complex128, device=dev) for _ in range(5))
+        hr, hp = torch.randn_like(he), torch.randn_like(he)
+        he.copy_(hr)
+        hx.zero_()
+        hpart = torch.empty((nb, nrhs, -(-Vh // 256)), dtype=torch.float64, device=dev)
+        hrpart = torch.empty_like(hpart)
+        t1 = show('hop (a = 1, no aux), odd sites', windows(lambda: ops.su3_wilson_hop_eo_n(xn, he, L, 1, out=ho), iters, repeats),
+                  2 * SPINOR + 2 * LINKS / nrhs, hsites, 2 * SPINOR + 2 * LINKS)
+        t2 = show('hop (aux, fused norm), even sites',
+                  windows(lambda: ops.su3_wilson_hop_eo_n(xn, ho, L, 0, a=-kappa * kappa, aux=he, b=1.0, out=hq, norm=hpart),
+                          iters, repeats), 3 * SPINOR + 2 * LINKS / nrhs, hsites, 3 * SPINOR + 2 * LINKS)
+        print(f'  Mhat = two hops {(t1 + t2) * 1e3:.3f} ms against M = one full apply {ta * 1e3:.3f} ms: ratio '
+              f'{(t1 + t2) / ta:.2f}')
+        tu = show('cg_update, full fields', windows(lambda: ops.su3_spinor_cg_update_(x, r, p, q, coef, rpart), iters, repeats),
+                  6 * SPINOR, sites)
+        tuh = show('cg_update, half fields', windows(lambda: ops.su3_spinor_cg_update_(hx, hr, hp, hq, coef, hrpart),
+                                                     iters, repeats), 6 * SPINOR, hsites)
+        tx = show('xpay, full fields', windows(lambda: ops.su3_spinor_xpay_(p, z, coef), iters, repeats), 3 * SPINOR, sites)
+        txh = show('xpay, half fields', windows(lambda: ops.su3_spinor_xpay_(hp, hz, coef), iters, repeats), 3 * SPINOR, hsites)
+
+        def iteration():
+            ops.su3_wilson_apply_n(xn, p, kappa, L, False, out=q, norm=part)
+            qq = ops.sum_parts(part)
+            ops.su3_spinor_cg_update_(x, r, p, q, (coef / (qq + 1.0)).contiguous(), rpart)
+            ops.su3_wilson_apply_n(xn, r, kappa, L, True, out=z, norm=part)
+            zn = ops.sum_parts(part)
+            ops.su3_spinor_xpay_(p, z, (coef / (zn + 1.0)).contiguous())
+
+        def schur(src, dst, dagger):
+            ops.su3_wilson_hop_eo_n(xn, src, L, 1, dagger, out=ho)
+            ops.su3_wilson_hop_eo_n(xn, ho, L, 0, dagger, a=-kappa * kappa, aux=src, b=1.0, out=dst, norm=hpart)
+            return ops.sum_parts(hpart)
+
+        def iteration_eo():
+            qq = schur(hp, hq, False)
+            ops.su3_spinor_cg_update_(hx, hr, hp, hq, (coef / (qq + 1.0)).contiguous(), hrpart)
+            zn = schur(hr, hz, True)
+            ops.su3_spinor_xpay_(hp, hz, (coef / (zn + 1.0)).contiguous())
+
+        ti = show('one CGNR iteration on M, as launched', windows(iteration, iters, repeats))
+        te = show('one CGNR iteration on Mhat, as launched', windows(iteration_eo, iters, repeats))
+        print(f'  launches by themselves: full 2 x {ta * 1e3:.3f} + {tu * 1e3:.3f} + {tx * 1e3:.3f} = '
+              f'{(2 * ta + tu + tx) * 1e3:.3f} ms; even-odd 2 x {(t1 + t2) * 1e3:.3f} + {tuh * 1e3:.3f} + {txh * 1e3:.3f} = '
+              f'{(2 * (t1 + t2) + tuh + txh) * 1e3:.3f} ms; iteration ratio even-odd / full {te / ti:.2f}')
+        del out, q, z, x, r, p, he, ho, hq, hz, hx, hr, hp
+        # time to solution: the same right-hand sides through both paths
+        kw = dict(tol=tol, max_iter=2000)
+
+        def timed(name, fn):
+            fn()                                                    # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            info = res[-1]
+            print(f'{name:44s} {dt * 1e3:9.1f} ms  iterations {int(info["iters"].min())} .. {int(info["iters"].max())}, '
+                  f'residual <= {float(info["residual"].max()):.3g}, all converged {bool(info["converged"].all())}')
+            return dt
+        tf = timed('wilson_solve_n', lambda: lat.wilson_solve_n(xn, psi, kappa, **kw))
+        to = timed('wilson_solve_eo_n', lambda: lat.wilson_solve_eo_n(xn, psi, kappa, **kw))
+        print(f'  time to solution, even-odd / full: {to / tf:.2f}')
+        pe = ops.su3_spinor_split_eo(psi, L)[0].contiguous()
+        tf = timed('wilson_solve_normal_n', lambda: lat.wilson_solve_normal_n(xn, psi, kappa, **kw))
+        to = timed('wilson_solve_schur_normal_n', lambda: lat.wilson_solve_schur_normal_n(xn, pe, kappa, **kw))
+        print(f'  time to solution, even-odd / full: {to / tf:.2f}')
+        del psi, pe
+
+
 def torch_apply(x, psi, kappa, gam):
     """M psi from roll / einsum on reference-layout tensors (antiperiodic in t)"""
     eye = torch.eye(4, dtype=psi.dtype, device=psi.device)
@@ -172,6 +268,10 @@ def main():
     ap.add_argument('--physics-nb', type=int, default=16)
     ap.add_argument('--therm', type=int, default=50)
     ap.add_argument('--kappa', type=float, default=0.10)
+    ap.add_argument('--eo', action='store_true')
+    ap.add_argument('--eo-kappa', type=float, default=0.12)
+    ap.add_argument('--eo-tol', type=float, default=1e-10)
+    ap.add_argument('--eo-therm', type=int, default=10)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
@@ -179,6 +279,8 @@ def main():
         kernels(args.nb, args.L, args.nrhs, args.iters, args.repeats)
     if args.torch:
         torch_compose(args.torch_nb, args.L, args.nrhs, max(2, args.iters // 4), args.repeats)
+    if args.eo:
+        even_odd(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol)
     if args.propagator:
         propagator(args.physics_nb, args.L, args.therm, args.kappa)
 

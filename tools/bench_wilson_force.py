@@ -9,7 +9,9 @@ for profiles/su3_wilson_force.md, SU(3) 8^4, complex128:
   --trajectory  on --physics-nb chains thermalised with `heatbath` at beta = 6 (nover = 3, what `Trainer.thermalize`
                 runs): one leapfrog of `WilsonHMC` stage by stage (each stage between device synchronisations: solves,
                 fermion force, gauge kick, link update), then --ntraj trajectories: acceptance, CG iterations per solve,
-                <exp(-dH)> with its standard error."""
+                <exp(-dH)> with its standard error; with --even-odd the same split and trajectories again with
+                `WilsonHMCEvenOdd` on the same thermalised links (profiles/su3_wilson_eo.md): its 'solves' stage is the
+                solve on the Schur complement plus the two hops and merges that complete X and Y."""
 import argparse
 import os
 import statistics
@@ -21,7 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'l2hmc-qcd_amd'))
 from l2hmc import _ops as ops  # noqa: E402
-from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC  # noqa: E402
+from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC, WilsonHMCEvenOdd  # noqa: E402
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3  # noqa: E402
 
 HBM_PEAK = 8.0e12       # B/s, the spec figure that DESIGN.md's fractions are taken against
@@ -81,14 +83,15 @@ def kernels(nb, L, npf_list, iters, repeats):
          3 * LINKS, sites)
 
 
-def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj):
+def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=False):
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
     lat = LatticeSU3(nb, L)
     x = lat.heatbath(lat.random().to(dev), beta, nsweeps=therm, nover=3)[0]
     print(f'{L} x {nb} chains, beta {beta} after {therm} heatbath sweeps (nover 3): plaquette '
-          f'{float(lat.plaqs(x).mean()):.5f}; kappa {kappa}, npf {npf}, eps {eps}, nleapfrog {nleapfrog}')
-    hmc = WilsonHMC(lat, beta, kappa, eps, nleapfrog, npf=npf)
+          f'{float(lat.plaqs(x).mean()):.5f}; kappa {kappa}, npf {npf}, eps {eps}, nleapfrog {nleapfrog}, '
+          f'even_odd {even_odd}')
+    hmc = (WilsonHMCEvenOdd if even_odd else WilsonHMC)(lat, beta, kappa, eps, nleapfrog, npf=npf)
     xn = lat.pack(x)
     hmc.trajectory_n(xn)                                         # warm-up
     # one leapfrog stage by stage
@@ -105,12 +108,13 @@ def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj):
 
     def kick(xn, vn, step):
         timed('gauge kick', lambda: ops.su3_force_kick_n(xn, beta, -step, vn, L))
-        X, Y, info = timed('solves', lambda: lat.wilson_solve_normal_n(xn, phin, kappa, **hmc._solve_kw(hmc.tol_md)))
+        solve = lat._schur_force_fields_n if even_odd else lat.wilson_solve_normal_n
+        X, Y, info = timed('solves', lambda: solve(xn, phin, kappa, **hmc._solve_kw(hmc.tol_md)))
         timed('fermion force', lambda: ops.su3_wilson_force_n(xn, X, Y, kappa, L, True, coef=-step, f_in=vn, out=vn))
         iters.append(info['iters'])
 
     vn = ops.su3_assemble_tah_n(torch.randn((8, nb, 4, lat.volume), dtype=torch.float64, device=dev))
-    phin, _ = lat.pseudofermion_refresh_n(xn, kappa, npf)
+    phin, _ = (lat.pseudofermion_refresh_eo_n if even_odd else lat.pseudofermion_refresh_n)(xn, kappa, npf)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     kick(xn, vn, 0.5 * eps)
@@ -157,14 +161,16 @@ def main():
     ap.add_argument('--eps', type=float, default=0.02)
     ap.add_argument('--nleapfrog', type=int, default=25)
     ap.add_argument('--ntraj', type=int, default=10)
+    ap.add_argument('--even-odd', action='store_true')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
     if args.kernels:
         kernels(args.nb, args.L, args.npf, args.iters, args.repeats)
     if args.trajectory:
-        trajectory(args.physics_nb, args.L, args.therm, args.beta, args.kappa, args.eps, args.nleapfrog, args.npf[0],
-                   args.ntraj)
+        for eo in (False, True) if args.even_odd else (False,):
+            trajectory(args.physics_nb, args.L, args.therm, args.beta, args.kappa, args.eps, args.nleapfrog, args.npf[0],
+                       args.ntraj, eo)
 
 
 if __name__ == '__main__':
