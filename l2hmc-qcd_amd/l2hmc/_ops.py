@@ -633,6 +633,19 @@ def _spinor_check(what: str, name: str, t: torch.Tensor, shape) -> None:
         raise ValueError(f'{what}: {name} must be contiguous complex128 {list(shape)}, got {t.dtype} {list(t.shape)}')
 
 
+def _norm_part(what: str, norm, nb: int, nrhs: int, parts, device) -> Optional[torch.Tensor]:
+    """the `norm` argument of an operator entry as its partial-sum tensor [nb, nrhs, parts()]: None for False (parts is
+    not asked then), a new tensor for True, or the tensor given, checked"""
+    if not isinstance(norm, torch.Tensor) and not norm:
+        return None
+    want = [nb, nrhs, parts()]
+    if not isinstance(norm, torch.Tensor):
+        return torch.empty(want, dtype=torch.float64, device=device)
+    if norm.dtype != torch.float64 or list(norm.shape) != want or not norm.is_contiguous():
+        raise ValueError(f'{what}: norm must be contiguous float64 {want}, got {list(norm.shape)}')
+    return norm
+
+
 def su3_wilson_apply_n(xn: torch.Tensor, psin: torch.Tensor, kappa: float, lat: Sequence[int], dagger: bool = False,
                        antiperiodic_t: bool = True, out: Optional[torch.Tensor] = None, norm: bool = False):
     """M psi (dagger: M^H psi) of the native spinor field psin[nb, nrhs, 12, V] on the native links xn (see l2q.h).  Out
@@ -647,14 +660,7 @@ def su3_wilson_apply_n(xn: torch.Tensor, psin: torch.Tensor, kappa: float, lat: 
     else:
         _spinor_check('su3_wilson_apply_n', 'out', out, psin.shape)
     nb, nrhs = psin.shape[:2]
-    part = None
-    if isinstance(norm, torch.Tensor):
-        part = norm
-        want = (nb, nrhs, su3_wilson_norm_parts(lat))
-        if part.dtype != torch.float64 or tuple(part.shape) != want or not part.is_contiguous():
-            raise ValueError(f'su3_wilson_apply_n: norm must be contiguous float64 {list(want)}, got {list(part.shape)}')
-    elif norm:
-        part = torch.empty((nb, nrhs, su3_wilson_norm_parts(lat)), dtype=torch.float64, device=psin.device)
+    part = _norm_part('su3_wilson_apply_n', norm, nb, nrhs, lambda: su3_wilson_norm_parts(lat), psin.device)
     N.call('l2q_su3_wilson_apply', xn, psin, out, part, float(kappa), int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1),
            nb, nrhs, T, X, Y, Z)
     return out if part is None else (out, part)
@@ -780,15 +786,7 @@ def su3_wilson_hop_eo_n(xn: torch.Tensor, src: torch.Tensor, lat: Sequence[int],
     else:
         _spinor_check('su3_wilson_hop_eo_n', 'out', out, src.shape)
     nb, nrhs = src.shape[:2]
-    parts = -(-Vh // 256)
-    part = None
-    if isinstance(norm, torch.Tensor):
-        part = norm
-        if part.dtype != torch.float64 or tuple(part.shape) != (nb, nrhs, parts) or not part.is_contiguous():
-            raise ValueError(f'su3_wilson_hop_eo_n: norm must be contiguous float64 {[nb, nrhs, parts]}, got '
-                             f'{list(part.shape)}')
-    elif norm:
-        part = torch.empty((nb, nrhs, parts), dtype=torch.float64, device=src.device)
+    part = _norm_part('su3_wilson_hop_eo_n', norm, nb, nrhs, lambda: -(-Vh // 256), src.device)
     N.call('l2q_su3_wilson_hop_eo', xn, src, aux, out, part, float(a), float(b),
            int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1), int(parity), nb, nrhs, T, X, Y, Z)
     return out if part is None else (out, part)

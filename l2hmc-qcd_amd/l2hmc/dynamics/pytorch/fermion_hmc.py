@@ -58,10 +58,8 @@ class WilsonHMC:
             ops.su3_force_kick_n(xn, self.beta, -step, vn, L)
         else:
             ops.axpy_(vn, lat.grad_action_n(xn, self.beta), -step)
-        if self.even_odd:                    # the full fields whose force is the even-odd one
-            X, Y, info = lat._schur_force_fields_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
-        else:
-            X, Y, info = lat.wilson_solve_normal_n(xn, phin, self.kappa, **self._solve_kw(self.tol_md))
+        X, Y, info = lat._force_fields_n('pseudofermion_force', xn, phin, self.kappa, self.even_odd,
+                                         **self._solve_kw(self.tol_md))
         ops.su3_wilson_force_n(xn, X, Y, self.kappa, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
         infos.append(info)
 

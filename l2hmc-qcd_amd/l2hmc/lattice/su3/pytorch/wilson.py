@@ -52,6 +52,19 @@ def ratio(live: Tensor, num: Tensor, den: Tensor) -> Tensor:
     return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
 
 
+def _norm2(f: Tensor, other: Tensor, spare: Tensor, zero: Tensor, part: Optional[Tensor] = None) -> Tensor:
+    """|f|^2 per system [nb, nrhs] by the update kernel at alpha = 0 (`zero`): it leaves spare (its x) and f (its r)
+    as they are and |f|^2 in its partial sums; `other` is the p and q it reads"""
+    return ops.sum_parts(ops.su3_spinor_cg_update_(spare, f, other, other, zero, part))
+
+
+def _residual(r: Tensor, spare: Tensor, p: Tensor, ax: Tensor, bb: Tensor, part: Optional[Tensor] = None) -> Tensor:
+    """the recomputed residual |b - A x| / sqrt(bb) per system, 0 where bb = 0: r holds b and becomes r - 1 * ax by the
+    update kernel, spare and p serving as the update's other pair"""
+    rr = ops.sum_parts(ops.su3_spinor_cg_update_(spare, r, p, ax, torch.ones_like(bb), part))
+    return torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
+
+
 class _WilsonOp:
     """M on full fields [nb, nrhs, 12, V] as the operator of a `_CG`: apply(src, dst, dagger, norm) writes dst = M src
     (dagger: M^H src) and, with norm, returns the fused |dst|^2 [nb, nrhs]; `sites` is the site count of its fields."""
@@ -107,7 +120,7 @@ class _CG:
         self.x, self.r, self.q, self.z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
         self.rpart = torch.empty((*b.shape[:2], -(-op.sites // 256)), dtype=torch.float64, device=b.device)
         self.zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
-        self.bb0 = ops.sum_parts(ops.su3_spinor_cg_update_(self.x, self.r, b, b, self.zero, self.rpart))   # alpha = 0: |b|^2
+        self.bb0 = _norm2(self.r, b, self.x, self.zero, self.rpart)                                       # |b|^2
         self.bb = self.bb0 if bb is None else bb
 
     def cgnr(self) -> None:
@@ -153,12 +166,14 @@ class _CG:
             self.iters = torch.where(now, it, self.iters)
             self.active = self.active & ~now
 
-    def info(self, spare: Tensor, p: Tensor, ax: Tensor) -> dict:
+    def residual(self, spare: Tensor, p: Tensor, ax: Tensor) -> Tensor:
         """after the loop: the residual recomputed as r = b - 1 * ax from ax = A x in a scratch field, spare and p
-        serving as the update's other pair; never raises on non-convergence"""
+        serving as the update's other pair"""
         self.r.copy_(self.b)
-        rr = ops.sum_parts(ops.su3_spinor_cg_update_(spare, self.r, p, ax, torch.ones_like(self.zero), self.rpart))
-        res = torch.sqrt(rr / torch.where(self.bb > 0, self.bb, torch.ones_like(self.bb)))
+        return _residual(self.r, spare, p, ax, self.bb, self.rpart)
+
+    def info(self, res: Tensor) -> dict:
+        """the info every solver returns, `res` its recomputed residual; never raises on non-convergence"""
         return {'iters': self.iters, 'converged': ~self.active, 'residual': res}
 
 
@@ -191,13 +206,14 @@ class WilsonFermions:
             raise ValueError(f'LatticeSU3.{what}: kappa must be a finite number, got {kappa!r}')
         return k
 
-    def _spinor_native(self, what: str, xn: Tensor, psin: Tensor) -> tuple[Tensor, bool]:
-        """psin as [nb, nrhs, 12, V] and whether it came without the nrhs axis"""
+    def _spinor_native(self, what: str, xn: Tensor, psin: Tensor, half: bool = False) -> tuple[Tensor, bool]:
+        """psin as [nb, nrhs, 12, V] (half: a half field, V/2 sites) and whether it came without the nrhs axis"""
+        sites, kind, v = (self.volume // 2, 'half', 'V/2') if half else (self.volume, 'spinor', 'V')
         single = psin.dim() == 3
         p = psin[:, None] if single else psin
-        if p.dim() != 4 or tuple(p.shape[2:]) != (12, self.volume) or p.shape[0] != xn.shape[0]:
-            raise ValueError(f'LatticeSU3.{what}: need a native spinor field [nb, nrhs, 12, V] or [nb, 12, V] with '
-                             f'nb = {xn.shape[0]}, V = {self.volume}, got {list(psin.shape)}')
+        if p.dim() != 4 or tuple(p.shape[2:]) != (12, sites) or p.shape[0] != xn.shape[0]:
+            raise ValueError(f'LatticeSU3.{what}: need a native {kind} field [nb, nrhs, 12, {v}] or [nb, 12, {v}] with '
+                             f'nb = {xn.shape[0]}, {v} = {sites}, got {list(psin.shape)}')
         return p.to(torch.complex128).contiguous(), single
 
     def _spinor_reference(self, what: str, x: Tensor, psi: Tensor) -> tuple[Tensor, bool]:
@@ -248,7 +264,7 @@ class WilsonFermions:
         op = _WilsonOp(xn, k, self._lattice_shape, antiperiodic_t, b)
         cg = _CG('wilson_solve', b, single, op, tol, max_iter, check_every)
         cg.cgnr()
-        return (cg.x[:, 0] if single else cg.x), cg.info(cg.z, cg.p, cg.q)
+        return (cg.x[:, 0] if single else cg.x), cg.info(cg.residual(cg.z, cg.p, cg.q))
 
     def wilson_solve_eo_n(self, xn: Tensor, bn: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
                           check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
@@ -267,19 +283,14 @@ class WilsonFermions:
         be, bo = ops.su3_spinor_split_eo(b, L)
         zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
         spare = torch.zeros_like(be)
-        bb = ops.sum_parts(ops.su3_spinor_cg_update_(spare, be, bo, bo, zero)) \
-            + ops.sum_parts(ops.su3_spinor_cg_update_(spare, bo, be, be, zero))        # alpha = 0: |b_e|^2 + |b_o|^2
+        bb = _norm2(be, bo, spare, zero) + _norm2(bo, be, spare, zero)                 # |b_e|^2 + |b_o|^2
         bhat = ops.su3_wilson_hop_eo_n(xn, bo, L, 0, False, antiperiodic_t, a=k, aux=be, b=1.0)
         cg = _CG('wilson_solve_eo', bhat, single, _SchurOp(xn, k, L, antiperiodic_t, bhat), tol, max_iter, check_every, bb=bb)
         cg.cgnr()
         psio = ops.su3_wilson_hop_eo_n(xn, cg.x, L, 1, False, antiperiodic_t, a=k, aux=bo, b=1.0)
         psi = ops.su3_spinor_merge_eo(cg.x, psio, L)
-        # the residual of the full system: r = b - 1 * (M psi), by the update kernel as in `_CG.info`
-        mpsi = ops.su3_wilson_apply_n(xn, psi, k, L, False, antiperiodic_t)
-        r = b.clone()
-        rr = ops.sum_parts(ops.su3_spinor_cg_update_(torch.zeros_like(b), r, mpsi, mpsi, torch.ones_like(zero)))
-        res = torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
-        return (psi[:, 0] if single else psi), {'iters': cg.iters, 'converged': ~cg.active, 'residual': res}
+        mpsi = ops.su3_wilson_apply_n(xn, psi, k, L, False, antiperiodic_t)             # the residual of the full system
+        return (psi[:, 0] if single else psi), cg.info(_residual(b.clone(), torch.zeros_like(b), mpsi, mpsi, bb))
 
     def wilson_solve(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
                      check_every: int = 10, antiperiodic_t: bool = True) -> tuple[Tensor, dict]:
@@ -369,22 +380,13 @@ class WilsonFermions:
     def _solve_normal(cg: _CG) -> tuple[Tensor, Tensor, dict]:
         Y, action = cg.normal()
         X = cg.x
-        info = {**cg.info(cg.q, cg.p, cg.z), 'action': action}
+        info = {**cg.info(cg.residual(cg.q, cg.p, cg.z)), 'action': action}
         return (X[:, 0], Y[:, 0], info) if cg.single else (X, Y, info)
 
     # ------------------------------------------------------------ even-odd preconditioning: the Schur complement
     def _eo_lattice(self, what: str):
         """the lattice, or ValueError naming it if an extent is odd"""
         return ops._even_lattice(f'LatticeSU3.{what}', self._lattice_shape)
-
-    def _half_native(self, what: str, xn: Tensor, fn: Tensor) -> tuple[Tensor, bool]:
-        """a half field as [nb, nrhs, 12, V/2] and whether it came without the nrhs axis"""
-        single = fn.dim() == 3
-        p = fn[:, None] if single else fn
-        if p.dim() != 4 or tuple(p.shape[2:]) != (12, self.volume // 2) or p.shape[0] != xn.shape[0]:
-            raise ValueError(f'LatticeSU3.{what}: need a native half field [nb, nrhs, 12, V/2] or [nb, 12, V/2] with '
-                             f'nb = {xn.shape[0]}, V/2 = {self.volume // 2}, got {list(fn.shape)}')
-        return p.to(torch.complex128).contiguous(), single
 
     def _half_reference(self, what: str, x: Tensor, psi: Tensor) -> tuple[Tensor, bool]:
         """the even half field of a full-shape field in the reference layout: its odd sites are not read"""
@@ -403,7 +405,7 @@ class WilsonFermions:
         `l2q_su3_wilson_hop_eo`; a new field.  Even extents only."""
         k = self._pf_checks('wilson_schur', kappa, xn, psi_e)
         L = self._eo_lattice('wilson_schur')
-        p, single = self._half_native('wilson_schur', xn, psi_e)
+        p, single = self._spinor_native('wilson_schur', xn, psi_e, half=True)
         out = torch.empty_like(p)
         _SchurOp(xn, k, L, antiperiodic_t, p).apply(p, out, dagger, norm=False)
         return out[:, 0] if single else out
@@ -427,21 +429,25 @@ class WilsonFermions:
         k = self._pf_checks('wilson_solve_schur_normal', kappa, xn, phi_e)
         _CG.check_args('wilson_solve_schur_normal', tol, max_iter, check_every)
         L = self._eo_lattice('wilson_solve_schur_normal')
-        b, single = self._half_native('wilson_solve_schur_normal', xn, phi_e)
+        b, single = self._spinor_native('wilson_solve_schur_normal', xn, phi_e, half=True)
         op = _SchurOp(xn, k, L, antiperiodic_t, b)
         return self._solve_normal(_CG('wilson_solve_schur_normal', b, single, op, tol, max_iter, check_every))
 
-    def _schur_force_fields_n(self, xn: Tensor, phi_e: Tensor, k: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
-        """The full fields (X, Y) whose `l2q_su3_wilson_force` is the force of the even-odd action phi_e^H (Mhat^H
+    def _force_fields_n(self, what: str, xn: Tensor, phin: Tensor, kappa: float, even_odd: bool,
+                        **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """(X, Y, info), X and Y the full fields whose `l2q_su3_wilson_force` is the force of the pseudofermion action:
+        those of `wilson_solve_normal_n`, or with even_odd, phin the half field phi_e and the action phi_e^H (Mhat^H
         Mhat)^-1 phi_e: X_e, Y_e from `wilson_solve_schur_normal_n`, X_o = kappa H_oe X_e, Y_o = kappa (H^H)_oe Y_e.
         Exact: dS_f = 2 kappa Re[Y_e^H dH_eo X_o + Y_o^H dH_oe X_e], the full-lattice expression."""
-        L = self._eo_lattice('pseudofermion_force')
+        if not even_odd:
+            return self.wilson_solve_normal_n(xn, phin, kappa, **solve_kwargs)
+        L = self._eo_lattice(what)
         ap = solve_kwargs.get('antiperiodic_t', True)
-        Xe, Ye, info = self.wilson_solve_schur_normal_n(xn, phi_e, k, **solve_kwargs)
+        Xe, Ye, info = self.wilson_solve_schur_normal_n(xn, phin, kappa, **solve_kwargs)
         if Xe.dim() == 3:
             Xe, Ye = Xe[:, None].contiguous(), Ye[:, None].contiguous()
-        Xo = ops.su3_wilson_hop_eo_n(xn, Xe, L, 1, False, ap, a=k)
-        Yo = ops.su3_wilson_hop_eo_n(xn, Ye, L, 1, True, ap, a=k)
+        Xo = ops.su3_wilson_hop_eo_n(xn, Xe, L, 1, False, ap, a=kappa)
+        Yo = ops.su3_wilson_hop_eo_n(xn, Ye, L, 1, True, ap, a=kappa)
         return ops.su3_spinor_merge_eo(Xe, Xo, L), ops.su3_spinor_merge_eo(Ye, Yo, L), info
 
     def wilson_solve_normal(self, x: Tensor, phi: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
@@ -484,8 +490,7 @@ class WilsonFermions:
         else:
             phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
         zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
-        part = ops.su3_spinor_cg_update_(torch.zeros_like(eta), eta, phi, phi, zero)     # alpha = 0: |eta|^2
-        return phi, self._sum_fields(ops.sum_parts(part))
+        return phi, self._sum_fields(_norm2(eta, phi, torch.zeros_like(eta), zero))      # |eta|^2
 
     def pseudofermion_refresh(self, x: Tensor, kappa: float, npf: int = 1, generator: Optional[torch.Generator] = None,
                               antiperiodic_t: bool = True) -> tuple[Tensor, Tensor]:
@@ -504,29 +509,31 @@ class WilsonFermions:
         phi, s0 = self.pseudofermion_refresh_eo_n(self.pack(x), kappa, npf, generator, antiperiodic_t)
         return self._half_to_reference(phi), s0
 
+    def _pf_field(self, what: str, x: Tensor, phi: Tensor, even_odd: bool, native: bool) -> Tensor:
+        """the checked native field of the action and the force: phi (native, or in the reference layout on the links
+        x) as [nb, npf, 12, V], or with even_odd (even extents then) as the half field [nb, npf, 12, V/2]"""
+        if even_odd:
+            self._eo_lattice(what)
+        if native:
+            return self._spinor_native(what, x, phi, half=even_odd)[0]
+        return (self._half_reference if even_odd else self._spinor_reference)(what, x, phi)[0]
+
     def pseudofermion_action_n(self, xn: Tensor, phin: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
         """S_f = sum_r phi_r^H (M^H M)^-1 phi_r = sum_r |Y_r|^2 per chain, by one `wilson_solve_normal_n` (whose
         keywords these are): (S_f [nb], info).  One more keyword, even_odd (default False): with True phin is the half
         field phi_e and S_f = sum_r |Y_e,r|^2 by one `wilson_solve_schur_normal_n`."""
         self._pf_checks('pseudofermion_action', kappa, xn, phin)
-        if solve_kwargs.pop('even_odd', False):
-            self._eo_lattice('pseudofermion_action')
-            b, _ = self._half_native('pseudofermion_action', xn, phin)
-            _, _, info = self.wilson_solve_schur_normal_n(xn, b, kappa, **solve_kwargs)
-        else:
-            b, _ = self._spinor_native('pseudofermion_action', xn, phin)
-            _, _, info = self.wilson_solve_normal_n(xn, b, kappa, **solve_kwargs)
+        even_odd = bool(solve_kwargs.pop('even_odd', False))
+        b = self._pf_field('pseudofermion_action', xn, phin, even_odd, native=True)
+        solve = self.wilson_solve_schur_normal_n if even_odd else self.wilson_solve_normal_n
+        info = solve(xn, b, kappa, **solve_kwargs)[2]
         return self._sum_fields(info['action']), info
 
     def pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
         """`pseudofermion_action_n` in the reference layout; with even_odd only the even sites of phi are read"""
         self._pf_checks('pseudofermion_action', kappa, x, phi)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
-        if even_odd:
-            self._eo_lattice('pseudofermion_action')
-            pn, _ = self._half_reference('pseudofermion_action', x, phi)
-        else:
-            pn, _ = self._spinor_reference('pseudofermion_action', x, phi)
+        pn = self._pf_field('pseudofermion_action', x, phi, even_odd, native=False)
         return self.pseudofermion_action_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
 
     def pseudofermion_force_n(self, xn: Tensor, phin: Tensor, kappa: float,
@@ -537,13 +544,9 @@ class WilsonFermions:
         the force is that of phi_e^H (Mhat^H Mhat)^-1 phi_e: one `wilson_solve_schur_normal_n`, the odd halves X_o = kappa H_oe X_e and
         Y_o = kappa (H^H)_oe Y_e by one hop each, and the same `l2q_su3_wilson_force` on the merged fields (exact)."""
         k = self._pf_checks('pseudofermion_force', kappa, xn, phin)
-        if solve_kwargs.pop('even_odd', False):
-            self._eo_lattice('pseudofermion_force')
-            b, _ = self._half_native('pseudofermion_force', xn, phin)
-            X, Y, info = self._schur_force_fields_n(xn, b, k, **solve_kwargs)
-        else:
-            b, _ = self._spinor_native('pseudofermion_force', xn, phin)
-            X, Y, info = self.wilson_solve_normal_n(xn, b, k, **solve_kwargs)
+        even_odd = bool(solve_kwargs.pop('even_odd', False))
+        b = self._pf_field('pseudofermion_force', xn, phin, even_odd, native=True)
+        X, Y, info = self._force_fields_n('pseudofermion_force', xn, b, k, even_odd, **solve_kwargs)
         F = ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True))
         return F, self._sum_fields(info['action']), info
 
@@ -552,10 +555,6 @@ class WilsonFermions:
         sites of phi are read"""
         self._pf_checks('pseudofermion_force', kappa, x, phi)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
-        if even_odd:
-            self._eo_lattice('pseudofermion_force')
-            pn, _ = self._half_reference('pseudofermion_force', x, phi)
-        else:
-            pn, _ = self._spinor_reference('pseudofermion_force', x, phi)
+        pn = self._pf_field('pseudofermion_force', x, phi, even_odd, native=False)
         F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
         return self.unpack(F), s, info

@@ -1,14 +1,17 @@
-"""CPU tier of the product's own CG loops: `LatticeSU3.wilson_solve_n` and `wilson_solve_normal_n` run on CPU tensors with
-the four kernel entries of `l2hmc._ops` they call replaced by numpy stand-ins built on tests/wilson_restatement.py
-(`ops.sum_parts` stays the real one).  What tests/test_wilson_host.py and tests/test_wilson_force_host.py assert of the
-numpy CGs `wr.cgnr` / `wf.normal_cg` is asserted here of the loops the GPU runs, with the same bounds: the dense solve,
-the freeze semantics, never raising -- and the launch sequence, which only the product has."""
+"""CPU tier of the product's own CG loops: `LatticeSU3.wilson_solve_n` and `wilson_solve_normal_n`, and their even-odd
+forms `wilson_solve_eo_n` and `wilson_solve_schur_normal_n`, run on CPU tensors with the five kernel entries of
+`l2hmc._ops` they call replaced by numpy stand-ins built on tests/wilson_restatement.py and tests/wilson_eo_restatement.py
+(`ops.sum_parts`, `su3_spinor_split_eo` and `su3_spinor_merge_eo` stay the real ones: they are pure torch).  What
+tests/test_wilson_host.py and tests/test_wilson_force_host.py assert of the numpy CGs `wr.cgnr` / `wf.normal_cg` is
+asserted here of the loops the GPU runs, with the same bounds: the dense solve, the freeze semantics, never raising --
+and the launch sequence, which only the product has."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import wilson_eo_restatement as we
 import wilson_force_restatement as wf
 import wilson_restatement as wr
 from l2hmc import _ops as ops
@@ -26,9 +29,11 @@ def norm_part(f):
 
 
 class StandIns:
-    """`su3_wilson_apply_n`, `su3_spinor_cg_update_`, `su3_spinor_xpay_` and `su3_wilson_norm_parts` of `l2hmc._ops` on
-    CPU tensors, with their signatures; `log` lists the calls as (entry, dagger, norm requested)."""
-    NAMES = ('su3_wilson_apply_n', 'su3_spinor_cg_update_', 'su3_spinor_xpay_', 'su3_wilson_norm_parts')
+    """`su3_wilson_apply_n`, `su3_wilson_hop_eo_n`, `su3_spinor_cg_update_`, `su3_spinor_xpay_` and
+    `su3_wilson_norm_parts` of `l2hmc._ops` on CPU tensors, with their signatures; `log` lists the calls as (entry,
+    dagger, norm requested), a hop as ('hop', parity, dagger, norm requested)."""
+    NAMES = ('su3_wilson_apply_n', 'su3_wilson_hop_eo_n', 'su3_spinor_cg_update_', 'su3_spinor_xpay_',
+             'su3_wilson_norm_parts')
 
     def __init__(self, monkeypatch=None):
         self.log = []
@@ -49,6 +54,19 @@ class StandIns:
         if not want_norm:
             return out
         part = norm if isinstance(norm, torch.Tensor) else torch.empty((*psin.shape[:2], 1), dtype=torch.float64)
+        return out, part.copy_(norm_part(out))
+
+    def su3_wilson_hop_eo_n(self, xn, src, lat, parity, dagger=False, antiperiodic_t=True, a=1.0, aux=None, b=0.0,
+                            out=None, norm=False):
+        want_norm = isinstance(norm, torch.Tensor) or bool(norm)
+        self.log.append(('hop', int(parity), bool(dagger), want_norm))
+        res = we.hop_eo(wf.unpack_links(xn.numpy(), lat), we.unpack_half(src.numpy(), lat, 1 - parity), parity, dagger,
+                        antiperiodic_t, a, None if aux is None else we.unpack_half(aux.numpy(), lat, parity), b)
+        out = torch.empty_like(src) if out is None else out              # out may be aux: res is complete by now
+        out.copy_(torch.from_numpy(we.pack_half(res, parity)))
+        if not want_norm:
+            return out
+        part = norm if isinstance(norm, torch.Tensor) else torch.empty((*src.shape[:2], 1), dtype=torch.float64)
         return out, part.copy_(norm_part(out))
 
     def su3_spinor_cg_update_(self, x, r, p, q, alpha, part=None):
@@ -87,10 +105,13 @@ def dense(L, kappa):
 
 
 def solve(lat, which, xn, bn, kappa, **kw):
-    """(solution, info) of either solver"""
-    if which == 'cgnr':
-        return lat.wilson_solve_n(xn, bn, kappa, **kw)
-    X, _, info = lat.wilson_solve_normal_n(xn, bn, kappa, **kw)
+    """(solution, info) of one of the four solvers; 'schur_normal' takes the even half of bn for its right-hand side"""
+    if which in ('cgnr', 'eo'):
+        return (lat.wilson_solve_n if which == 'cgnr' else lat.wilson_solve_eo_n)(xn, bn, kappa, **kw)
+    if which == 'schur_normal':
+        X, _, info = lat.wilson_solve_schur_normal_n(xn, ops.su3_spinor_split_eo(bn, lat._lattice_shape)[0], kappa, **kw)
+    else:
+        X, _, info = lat.wilson_solve_normal_n(xn, bn, kappa, **kw)
     return X, info
 
 
@@ -190,3 +211,103 @@ def test_bad_arguments_name_the_public_method(standins):
         with pytest.raises(ValueError, match=r'LatticeSU3\.wilson_solve_normal: need tol > 0'):
             lat.wilson_solve_normal_n(xn, bn, 0.1, **kw)
     assert standins.log == []
+
+
+# ------------------------------------------------------------------ the even-odd solvers through the same stand-ins
+@functools.lru_cache(maxsize=None)
+def dense_schur(L, kappa):
+    """per chain of `inputs(L)`: (Mhat dense, its smallest and largest singular value)"""
+    out = []
+    for c in range(NB):
+        m = we.dense_schur(wr.links(L, NB)[c:c + 1], kappa)
+        s = np.linalg.svd(m, compute_uv=False)
+        out.append((m, s[-1], s[0]))
+    return out
+
+
+@pytest.mark.parametrize('L', LATTICES)
+def test_eo_cgnr_against_dense_solve(standins, L):
+    """`wilson_solve_eo_n` solves the full system: the bound of `test_cgnr_against_dense_solve` against the full dense M,
+    |psi - M^-1 b| <= 2 tol |b| / sigma_min(M)"""
+    tol = 1e-10
+    lat, x, b, xn, bn = inputs(L)
+    for kappa in wr.SOLVE_KAPPAS:
+        psin, info = lat.wilson_solve_eo_n(xn, bn, kappa, tol=tol, max_iter=200)
+        assert info['converged'].all() and (info['residual'] <= 2 * tol).all(), (kappa, info)
+        psi = wr.unpack_spinor(psin.numpy(), L)
+        for c, (m, smin, _) in enumerate(dense(L, kappa)):
+            for j in range(NRHS):
+                want = np.linalg.solve(m, b[c, j].reshape(-1))
+                err, bound = np.linalg.norm(psi[c, j].reshape(-1) - want), 2 * tol * np.linalg.norm(b[c, j]) / smin
+                print(L, kappa, c, j, 'iters', int(info['iters'][c, j]), 'error', err, 'bound', bound)
+                assert err <= bound, (kappa, c, j)
+
+
+@pytest.mark.parametrize('L', LATTICES)
+def test_schur_normal_cg_against_dense_solve(standins, L):
+    """the bound of `test_normal_cg_against_dense_solve` on the Schur complement: |dX_e| <= cond(Mhat^H Mhat) * residual,
+    cond < 100 (held here from the singular values of `we.dense_schur`), and info['action'] = |Y_e|^2 by the same sums"""
+    lat, x, b, xn, bn = inputs(L)
+    pe = ops.su3_spinor_split_eo(bn, L)[0]
+    for kappa in wr.SOLVE_KAPPAS:
+        assert all((smax / smin) ** 2 < 100 for _, smin, smax in dense_schur(L, kappa))
+        # rows of Mhat: even site, then spin and colour; a native half field is [12, V/2]
+        Xd = np.stack([np.linalg.solve(m.conj().T @ m, pe[c].numpy().transpose(2, 1, 0).reshape(-1, NRHS))
+                       .reshape(-1, 12, NRHS).transpose(2, 1, 0) for c, (m, _, _) in enumerate(dense_schur(L, kappa))])
+        for tol in (1e-6, 1e-10):
+            Xn, Yn, info = lat.wilson_solve_schur_normal_n(xn, pe, kappa, tol=tol)
+            assert info['converged'].all() and (info['residual'] <= 2 * tol).all(), (kappa, tol, info)
+            err = np.abs(Xn.numpy() - Xd).max()
+            print(L, kappa, tol, 'iters', info['iters'].tolist(), 'error', err, 'bound', 100 * tol * np.abs(Xd).max())
+            assert err <= 100 * tol * np.abs(Xd).max()
+            assert torch.equal(info['action'], ops.sum_parts(norm_part(Yn)))
+            assert torch.equal(Yn, lat.wilson_schur_n(xn, Xn, kappa))
+
+
+@pytest.mark.parametrize('which', ['eo', 'schur_normal'])
+@pytest.mark.parametrize('L', LATTICES)
+def test_eo_freeze_semantics(standins, L, which):
+    kappa = wr.SOLVE_KAPPAS[1]
+    lat, x, b, xn, bn = inputs(L)
+    X, info = solve(lat, which, xn, bn, kappa, tol=1e-10)
+    print(L, which, 'iters', info['iters'].tolist())
+    assert info['converged'].all()
+    # a system keeps its bits when others join the batch
+    X1, i1 = solve(lat, which, xn[:1], bn[:1, :1].contiguous(), kappa, tol=1e-10)
+    assert torch.equal(X1[0, 0], X[0, 0]) and torch.equal(i1['iters'][0, 0], info['iters'][0, 0])
+    assert torch.equal(i1['residual'][0, 0], info['residual'][0, 0])
+    # b = 0: a zero solution in zero iterations, and the others as before
+    big = bn.clone()
+    big[1, 1] = 0.0
+    Xb, ib = solve(lat, which, xn, big, kappa, tol=1e-10)
+    assert not Xb[1, 1].any() and ib['iters'][1, 1] == 0 and ib['residual'][1, 1] == 0.0 and ib['converged'].all()
+    assert torch.equal(Xb[0], X[0])
+    # never raises: too few iterations are reported
+    few = solve(lat, which, xn, bn, kappa, tol=1e-10, max_iter=3)[1]
+    assert not few['converged'].any() and (few['iters'] == 3).all()
+
+
+@pytest.mark.parametrize('which', ['eo', 'schur_normal'])
+def test_eo_launch_sequence(standins, which):
+    """as `test_launch_sequence_and_check_arithmetic`: 7 iterations, iters = 7, and the whole list of calls.  Mhat is
+    two hops, odd then even, the fused norm from the second.  `wilson_solve_eo_n` adds |b_e|^2 and |b_o|^2 (two updates),
+    the source, the reconstruction and one full apply for its residual: 34 hops, 1 apply, 11 updates, 7 xpays."""
+    L = LATTICES[1]
+    lat, x, b, xn, bn = inputs(L)
+    del standins.log[:]
+    _, info = solve(lat, which, xn, bn, wr.SOLVE_KAPPAS[0], tol=1e-30, max_iter=7, check_every=3)
+    assert not info['converged'].any() and (info['iters'] == 7).all()
+    update, xpay = ('update', None, None), ('xpay', None, None)
+    mhat = [('hop', 1, False, False), ('hop', 0, False, True)]
+    if which == 'eo':
+        mhath = [('hop', 1, True, False), ('hop', 0, True, True)]
+        want = [update, update, ('hop', 0, False, False), update] + mhath + 7 * (mhat + [update] + mhath + [xpay]) \
+            + mhat + [('hop', 1, False, False), ('apply', False, False), update]
+        counts = (34, 1, 11, 7)
+    else:
+        mhath = [('hop', 1, True, False), ('hop', 0, True, False)]
+        want = [update] + 7 * (mhat + mhath + [update, xpay]) + mhat + mhath + [update]
+        counts = (32, 0, 9, 7)
+    assert standins.log == want
+    names = [e[0] for e in standins.log]
+    assert tuple(names.count(n) for n in ('hop', 'apply', 'update', 'xpay')) == counts

@@ -20,23 +20,13 @@ import gaugefix_restatement as gf
 import wilson_eo_restatement as we
 import wilson_force_restatement as wf
 import wilson_restatement as wr
+import wilson_gpu_util
+from wilson_gpu_util import dev, host, unit_links
 
 gpu = pytest.mark.gpu
 NB = 3
 TOL_SOLVE = 1e-10
 SCHUR_TOL = we.TOL                                       # see the head of the file
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def unit_links(nb, L):
-    return np.broadcast_to(np.eye(3, dtype=complex), (nb, 4, *L, 3, 3)).copy()
 
 
 @functools.lru_cache(maxsize=None)
@@ -340,16 +330,8 @@ def test_force_against_restatement_and_differences(L, ap):
     assert ((ratio > 3.5) & (ratio < 4.5)).all(), ratio
 
 
-def _hmc(L, nb=2, cls='WilsonHMCEvenOdd', **kw):
-    from l2hmc.dynamics.pytorch import fermion_hmc
-    from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
-    lat = LatticeSU3(nb, list(L))
-    return lat, getattr(fermion_hmc, cls)(lat, **{**wf.TRAJ, **kw})
-
-
-def _native(x, v, phi_e):
-    from l2hmc import _ops as ops
-    return ops.su3_pack(dev(x)), ops.su3_pack(dev(v)), dev(we.pack_half(phi_e, 0))
+_hmc = functools.partial(wilson_gpu_util._hmc, cls='WilsonHMCEvenOdd')
+_native = functools.partial(wilson_gpu_util._native, half=True)
 
 
 @gpu
@@ -414,7 +396,7 @@ def test_trajectory_accept_reject_and_seed():
     xo2, m2 = run(hmc)
     assert torch.equal(x, keep)
     assert torch.equal(xo, xo2) and all(torch.equal(m[k], m2[k]) for k in ('acc', 'acc_mask', 'dH', 'plaq'))
-    _, mf = run(_hmc(L, nb, 'WilsonHMC', npf=2)[1])
+    _, mf = run(_hmc(L, nb, cls='WilsonHMC', npf=2)[1])
     assert sorted(m) == sorted(mf)                                               # the same metrics
     assert m['unconverged'] == 0 and 0 < m['cg_iters_md']['mean'] < mf['cg_iters_md']['mean'] and m['cg_iters_h']['max'] > 0
     assert tuple(m['dH'].shape) == (nb,) and bool(torch.isfinite(m['dH']).all())

@@ -11,6 +11,7 @@ import pytest
 import host_emu
 import wilson_force_restatement as wf
 import wilson_restatement as wr
+from wilson_gpu_util import antihermitian_bits
 
 NB = 2
 COEF = -0.05
@@ -25,13 +26,6 @@ def emu(tmp_path_factory):
         outs = host_emu.run(exe, [NB, npf, *L, swz, repr(wr.KAPPA), repr(COEF)], [xn, Xn, Yn, vn], 4)
         return [o.view(np.complex128).reshape(2, -1, 4, 9, V) for o in outs]
     return run
-
-
-def antihermitian_bits(fn):
-    """plane (j, i) is (-re, im) of plane (i, j), the diagonal has no real part"""
-    m = fn.reshape(*fn.shape[:-2], 3, 3, fn.shape[-1])
-    t = np.swapaxes(m, -3, -2)
-    return np.array_equal(t.real, -m.real) and np.array_equal(t.imag, m.imag)
 
 
 @pytest.mark.parametrize('npf', [1, 3])

@@ -14,25 +14,11 @@ import torch
 import wilson_force_restatement as wf
 import wilson_restatement as wr
 from oracle import su3 as osu3
+from wilson_gpu_util import _hmc, _native, antihermitian_bits, dev, host
 
 gpu = pytest.mark.gpu
 NB = 3
 COEF = -0.05
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def antihermitian_bits(fn):
-    """plane (j, i) is (-re, im) of plane (i, j), the diagonal has no real part"""
-    m = fn.reshape(*fn.shape[:-2], 3, 3, fn.shape[-1])
-    t = np.swapaxes(m, -3, -2)
-    return np.array_equal(t.real, -m.real) and np.array_equal(t.imag, m.imag)
 
 
 @functools.lru_cache(maxsize=None)
@@ -152,18 +138,6 @@ def test_force_by_finite_differences(ap):
     assert ((ratio > 3.5) & (ratio < 4.5)).all(), ratio
 
 
-def _hmc(L, nb=2, **kw):
-    from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC
-    from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
-    lat = LatticeSU3(nb, list(L))
-    return lat, WilsonHMC(lat, **{**wf.TRAJ, **kw})
-
-
-def _native(lat, x, v, phi):
-    from l2hmc import _ops as ops
-    return ops.su3_pack(dev(x)), ops.su3_pack(dev(v)), ops.su3_spinor_pack(dev(phi))
-
-
 @gpu
 @pytest.mark.parametrize('L', wf.TRAJ_LATTICES)
 def test_trajectory_against_restatement(L):
@@ -173,7 +147,7 @@ def test_trajectory_against_restatement(L):
     x, v, phi, s0 = wf.traj_inputs(L)
     x1w, v1w, dhw = wf.delta_h(x, v, phi, **wf.TRAJ)
     lat, hmc = _hmc(L, tol_md=wf.TRAJ_TOL_MD, tol_h=wf.TRAJ_TOL_H)
-    xn, vn, pn = _native(lat, x, v, phi)
+    xn, vn, pn = _native(x, v, phi)
     keep = [t.clone() for t in (xn, vn, pn)]
     x1, v1, info = hmc.leapfrog_n(xn, vn, pn)
     assert all(torch.equal(a, b) for a, b in zip((xn, vn, pn), keep))
@@ -198,7 +172,7 @@ def test_reversibility_and_step_size_scaling():
     L = (4, 4, 4, 4)
     x, v, phi, _ = wf.traj_inputs(L)
     lat, hmc = _hmc(L, tol_md=1e-12)
-    xn, vn, pn = _native(lat, x, v, phi)
+    xn, vn, pn = _native(x, v, phi)
     x1, v1, info = hmc.leapfrog_n(xn, vn, pn)
     x2, v2, _ = hmc.leapfrog_n(x1, -v1, pn)
     rev = max(float((x2 - xn).abs().max()), float((v2 + vn).abs().max()))
@@ -267,7 +241,7 @@ def test_kappa_zero():
     L = (4, 2, 2, 2)
     x, v, phi, _ = wf.traj_inputs(L)
     lat, hmc = _hmc(L, kappa=0.0)
-    xn, vn, pn = _native(lat, x, v, phi)
+    xn, vn, pn = _native(x, v, phi)
     X, Y, info = lat.wilson_solve_normal_n(xn, pn, 0.0)
     assert torch.equal(ops.su3_wilson_force_n(xn, X, Y, 0.0, L, coef=-0.3, f_in=vn), vn)
     sf, _ = lat.pseudofermion_action_n(xn, pn, 0.0)

@@ -14,22 +14,11 @@ import torch
 
 import gaugefix_restatement as gf
 import wilson_restatement as wr
+from wilson_gpu_util import dev, host, unit_links
 
 gpu = pytest.mark.gpu
 NB = 3
 TOL_SOLVE = 1e-10
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def unit_links(nb, L):
-    return np.broadcast_to(np.eye(3, dtype=complex), (nb, 4, *L, 3, 3)).copy()
 
 
 @functools.lru_cache(maxsize=None)

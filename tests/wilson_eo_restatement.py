@@ -16,7 +16,6 @@ import numpy as np
 
 import wilson_force_restatement as wfr
 import wilson_restatement as wr
-from oracle import su3 as osu3
 
 
 # ------------------------------------------------------------------ parities and the half layout
@@ -78,77 +77,10 @@ def dense_schur(x, kappa, antiperiodic_t=True):
     return schur(x[:1], basis, kappa, False, antiperiodic_t).reshape(len(idx), n).T[idx]
 
 
-# ------------------------------------------------------------------ the two CG loops on any operator
-def cgnr_op(op, b, bb, tol=1e-10, max_iter=1000, check_every=10):
-    """A psi = b by CG on A^H A, `wr.cgnr` with op(p, dagger) for the operator and bb [nb, nrhs] for the reference norm of
-    the stopping test |r|^2 <= tol^2 bb.  Returns (psi, iters, done)."""
-    psi = np.zeros_like(b)
-    r = b.copy()
-    z = op(r, True)
-    p = z.copy()
-    zz = wr.norm2(z)
-    rr = wr.norm2(b)
-    done = bb <= tol * tol * bb
-    iters = np.where(done, 0, max_iter)
-    k = 0
-    while k < max_iter and not done.all():
-        q = op(p, False)
-        qq = wr.norm2(q)
-        live = ~done & (qq > 0)
-        alpha = np.where(live, zz / np.where(live, qq, 1.0), 0.0)
-        psi = psi + wr._bc(alpha) * p
-        r = r - wr._bc(alpha) * q
-        rr = wr.norm2(r)
-        z = op(r, True)
-        zn = wr.norm2(z)
-        live = ~done & (zz > 0)
-        beta = np.where(live, zn / np.where(live, zz, 1.0), 0.0)
-        p = z + wr._bc(beta) * p
-        zz = zn
-        k += 1
-        if k % check_every == 0 or k == max_iter:
-            now = ~done & (rr <= tol * tol * bb)
-            iters = np.where(now, k, iters)
-            done = done | now
-    return psi, iters, done
-
-
-def normal_cg_op(op, phi, tol=1e-10, max_iter=1000, check_every=10):
-    """A^H A X = phi by CG, `wfr.normal_cg` with op(p, dagger) for the operator: (X, Y = A X, info)"""
-    X = np.zeros_like(phi)
-    r = phi.copy()
-    p = phi.copy()
-    bb = wr.norm2(phi)
-    rr = bb.copy()
-    done = rr <= tol * tol * bb
-    iters = np.where(done, 0, max_iter)
-    k = 0
-    while k < max_iter and not done.all():
-        q = op(p, False)
-        qq = wr.norm2(q)
-        z = op(q, True)
-        live = ~done & (qq > 0)
-        alpha = np.where(live, rr / np.where(live, qq, 1.0), 0.0)
-        X = X + wr._bc(alpha) * p
-        r = r - wr._bc(alpha) * z
-        rn = wr.norm2(r)
-        live = ~done & (rr > 0)
-        beta = np.where(live, rn / np.where(live, rr, 1.0), 0.0)
-        p = r + wr._bc(beta) * p
-        rr = rn
-        k += 1
-        if k % check_every == 0 or k == max_iter:
-            now = ~done & (rr <= tol * tol * bb)
-            iters = np.where(now, k, iters)
-            done = done | now
-    Y = op(X, False)
-    res = np.sqrt(wr.norm2(phi - op(Y, True)) / np.where(bb > 0, bb, 1.0))
-    return X, Y, {'iters': iters, 'converged': done, 'residual': res, 'action': wr.norm2(Y)}
-
-
+# ------------------------------------------------------------------ the solves: `wr.cgnr_op` and `wfr.normal_cg_op`
 def full_cgnr(x, b, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
-    """`cgnr_op` on the full M: (psi, iters) -- the unpreconditioned solve by the same loop, for the iteration counts"""
-    psi, iters, _ = cgnr_op(lambda p, d: wr.wilson(x, p, kappa, d, antiperiodic_t), b, wr.norm2(b), tol, max_iter,
+    """`wr.cgnr_op` on the full M: (psi, iters) -- the unpreconditioned solve by the same loop, for the iteration counts"""
+    psi, iters, _ = wr.cgnr_op(lambda p, d: wr.wilson(x, p, kappa, d, antiperiodic_t), b, wr.norm2(b), tol, max_iter,
                             check_every)
     return psi, iters
 
@@ -161,7 +93,7 @@ def solve_eo(x, b, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic
     be, bo = b * mask(L, 0), b * mask(L, 1)
     bb = wr.norm2(b)
     bhat = hop_eo(x, bo, 0, False, antiperiodic_t, a=kappa, aux=be, b=1.0)
-    pe, iters, done = cgnr_op(lambda p, d: schur(x, p, kappa, d, antiperiodic_t), bhat, bb, tol, max_iter, check_every)
+    pe, iters, done = wr.cgnr_op(lambda p, d: schur(x, p, kappa, d, antiperiodic_t), bhat, bb, tol, max_iter, check_every)
     psi = pe + hop_eo(x, pe, 1, False, antiperiodic_t, a=kappa, aux=bo, b=1.0)
     res = np.sqrt(wr.norm2(b - wr.wilson(x, psi, kappa, False, antiperiodic_t)) / np.where(bb > 0, bb, 1.0))
     return psi, {'iters': iters, 'residual': res, 'converged': done}
@@ -183,19 +115,8 @@ def dense_normal_eo(x, phi_e, kappa, antiperiodic_t=True):
 
 
 def normal_cg_eo(x, phi_e, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
-    return normal_cg_op(lambda p, d: schur(x, p, kappa, d, antiperiodic_t), phi_e, tol, max_iter, check_every)
-
-
-def _solve(x, phi_e, kappa, antiperiodic_t, tol):
-    """tol None: dense; else the CG at that tol"""
-    if tol is None:
-        return dense_normal_eo(x, phi_e, kappa, antiperiodic_t)
-    return normal_cg_eo(x, phi_e, kappa, tol=tol, max_iter=4000, antiperiodic_t=antiperiodic_t)[:2]
-
-
-def fermion_action(x, phi_e, kappa, antiperiodic_t=True, tol=None):
-    """S_f [nb] = sum_r |Y_e,r|^2 = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r"""
-    return wr.norm2(_solve(x, phi_e, kappa, antiperiodic_t, tol)[1]).sum(1)
+    """Mhat^H Mhat X_e = phi_e by `wfr.normal_cg_op` on the Schur complement: (X_e, Y_e = Mhat X_e, info)"""
+    return wfr.normal_cg_op(lambda p, d: schur(x, p, kappa, d, antiperiodic_t), phi_e, tol, max_iter, check_every)
 
 
 def completed(x, Xe, Ye, kappa, antiperiodic_t=True):
@@ -204,9 +125,9 @@ def completed(x, Xe, Ye, kappa, antiperiodic_t=True):
             Ye + hop_eo(x, Ye, 1, True, antiperiodic_t, a=kappa))
 
 
-def fermion_force(x, phi_e, kappa, antiperiodic_t=True, tol=None):
-    X, Y = completed(x, *_solve(x, phi_e, kappa, antiperiodic_t, tol), kappa, antiperiodic_t)
-    return wfr.force(x, X, Y, kappa, antiperiodic_t)
+# S_f [nb] = sum_r |Y_e,r|^2 = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r, its force (that of the completed fields) and its leapfrog
+fermion_action, fermion_force, total_force, leapfrog, hamiltonian, delta_h = wfr.Trajectory(
+    dense_normal_eo, normal_cg_eo, completed).names()
 
 
 def refresh(x, eta_e, kappa, antiperiodic_t=True):
@@ -214,31 +135,6 @@ def refresh(x, eta_e, kappa, antiperiodic_t=True):
     L = eta_e.shape[2:6]
     eta_e = eta_e * mask(L, 0)
     return schur(x, eta_e, kappa, True, antiperiodic_t), wr.norm2(eta_e).sum(1)
-
-
-def total_force(x, phi_e, beta, kappa, antiperiodic_t=True, tol=None):
-    f = fermion_force(x, phi_e, kappa, antiperiodic_t, tol)
-    return f + osu3.grad_action(x, beta) if beta != 0 else f
-
-
-def leapfrog(x, v, phi_e, beta, kappa, eps, nleapfrog, antiperiodic_t=True, tol=None):
-    """`wfr.leapfrog` under the even-odd action"""
-    v = v - 0.5 * eps * total_force(x, phi_e, beta, kappa, antiperiodic_t, tol)
-    for k in range(nleapfrog):
-        x = osu3.expm(eps * v) @ x
-        v = v - (1.0 if k + 1 < nleapfrog else 0.5) * eps * total_force(x, phi_e, beta, kappa, antiperiodic_t, tol)
-    return x, v
-
-
-def hamiltonian(x, v, phi_e, beta, kappa, antiperiodic_t=True, tol=None):
-    return osu3.kinetic_energy(v) + osu3.action(x, beta) + fermion_action(x, phi_e, kappa, antiperiodic_t, tol)
-
-
-def delta_h(x, v, phi_e, beta, kappa, eps, nleapfrog, tol=None, tol_h=None):
-    """(x', v', H' - H) of one leapfrog"""
-    x1, v1 = leapfrog(x, v, phi_e, beta, kappa, eps, nleapfrog, True, tol)
-    return x1, v1, (hamiltonian(x1, v1, phi_e, beta, kappa, True, tol_h)
-                    - hamiltonian(x, v, phi_e, beta, kappa, True, tol_h))
 
 
 # ------------------------------------------------------------------ the inputs and the tolerances of the even-odd tests

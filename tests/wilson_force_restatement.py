@@ -71,12 +71,12 @@ def dense_normal(x, phi, kappa, antiperiodic_t=True):
     return X, wr.wilson(x, X, kappa, False, antiperiodic_t)
 
 
-def normal_cg(x, phi, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
-    """M^H M X = phi by CG from X = 0; per iteration q = M p, z = M^H q, alpha = |r|^2 / |q|^2, X += alpha p,
-    r -= alpha z, beta = |r'|^2 / |r|^2, p = r + beta p.  |r|^2 <= tol^2 |phi|^2 is looked at every check_every
-    iterations (and at 0 and max_iter); a converged system takes alpha = beta = 0 from then on.  Returns (X, Y, info),
-    Y = M X, info = {'iters', 'converged', 'residual' (|phi - M^H M X| / |phi| recomputed, 0 for phi = 0), 'action'
-    (|Y|^2)} each [nb, npf]."""
+def normal_cg_op(op, phi, tol=1e-10, max_iter=1000, check_every=10):
+    """A^H A X = phi by CG from X = 0, op(p, dagger) the operator; per iteration q = A p, z = A^H q, alpha = |r|^2 /
+    |q|^2, X += alpha p, r -= alpha z, beta = |r'|^2 / |r|^2, p = r + beta p.  |r|^2 <= tol^2 |phi|^2 is looked at every
+    check_every iterations (and at 0 and max_iter); a converged system takes alpha = beta = 0 from then on.  Returns (X,
+    Y, info), Y = A X, info = {'iters', 'converged', 'residual' (|phi - A^H A X| / |phi| recomputed, 0 for phi = 0),
+    'action' (|Y|^2)} each [nb, npf]."""
     X = np.zeros_like(phi)
     r = phi.copy()
     p = phi.copy()
@@ -86,9 +86,9 @@ def normal_cg(x, phi, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperio
     iters = np.where(done, 0, max_iter)
     k = 0
     while k < max_iter and not done.all():
-        q = wr.wilson(x, p, kappa, False, antiperiodic_t)
+        q = op(p, False)
         qq = wr.norm2(q)
-        z = wr.wilson(x, q, kappa, True, antiperiodic_t)
+        z = op(q, True)
         live = ~done & (qq > 0)
         alpha = np.where(live, rr / np.where(live, qq, 1.0), 0.0)
         X = X + wr._bc(alpha) * p
@@ -103,29 +103,71 @@ def normal_cg(x, phi, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperio
             now = ~done & (rr <= tol * tol * bb)
             iters = np.where(now, k, iters)
             done = done | now
-    Y = wr.wilson(x, X, kappa, False, antiperiodic_t)
-    res = np.sqrt(wr.norm2(phi - wr.wilson(x, Y, kappa, True, antiperiodic_t)) / np.where(bb > 0, bb, 1.0))
+    Y = op(X, False)
+    res = np.sqrt(wr.norm2(phi - op(Y, True)) / np.where(bb > 0, bb, 1.0))
     return X, Y, {'iters': iters, 'converged': done, 'residual': res, 'action': wr.norm2(Y)}
 
 
-def _solve(x, phi, kappa, antiperiodic_t, tol):
-    """tol None: dense; else the CG at that tol"""
-    if tol is None:
-        return dense_normal(x, phi, kappa, antiperiodic_t)
-    return normal_cg(x, phi, kappa, tol=tol, max_iter=4000, antiperiodic_t=antiperiodic_t)[:2]
+def normal_cg(x, phi, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
+    """M^H M X = phi by `normal_cg_op` on M: (X, Y = M X, info)"""
+    return normal_cg_op(lambda p, d: wr.wilson(x, p, kappa, d, antiperiodic_t), phi, tol, max_iter, check_every)
 
 
-# ------------------------------------------------------------------ action, heatbath, trajectory
-def fermion_action(x, phi, kappa, antiperiodic_t=True, tol=None):
-    """S_f [nb] = sum_r |Y_r|^2"""
-    return wr.norm2(_solve(x, phi, kappa, antiperiodic_t, tol)[1]).sum(1)
+# ------------------------------------------------------------------ action, force, trajectory
+class Trajectory:
+    """The action, the force and the leapfrog of a pseudofermion action phi^H (A^H A)^-1 phi over its three pieces:
+    dense(x, phi, kappa, antiperiodic_t) and cg(x, phi, kappa, tol=, max_iter=, antiperiodic_t=) solve A^H A X = phi and
+    give (X, Y = A X, ...); complete(x, X, Y, kappa, antiperiodic_t) gives the full fields whose `force` is the
+    action's.  Below for A = M; `wilson_eo_restatement` builds the one of the Schur complement."""
+
+    def __init__(self, dense, cg, complete):
+        self.dense, self.cg, self.complete = dense, cg, complete
+
+    def solve(self, x, phi, kappa, antiperiodic_t, tol):
+        """tol None: dense; else the CG at that tol"""
+        if tol is None:
+            return self.dense(x, phi, kappa, antiperiodic_t)
+        return self.cg(x, phi, kappa, tol=tol, max_iter=4000, antiperiodic_t=antiperiodic_t)[:2]
+
+    def fermion_action(self, x, phi, kappa, antiperiodic_t=True, tol=None):
+        """S_f [nb] = sum_r |Y_r|^2"""
+        return wr.norm2(self.solve(x, phi, kappa, antiperiodic_t, tol)[1]).sum(1)
+
+    def fermion_force(self, x, phi, kappa, antiperiodic_t=True, tol=None):
+        X, Y = self.complete(x, *self.solve(x, phi, kappa, antiperiodic_t, tol), kappa, antiperiodic_t)
+        return force(x, X, Y, kappa, antiperiodic_t)
+
+    def total_force(self, x, phi, beta, kappa, antiperiodic_t=True, tol=None):
+        f = self.fermion_force(x, phi, kappa, antiperiodic_t, tol)
+        return f + osu3.grad_action(x, beta) if beta != 0 else f
+
+    def leapfrog(self, x, v, phi, beta, kappa, eps, nleapfrog, antiperiodic_t=True, tol=None):
+        """half kick, nleapfrog link updates U <- exp(eps p) U with full kicks between them, half kick"""
+        v = v - 0.5 * eps * self.total_force(x, phi, beta, kappa, antiperiodic_t, tol)
+        for k in range(nleapfrog):
+            x = osu3.expm(eps * v) @ x
+            v = v - (1.0 if k + 1 < nleapfrog else 0.5) * eps * self.total_force(x, phi, beta, kappa, antiperiodic_t, tol)
+        return x, v
+
+    def hamiltonian(self, x, v, phi, beta, kappa, antiperiodic_t=True, tol=None):
+        return osu3.kinetic_energy(v) + osu3.action(x, beta) + self.fermion_action(x, phi, kappa, antiperiodic_t, tol)
+
+    def delta_h(self, x, v, phi, beta, kappa, eps, nleapfrog, tol=None, tol_h=None):
+        """(x', v', H' - H) of one leapfrog"""
+        x1, v1 = self.leapfrog(x, v, phi, beta, kappa, eps, nleapfrog, True, tol)
+        return x1, v1, (self.hamiltonian(x1, v1, phi, beta, kappa, True, tol_h)
+                        - self.hamiltonian(x, v, phi, beta, kappa, True, tol_h))
+
+    def names(self):
+        """the functions a restatement module exports under these names"""
+        return self.fermion_action, self.fermion_force, self.total_force, self.leapfrog, self.hamiltonian, self.delta_h
 
 
-def fermion_force(x, phi, kappa, antiperiodic_t=True, tol=None):
-    X, Y = _solve(x, phi, kappa, antiperiodic_t, tol)
-    return force(x, X, Y, kappa, antiperiodic_t)
+fermion_action, fermion_force, total_force, leapfrog, hamiltonian, delta_h = Trajectory(
+    dense_normal, normal_cg, lambda x, X, Y, kappa, antiperiodic_t: (X, Y)).names()
 
 
+# ------------------------------------------------------------------ heatbath and inputs of a trajectory
 def refresh(x, eta, kappa, antiperiodic_t=True):
     """(phi, S0): phi = M^H eta is distributed as exp(-S_f) for eta distributed as exp(-eta^H eta); S0 = |eta|^2 [nb]"""
     return wr.wilson(x, eta, kappa, True, antiperiodic_t), wr.norm2(eta).sum(1)
@@ -141,24 +183,6 @@ def gaussian_eta(L, nb, npf, seed=0):
 def momentum(L, nb, seed=0):
     rng = np.random.default_rng(6000 + seed + 1000 * L[0] + 100 * L[1] + 10 * L[2] + L[3])
     return osu3.rand_tah3(rng.standard_normal((8, nb, 4, *L)))
-
-
-def total_force(x, phi, beta, kappa, antiperiodic_t=True, tol=None):
-    f = fermion_force(x, phi, kappa, antiperiodic_t, tol)
-    return f + osu3.grad_action(x, beta) if beta != 0 else f
-
-
-def leapfrog(x, v, phi, beta, kappa, eps, nleapfrog, antiperiodic_t=True, tol=None):
-    """half kick, nleapfrog link updates U <- exp(eps p) U with full kicks between them, half kick"""
-    v = v - 0.5 * eps * total_force(x, phi, beta, kappa, antiperiodic_t, tol)
-    for k in range(nleapfrog):
-        x = osu3.expm(eps * v) @ x
-        v = v - (1.0 if k + 1 < nleapfrog else 0.5) * eps * total_force(x, phi, beta, kappa, antiperiodic_t, tol)
-    return x, v
-
-
-def hamiltonian(x, v, phi, beta, kappa, antiperiodic_t=True, tol=None):
-    return osu3.kinetic_energy(v) + osu3.action(x, beta) + fermion_action(x, phi, kappa, antiperiodic_t, tol)
 
 
 def richardson(x, phi, p, kappa, antiperiodic_t=True, h=1e-3, tol=None, action=None):
@@ -241,12 +265,6 @@ def traj_inputs(L, nb=2, npf=1):
     x = wr.links(L, nb)
     phi, s0 = refresh(x, gaussian_eta(L, nb, npf), TRAJ['kappa'])
     return x, momentum(L, nb, 1), phi, s0
-
-
-def delta_h(x, v, phi, beta, kappa, eps, nleapfrog, tol=None, tol_h=None):
-    """(x', v', H' - H) of one leapfrog"""
-    x1, v1 = leapfrog(x, v, phi, beta, kappa, eps, nleapfrog, True, tol)
-    return x1, v1, hamiltonian(x1, v1, phi, beta, kappa, True, tol_h) - hamiltonian(x, v, phi, beta, kappa, True, tol_h)
 
 
 def measure(lattices=None, nb=3, npf=3):

@@ -93,33 +93,29 @@ def _bc(a):
     return a.reshape(a.shape + (1,) * 6)
 
 
-def cgnr(x, b, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
-    """M psi = b by CG on M^H M with the true residual r = b - M psi carried along; per system alpha = |z|^2 / |M p|^2.
-    Convergence |r|^2 <= tol^2 |b|^2 is looked at every check_every iterations (and at 0 and max_iter); a converged
-    system takes alpha = beta = 0 from then on.  Returns (psi, info), info = {'iters', 'residual', 'converged'} each
-    [nb, nrhs]; residual is |b - M psi| / |b| recomputed at the end (0 for b = 0)."""
-    squeeze = b.ndim == 7
-    if squeeze:
-        b = b[:, None]
+def cgnr_op(op, b, bb, tol=1e-10, max_iter=1000, check_every=10):
+    """A psi = b by CG on A^H A with the true residual r = b - A psi carried along, op(p, dagger) the operator; per
+    system alpha = |z|^2 / |A p|^2.  Convergence |r|^2 <= tol^2 bb (bb [nb, nrhs], the reference norm) is looked at every
+    check_every iterations (and at 0 and max_iter); a converged system takes alpha = beta = 0 from then on.  Returns
+    (psi, iters, done)."""
     psi = np.zeros_like(b)
     r = b.copy()
-    bb = norm2(b)
-    z = wilson(x, r, kappa, True, antiperiodic_t)
+    z = op(r, True)
     p = z.copy()
     zz = norm2(z)
-    rr = bb.copy()
-    done = rr <= tol * tol * bb
+    rr = norm2(b)
+    done = bb <= tol * tol * bb
     iters = np.where(done, 0, max_iter)
     k = 0
     while k < max_iter and not done.all():
-        q = wilson(x, p, kappa, False, antiperiodic_t)
+        q = op(p, False)
         qq = norm2(q)
         live = ~done & (qq > 0)
         alpha = np.where(live, zz / np.where(live, qq, 1.0), 0.0)
         psi = psi + _bc(alpha) * p
         r = r - _bc(alpha) * q
         rr = norm2(r)
-        z = wilson(x, r, kappa, True, antiperiodic_t)
+        z = op(r, True)
         zn = norm2(z)
         live = ~done & (zz > 0)
         beta = np.where(live, zn / np.where(live, zz, 1.0), 0.0)
@@ -130,6 +126,18 @@ def cgnr(x, b, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=T
             now = ~done & (rr <= tol * tol * bb)
             iters = np.where(now, k, iters)
             done = done | now
+    return psi, iters, done
+
+
+def cgnr(x, b, kappa, tol=1e-10, max_iter=1000, check_every=10, antiperiodic_t=True):
+    """M psi = b by `cgnr_op` on M, stopping on |r|^2 <= tol^2 |b|^2; b with or without the nrhs axis.  Returns (psi,
+    info), info = {'iters', 'residual', 'converged'} each [nb, nrhs]; residual is |b - M psi| / |b| recomputed at the
+    end (0 for b = 0)."""
+    squeeze = b.ndim == 7
+    if squeeze:
+        b = b[:, None]
+    bb = norm2(b)
+    psi, iters, done = cgnr_op(lambda p, d: wilson(x, p, kappa, d, antiperiodic_t), b, bb, tol, max_iter, check_every)
     res = np.sqrt(norm2(b - wilson(x, psi, kappa, False, antiperiodic_t)) / np.where(bb > 0, bb, 1.0))
     info = {'iters': iters, 'residual': res, 'converged': done}
     return (psi[:, 0] if squeeze else psi), info

@@ -108,8 +108,8 @@ def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=F
 
     def kick(xn, vn, step):
         timed('gauge kick', lambda: ops.su3_force_kick_n(xn, beta, -step, vn, L))
-        solve = lat._schur_force_fields_n if even_odd else lat.wilson_solve_normal_n
-        X, Y, info = timed('solves', lambda: solve(xn, phin, kappa, **hmc._solve_kw(hmc.tol_md)))
+        X, Y, info = timed('solves', lambda: lat._force_fields_n('pseudofermion_force', xn, phin, kappa, even_odd,
+                                                                 **hmc._solve_kw(hmc.tol_md)))
         timed('fermion force', lambda: ops.su3_wilson_force_n(xn, X, Y, kappa, L, True, coef=-step, f_in=vn, out=vn))
         iters.append(info['iters'])
 
