@@ -469,6 +469,37 @@ int l2q_su3_wilson_force(const void* xn, const void* X, const void* Y, const voi
  * V of 2^31 or more; a or b not finite; flags outside 0..3; parity not 0 or 1.  L2Q_ESHAPE: an odd extent. */
 int l2q_su3_wilson_hop_eo(const void* xn, const void* src, const void* aux, void* out, double* norm_part, double a,
                           double b, int flags, int parity, int nb, int nrhs, int T, int X, int Y, int Z, void* stream);
+/* csrc/su3_wilson_f32.hip.  The single-precision kernels of the mixed-precision even-odd solves (defect correction: the
+ * inner CG on Mhat runs on these, the outer loop recomputes the true residual with the fp64 entries above).
+ * l2q_su3_links_demote_eo: the fp32, parity-ordered copy of the native links xn[nb][4][9][V] complex128,
+ *   x32[nb][parity][4][9][V/2] float2: entry h of parity p is the link at the site of parity p of the pair (2h, 2h + 1),
+ * every entry rounded to float once.  One thread per (chain, half-site), plain vector loads and stores.  L2Q_EINVAL: a
+ * null pointer; x32 aliasing xn; a non-positive size.  L2Q_ESHAPE: an odd extent. */
+int l2q_su3_links_demote_eo(const void* xn, void* x32, int nb, int T, int X, int Y, int Z, void* stream);
+/* out = b aux + a H src on the sites of `parity`: l2q_su3_wilson_hop_eo on float2 half fields [nb][nrhs][12][V/2] and the
+ * link copy x32 of l2q_su3_links_demote_eo, with its semantics and argument checks (aux and norm_part may be null, out
+ * may be aux, an extent of 2 is legal; the same gamma basis, seam sign and flags).  The forward link of a site is entry h
+ * of this parity's block of x32, the backward link entry s' >> 1 of the other parity's: every link load is contiguous
+ * across lanes.  Arithmetic in float (a and b are rounded to float); one thread per (system, half-site), 8 B per lane
+ * and plane; algorithmic traffic per (system, half-site) 96 B of output, 96 B of aux if given, 96 B of src and 576 B of
+ * links, which the nrhs systems of a chain share.  norm_part: [nb][nrhs][ceil((V/2) / 256)] doubles; every thread adds
+ * its 24 squares in double and the block partial is the fixed tree of the fp64 kernels: a system's partials are the same
+ * bits whatever else the batch holds.  Errors as l2q_su3_wilson_hop_eo. */
+int l2q_su3_wilson_hop_eo_f32(const void* x32, const void* src, const void* aux, void* out, double* norm_part, double a,
+                              double b, int flags, int parity, int nb, int nrhs, int T, int X, int Y, int Z,
+                              void* stream);
+/* l2q_su3_spinor_cg_update and l2q_su3_spinor_xpay on float2 fields: alpha and beta stay device arrays [nsys] of doubles
+ * and are rounded to float in the kernel; rr_part stays double, every thread adding its squares in double.  Errors as
+ * there. */
+int l2q_su3_spinor_cg_update_f32(void* x, void* r, const void* p, const void* q, const double* alpha, double* rr_part,
+                                 long nsys, long V, void* stream);
+int l2q_su3_spinor_xpay_f32(void* p, const void* z, const double* beta, long nsys, long V, void* stream);
+/* out32 = scale[s] in64: nsys systems of 12 V entries, complex128 to float2, scale a device array [nsys] of doubles; the
+ * product in double, rounded to float once.  L2Q_EINVAL: a null pointer; out32 aliasing in64; a size as above. */
+int l2q_su3_spinor_demote(const void* in64, const double* scale, void* out32, long nsys, long V, void* stream);
+/* x64 += scale[s] e32, product and sum in double; a system with scale[s] = 0 is not written and keeps its bits.
+ * L2Q_EINVAL: a null pointer; x64 aliasing e32; a size as above. */
+int l2q_su3_spinor_promote_axpy(void* x64, const void* e32, const double* scale, long nsys, long V, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

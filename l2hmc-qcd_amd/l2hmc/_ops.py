@@ -792,6 +792,126 @@ def su3_wilson_hop_eo_n(xn: torch.Tensor, src: torch.Tensor, lat: Sequence[int],
     return out if part is None else (out, part)
 
 
+# the single-precision kernels of the mixed-precision even-odd solves (csrc/su3_wilson_f32.hip)
+C64 = torch.complex64
+
+
+def _spinor_check_f32(what: str, name: str, t: torch.Tensor, shape) -> None:
+    if t.dtype != C64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{what}: {name} must be contiguous complex64 {list(shape)}, got {t.dtype} {list(t.shape)}')
+
+
+def _system_scalars(what: str, name: str, t: torch.Tensor, nb: int, nrhs: int) -> None:
+    if t.dtype != torch.float64 or t.numel() != nb * nrhs or not t.is_contiguous():
+        raise ValueError(f'{what}: {name} must be contiguous float64 [{nb}, {nrhs}]')
+
+
+def su3_links_demote_eo_n(xn: torch.Tensor, lat: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the fp32, parity-ordered copy of the native links xn[nb, 4, 9, V] complex128: x32[nb, 2, 4, 9, V/2] complex64,
+    entry h of parity p the link at the site of that parity of the pair (2h, 2h + 1) (see l2q.h).  Even extents."""
+    T, X, Y, Z = _even_lattice('su3_links_demote_eo_n', lat)
+    V = T * X * Y * Z
+    if xn.dtype != C128 or xn.dim() != 4 or tuple(xn.shape[1:]) != (4, 9, V) or not xn.is_contiguous():
+        raise ValueError(f'su3_links_demote_eo_n: xn must be contiguous complex128 [nb, 4, 9, {V}], got {xn.dtype} '
+                         f'{list(xn.shape)}')
+    shape = (xn.shape[0], 2, 4, 9, V // 2)
+    if out is None:
+        out = torch.empty(shape, dtype=C64, device=xn.device)
+    elif out.dtype != C64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f'su3_links_demote_eo_n: out must be contiguous complex64 {list(shape)}, got {out.dtype} '
+                         f'{list(out.shape)}')
+    N.call('l2q_su3_links_demote_eo', xn, out, xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_wilson_hop_eo_f32_n(x32: torch.Tensor, src: torch.Tensor, lat: Sequence[int], parity: int,
+                            dagger: bool = False, antiperiodic_t: bool = True, a: float = 1.0,
+                            aux: Optional[torch.Tensor] = None, b: float = 0.0, out: Optional[torch.Tensor] = None,
+                            norm: bool = False):
+    """`su3_wilson_hop_eo_n` in single precision: complex64 half fields [nb, nrhs, 12, V/2] on the link copy x32[nb, 2,
+    4, 9, V/2] of `su3_links_demote_eo_n`.  The norm partials stay float64."""
+    T, X, Y, Z = _even_lattice('su3_wilson_hop_eo_f32_n', lat)
+    Vh = T * X * Y * Z // 2
+    if parity not in (0, 1):
+        raise ValueError(f'su3_wilson_hop_eo_f32_n: parity must be 0 or 1, got {parity!r}')
+    if x32.dtype != C64 or x32.dim() != 5 or tuple(x32.shape[1:]) != (2, 4, 9, Vh) or not x32.is_contiguous():
+        raise ValueError(f'su3_wilson_hop_eo_f32_n: x32 must be contiguous complex64 [nb, 2, 4, 9, {Vh}], got '
+                         f'{x32.dtype} {list(x32.shape)}')
+    if src.dim() != 4 or src.shape[0] != x32.shape[0] or src.shape[1] < 1 or src.shape[2] != 12 or src.shape[3] != Vh:
+        raise ValueError(f'su3_wilson_hop_eo_f32_n: need a half field src [nb, nrhs, 12, V/2] on x32 {list(x32.shape)}, '
+                         f'got {list(src.shape)}')
+    _spinor_check_f32('su3_wilson_hop_eo_f32_n', 'src', src, src.shape)
+    if aux is not None:
+        _spinor_check_f32('su3_wilson_hop_eo_f32_n', 'aux', aux, src.shape)
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _spinor_check_f32('su3_wilson_hop_eo_f32_n', 'out', out, src.shape)
+    nb, nrhs = src.shape[:2]
+    part = _norm_part('su3_wilson_hop_eo_f32_n', norm, nb, nrhs, lambda: -(-Vh // 256), src.device)
+    N.call('l2q_su3_wilson_hop_eo_f32', x32, src, aux, out, part, float(a), float(b),
+           int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1), int(parity), nb, nrhs, T, X, Y, Z)
+    return out if part is None else (out, part)
+
+
+def su3_spinor_cg_update_f32_(x: torch.Tensor, r: torch.Tensor, p: torch.Tensor, q: torch.Tensor, alpha: torch.Tensor,
+                              part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`su3_spinor_cg_update_` on complex64 fields; alpha [nb, nrhs] and the partial sums of |r|^2 stay float64"""
+    if x.dim() != 4 or x.shape[2] != 12:
+        raise ValueError(f'su3_spinor_cg_update_f32_: need fields [nb, nrhs, 12, V], got {list(x.shape)}')
+    for name, t in (('x', x), ('r', r), ('p', p), ('q', q)):
+        _spinor_check_f32('su3_spinor_cg_update_f32_', name, t, x.shape)
+    nb, nrhs, _, V = x.shape
+    _system_scalars('su3_spinor_cg_update_f32_', 'alpha', alpha, nb, nrhs)
+    parts = -(-V // 256)
+    if part is None:
+        part = torch.empty((nb, nrhs, parts), dtype=torch.float64, device=x.device)
+    elif part.dtype != torch.float64 or tuple(part.shape) != (nb, nrhs, parts) or not part.is_contiguous():
+        raise ValueError(f'su3_spinor_cg_update_f32_: part must be contiguous float64 {[nb, nrhs, parts]}')
+    N.call('l2q_su3_spinor_cg_update_f32', x, r, p, q, alpha, part, nb * nrhs, V)
+    return part
+
+
+def su3_spinor_xpay_f32_(p: torch.Tensor, z: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """`su3_spinor_xpay_` on complex64 fields; beta [nb, nrhs] stays float64"""
+    if p.dim() != 4 or p.shape[2] != 12:
+        raise ValueError(f'su3_spinor_xpay_f32_: need fields [nb, nrhs, 12, V], got {list(p.shape)}')
+    _spinor_check_f32('su3_spinor_xpay_f32_', 'p', p, p.shape)
+    _spinor_check_f32('su3_spinor_xpay_f32_', 'z', z, p.shape)
+    nb, nrhs, _, V = p.shape
+    _system_scalars('su3_spinor_xpay_f32_', 'beta', beta, nb, nrhs)
+    N.call('l2q_su3_spinor_xpay_f32', p, z, beta, nb * nrhs, V)
+    return p
+
+
+def su3_spinor_demote(f64: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out32 = scale_s f64: a complex128 field [nb, nrhs, 12, V] times its system's float64 scale [nb, nrhs], rounded to
+    complex64 once; out None = a new field"""
+    if f64.dim() != 4 or f64.shape[2] != 12:
+        raise ValueError(f'su3_spinor_demote: need a field [nb, nrhs, 12, V], got {list(f64.shape)}')
+    _spinor_check('su3_spinor_demote', 'f64', f64, f64.shape)
+    nb, nrhs, _, V = f64.shape
+    _system_scalars('su3_spinor_demote', 'scale', scale, nb, nrhs)
+    if out is None:
+        out = torch.empty(f64.shape, dtype=C64, device=f64.device)
+    else:
+        _spinor_check_f32('su3_spinor_demote', 'out', out, f64.shape)
+    N.call('l2q_su3_spinor_demote', f64, scale, out, nb * nrhs, V)
+    return out
+
+
+def su3_spinor_promote_axpy_(x64: torch.Tensor, e32: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x64 += scale_s e32 in place, product and sum in float64; a system with scale_s = 0 keeps its bits"""
+    if x64.dim() != 4 or x64.shape[2] != 12:
+        raise ValueError(f'su3_spinor_promote_axpy_: need a field [nb, nrhs, 12, V], got {list(x64.shape)}')
+    _spinor_check('su3_spinor_promote_axpy_', 'x64', x64, x64.shape)
+    _spinor_check_f32('su3_spinor_promote_axpy_', 'e32', e32, x64.shape)
+    nb, nrhs, _, V = x64.shape
+    _system_scalars('su3_spinor_promote_axpy_', 'scale', scale, nb, nrhs)
+    N.call('l2q_su3_spinor_promote_axpy', x64, e32, scale, nb * nrhs, V)
+    return x64
+
+
 def sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
     partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""

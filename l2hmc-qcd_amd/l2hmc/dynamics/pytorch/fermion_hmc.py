@@ -13,7 +13,7 @@ import torch
 
 from l2hmc import _ops as ops
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3
-from l2hmc.lattice.su3.pytorch.wilson import draw
+from l2hmc.lattice.su3.pytorch.wilson import MIXED_INNER_TOL, MIXED_MAX_INNER, MIXED_MAX_OUTER, _MixedSolve, draw
 
 Tensor = torch.Tensor
 
@@ -142,3 +142,19 @@ class WilsonHMCEvenOdd(WilsonHMC):
     noise is drawn with that shape."""
 
     even_odd = True
+
+
+class WilsonHMCMixed(WilsonHMCEvenOdd):
+    """`WilsonHMCEvenOdd` with every solve in mixed precision (`wilson_solve_schur_normal_mixed_n`: fp32 inner CG, fp64
+    defect correction to the same stopping test): the same trajectory, draw order and metrics.  `inner_tol` and
+    `max_inner` are those of the mixed solves (None: their defaults); 'cg_iters_md' and 'cg_iters_h' count the summed
+    inner iterations."""
+
+    def __init__(self, *args, inner_tol: Optional[float] = None, max_inner: Optional[int] = None, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.mixed_kw = {k: v for k, v in (('inner_tol', inner_tol), ('max_inner', max_inner)) if v is not None}
+        _MixedSolve.check_args('WilsonHMCMixed', self.mixed_kw.get('inner_tol', MIXED_INNER_TOL),
+                               self.mixed_kw.get('max_inner', MIXED_MAX_INNER), MIXED_MAX_OUTER)
+
+    def _solve_kw(self, tol: float) -> dict:
+        return dict(super()._solve_kw(tol), mixed=True, **self.mixed_kw)

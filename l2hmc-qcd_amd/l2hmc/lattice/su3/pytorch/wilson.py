@@ -1,6 +1,8 @@
-"""The host side of the Wilson fermions on `LatticeSU3` (kernels: csrc/su3_wilson.hip, csrc/su3_wilson_force.hip): the
-mixin ``WilsonFermions`` with the operator, the two solvers on one CG loop (``_CG``), the propagator and the
-pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the random-draw rule of the fermion layer."""
+"""The host side of the Wilson fermions on `LatticeSU3` (kernels: csrc/su3_wilson.hip, csrc/su3_wilson_eo.hip,
+csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip): the mixin ``WilsonFermions`` with the operator, the two solvers on
+one CG loop (``_CG``), their even-odd and mixed-precision forms (``_MixedSolve``: fp64 defect correction around the same
+loop on fp32 fields), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
+random-draw rule of the fermion layer."""
 from __future__ import annotations
 
 from typing import Optional
@@ -52,10 +54,11 @@ def ratio(live: Tensor, num: Tensor, den: Tensor) -> Tensor:
     return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).contiguous()
 
 
-def _norm2(f: Tensor, other: Tensor, spare: Tensor, zero: Tensor, part: Optional[Tensor] = None) -> Tensor:
+def _norm2(f: Tensor, other: Tensor, spare: Tensor, zero: Tensor, part: Optional[Tensor] = None, update=None) -> Tensor:
     """|f|^2 per system [nb, nrhs] by the update kernel at alpha = 0 (`zero`): it leaves spare (its x) and f (its r)
-    as they are and |f|^2 in its partial sums; `other` is the p and q it reads"""
-    return ops.sum_parts(ops.su3_spinor_cg_update_(spare, f, other, other, zero, part))
+    as they are and |f|^2 in its partial sums; `other` is the p and q it reads.  `update`: the kernel wrapper, that of
+    the complex128 fields unless given"""
+    return ops.sum_parts((update or ops.su3_spinor_cg_update_)(spare, f, other, other, zero, part))
 
 
 def _residual(r: Tensor, spare: Tensor, p: Tensor, ax: Tensor, bb: Tensor, part: Optional[Tensor] = None) -> Tensor:
@@ -97,13 +100,32 @@ class _SchurOp:
         self.apply = apply
 
 
+class _SchurOpF32:
+    """`_SchurOp` in single precision: Mhat on complex64 even half fields, two `su3_wilson_hop_eo_f32_n` on the fp32,
+    parity-ordered link copy x32 -- made here from xn, once per solve, unless given.  The fused norm stays float64."""
+
+    def __init__(self, xn: Optional[Tensor], k: float, L, antiperiodic_t, like: Tensor, x32: Optional[Tensor] = None):
+        self.sites = like.shape[3]
+        self.x32 = x32 = ops.su3_links_demote_eo_n(xn, L) if x32 is None else x32
+        part = torch.empty((*like.shape[:2], -(-self.sites // 256)), dtype=torch.float64, device=like.device)
+        odd = torch.empty_like(like)
+
+        def apply(src, dst, dagger, norm=True):
+            ops.su3_wilson_hop_eo_f32_n(x32, src, L, 1, dagger, antiperiodic_t, out=odd)
+            ops.su3_wilson_hop_eo_f32_n(x32, odd, L, 0, dagger, antiperiodic_t, a=-k * k, aux=src, b=1.0, out=dst,
+                                        norm=part if norm else False)
+            return ops.sum_parts(part) if norm else None
+        self.apply = apply
+
+
 class _CG:
     """What the solvers share: a batched CG from x = 0 for every system (chain, rhs) of the field b [nb, nrhs, 12,
     sites] at once, on the operator `op` (`_WilsonOp` on full fields, `_SchurOp` on even half fields: its apply(src,
     dst, dagger, norm) and the site count of its fields).  It owns the argument checks, the workspace (x, r, q, z, the
     partial sums rpart of the updates), the loop with its look at |r|^2 <= tol^2 bb every check_every iterations (and
     after the last), and the recomputed residual; bb, the reference norm of the stopping test, is |b|^2 unless given (the
-    even-odd solve gives |b|^2 of the full right-hand side).  `cgnr` and `normal` are the two loop bodies."""
+    even-odd solve gives |b|^2 of the full right-hand side).  `cgnr` and `normal` are the two loop bodies.  On complex64
+    fields (the inner solves of `_MixedSolve`, on a `_SchurOpF32`) the same loops run on the fp32 update and xpay."""
 
     @staticmethod
     def check_args(what: str, tol, max_iter, check_every) -> None:
@@ -117,36 +139,43 @@ class _CG:
         assert b.shape[3] == op.sites
         self.b, self.single, self.apply = b, single, op.apply
         self.tol2, self.max_iter, self.check_every = float(tol) ** 2, int(max_iter), int(check_every)
+        f32 = b.dtype == torch.complex64
+        self.update = ops.su3_spinor_cg_update_f32_ if f32 else ops.su3_spinor_cg_update_
+        self.xpay = ops.su3_spinor_xpay_f32_ if f32 else ops.su3_spinor_xpay_
         self.x, self.r, self.q, self.z = torch.zeros_like(b), b.clone(), torch.empty_like(b), torch.empty_like(b)
         self.rpart = torch.empty((*b.shape[:2], -(-op.sites // 256)), dtype=torch.float64, device=b.device)
         self.zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
-        self.bb0 = _norm2(self.r, b, self.x, self.zero, self.rpart)                                       # |b|^2
+        self.bb0 = _norm2(self.r, b, self.x, self.zero, self.rpart, self.update)                          # |b|^2
         self.bb = self.bb0 if bb is None else bb
 
-    def cgnr(self) -> None:
-        """A x = b by CG on A^H A with the true residual r = b - A x carried along; leaves x, and A x in q"""
+    def cgnr(self, final: bool = True) -> None:
+        """A x = b by CG on A^H A with the true residual r = b - A x carried along; leaves x, and (final) A x in q"""
         psi, r, q, z, apply = self.x, self.r, self.q, self.z, self.apply
         zz = apply(r, z, True)
         self.p = p = z.clone()
         for active in self.iterations(lambda: ops.sum_parts(self.rpart)):      # |r|^2 is summed at a check only
             qq = apply(p, q, False)
-            ops.su3_spinor_cg_update_(psi, r, p, q, ratio(active, zz, qq), self.rpart)
+            self.update(psi, r, p, q, ratio(active, zz, qq), self.rpart)
             zn = apply(r, z, True)
-            ops.su3_spinor_xpay_(p, z, ratio(active, zn, zz))
+            self.xpay(p, z, ratio(active, zn, zz))
             zz = zn
-        apply(psi, q, False)
+        if final:
+            apply(psi, q, False)
 
-    def normal(self) -> tuple[Tensor, Tensor]:
-        """A^H A X = b by CG: (Y = A X, |Y|^2 from the fused norm); leaves X in x and A^H A X in z"""
+    def normal(self, final: bool = True) -> Optional[tuple[Tensor, Tensor]]:
+        """A^H A X = b by CG: (Y = A X, |Y|^2 from the fused norm); leaves X in x and A^H A X in z.  Without final the
+        loop only: X in x, nothing returned"""
         X, r, q, z, apply = self.x, self.r, self.q, self.z, self.apply
         self.p = p = self.b.clone()
         rr = self.bb0
         for active in self.iterations(lambda: rr):                             # |r|^2 is carried from every update
             qq = apply(p, q, False)
             apply(q, z, True, norm=False)
-            rn = ops.sum_parts(ops.su3_spinor_cg_update_(X, r, p, z, ratio(active, rr, qq), self.rpart))
-            ops.su3_spinor_xpay_(p, r, ratio(active, rn, rr))
+            rn = ops.sum_parts(self.update(X, r, p, z, ratio(active, rr, qq), self.rpart))
+            self.xpay(p, r, ratio(active, rn, rr))
             rr = rn
+        if not final:
+            return None
         Y = torch.empty_like(X)
         action = apply(X, Y, False)
         apply(Y, z, True, norm=False)
@@ -175,6 +204,85 @@ class _CG:
     def info(self, res: Tensor) -> dict:
         """the info every solver returns, `res` its recomputed residual; never raises on non-convergence"""
         return {'iters': self.iters, 'converged': ~self.active, 'residual': res}
+
+
+# the mixed-precision solves: defaults and the margin of the relaxed inner target
+MIXED_INNER_TOL = 1e-4       # chosen from the iteration and timing tables of profiles/su3_wilson_mixed.md
+MIXED_MAX_INNER = 500
+MIXED_MAX_OUTER = 30
+MIXED_SAFETY = 0.5           # the last cycle aims at half of what the outer test still needs, so that the rounding of
+                             # the fp32 correction (relative ~1e-7 of |r|) does not cost one more cycle
+
+
+class _MixedSolve:
+    """Defect correction on the even-odd Schur complement (Mhat: `form` 'cgnr', Mhat^H Mhat: 'normal'): the outer loop
+    in fp64 on `op64` (a `_SchurOp`) recomputes the true residual r = b - A x, tests |r|^2 <= tol^2 bb per system,
+    hands r / |r| of the live systems to an inner fp32 `_CG` from zero on `op32` (a `_SchurOpF32`) and adds x += |r| e.
+    A system found converged gets the scale 0 and is frozen from then on: its inner right-hand side is zero, which the
+    inner `_CG` leaves alone, and `su3_spinor_promote_axpy_` does not touch it, so a system's bits do not depend on the
+    batch (as long as no system of the batch runs into max_iter: the budget left to a cycle is that of the system that
+    has spent most).  The inner target per system is inner_tol relaxed to MIXED_SAFETY * tol sqrt(bb) / |r|, handed to
+    the inner `_CG` through its bb argument (its test is |r_in|^2 <= inner_tol^2 bb_in, bb_in = (target / inner_tol)^2).
+    Stops when nothing is live, when the summed inner iterations reach max_iter, or after max_outer cycles; never raises
+    on non-convergence."""
+
+    @staticmethod
+    def check_args(what: str, inner_tol, max_inner, max_outer) -> None:
+        ok = isinstance(inner_tol, (int, float, np.floating)) and not isinstance(inner_tol, bool) and 0.0 < inner_tol < 1.0
+        for v, lo in ((max_inner, 1), (max_outer, 0)):
+            ok = ok and not isinstance(v, bool) and isinstance(v, (int, np.integer)) and v >= lo
+        if not ok:
+            raise ValueError(f'LatticeSU3.{what}: need 0 < inner_tol < 1, an integer max_inner >= 1 and max_outer >= 0, '
+                             f'got {inner_tol!r}, {max_inner!r}, {max_outer!r}')
+
+    def __init__(self, what: str, form: str, b: Tensor, op64, op32, tol, max_iter, check_every, inner_tol, max_inner,
+                 max_outer, bb: Optional[Tensor] = None):
+        _CG.check_args(what, tol, max_iter, check_every)
+        self.check_args(what, inner_tol, max_inner, max_outer)
+        assert form in ('cgnr', 'normal') and b.shape[3] == op64.sites == op32.sites
+        tol2, inner_tol = float(tol) ** 2, float(inner_tol)
+        apply = op64.apply
+        shape = b.shape[:2]
+        self.x = x = torch.zeros_like(b)
+        r, ax, spare = b.clone(), torch.empty_like(b), torch.zeros_like(b)
+        mid = torch.empty_like(b) if form == 'normal' else None
+        part = torch.empty((*shape, -(-op64.sites // 256)), dtype=torch.float64, device=b.device)
+        zero = torch.zeros(shape, dtype=torch.float64, device=b.device)
+        one = torch.ones_like(zero)
+        r32 = torch.empty(b.shape, dtype=torch.complex64, device=b.device)
+        rr = _norm2(r, b, spare, zero, part)                                                # |b|^2
+        self.bb = bb = rr if bb is None else bb
+        live = ~(bb <= tol2 * bb)
+        self.iters = torch.zeros(shape, dtype=torch.int64, device=b.device)
+        self.outer = torch.zeros_like(self.iters)
+        cycles = 0
+        while True:
+            live = live & ~(rr <= tol2 * bb)
+            spent = int(torch.where(live, self.iters, 0).max())
+            if not bool(live.any()) or cycles >= int(max_outer) or spent >= int(max_iter):
+                break
+            rn = torch.sqrt(torch.where(live, rr, one))
+            ops.su3_spinor_demote(r, torch.where(live, 1.0 / rn, zero).contiguous(), out=r32)
+            target = torch.clamp(MIXED_SAFETY * float(tol) * torch.sqrt(bb) / rn, min=inner_tol)
+            inner = _CG(what, r32, False, op32, inner_tol, min(int(max_inner), int(max_iter) - spent), check_every,
+                        bb=torch.where(live, (target / inner_tol) ** 2, zero))
+            inner.cgnr(final=False) if form == 'cgnr' else inner.normal(final=False)
+            ops.su3_spinor_promote_axpy_(x, inner.x, torch.where(live, rn, zero).contiguous())
+            self.iters = self.iters + torch.where(live, inner.iters, 0)
+            self.outer = self.outer + live.to(torch.int64)
+            cycles += 1
+            if form == 'cgnr':                                                              # r = b - Mhat x
+                apply(x, ax, False, norm=False)
+            else:                                                                           # r = b - Mhat^H Mhat x
+                apply(x, mid, False, norm=False)
+                apply(mid, ax, True, norm=False)
+            r.copy_(b)
+            rr = ops.sum_parts(ops.su3_spinor_cg_update_(spare, r, ax, ax, one, part))
+        self.live = live
+        self.residual = torch.sqrt(rr / torch.where(bb > 0, bb, one))
+
+    def info(self) -> dict:
+        return {'iters': self.iters, 'outer': self.outer, 'converged': ~self.live, 'residual': self.residual}
 
 
 class WilsonFermions:
@@ -312,15 +420,100 @@ class WilsonFermions:
         psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
         return (psi[:, 0] if single else psi), info
 
+    # ------------------------------------------------------------ mixed-precision even-odd solves (defect correction)
+    @staticmethod
+    def _pop_mixed(what: str, solve_kwargs: dict, even_odd: bool) -> Optional[dict]:
+        """the mixed-precision keywords popped from solve_kwargs: None without mixed=True, else the dict of inner_tol,
+        max_inner, max_outer that were given.  ValueError: mixed without even_odd, or the others without mixed."""
+        mixed = bool(solve_kwargs.pop('mixed', False))
+        given = {k: solve_kwargs.pop(k) for k in ('inner_tol', 'max_inner', 'max_outer') if k in solve_kwargs}
+        if mixed and not even_odd:
+            raise ValueError(f'LatticeSU3.{what}: mixed=True needs even_odd=True: the mixed-precision solves are those '
+                             f'of the even-odd Schur complement')
+        if given and not mixed:
+            raise ValueError(f'LatticeSU3.{what}: {sorted(given)} are keywords of the mixed-precision solves: pass '
+                             f'mixed=True (with even_odd=True)')
+        return given if mixed else None
+
+    def wilson_solve_eo_mixed_n(self, xn: Tensor, bn: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                                check_every: int = 10, antiperiodic_t: bool = True, inner_tol: float = MIXED_INNER_TOL,
+                                max_inner: int = MIXED_MAX_INNER, max_outer: int = MIXED_MAX_OUTER) -> tuple[Tensor, dict]:
+        """`wilson_solve_eo_n` in mixed precision, by defect correction: the outer loop recomputes the true residual
+        rhat = bhat - Mhat psi_e with the fp64 kernels and stops on the test of `wilson_solve_eo_n`, |rhat|^2 <= tol^2
+        |b|^2 (|b|^2 of the full right-hand side), so the answer meets the same double-precision test; each cycle solves
+        Mhat e = rhat / |rhat| from zero by the same CGNR loop on the fp32 kernels (csrc/su3_wilson_f32.hip, on an fp32,
+        parity-ordered copy of the links made once per solve) to the relative target max(inner_tol, 0.5 tol |b| /
+        |rhat|), at most max_inner iterations, and adds psi_e += |rhat| e in fp64.  It stops when every system has
+        converged, when a system's summed inner iterations reach max_iter, or after max_outer cycles; never raises on
+        non-convergence; b = 0 gives psi = 0.  A converged system is frozen: its bits do not depend on the batch.
+        info, each [nb, nrhs]: 'iters' (the summed inner iterations), 'outer' (cycles), 'converged', 'residual' (the
+        last |rhat| / |b|, recomputed in fp64: with psi_o reconstructed it is |b - M psi| / |b|)."""
+        k = self._wilson_checks('wilson_solve_eo_mixed', kappa, xn, bn)
+        _CG.check_args('wilson_solve_eo_mixed', tol, max_iter, check_every)
+        _MixedSolve.check_args('wilson_solve_eo_mixed', inner_tol, max_inner, max_outer)
+        L = self._eo_lattice('wilson_solve_eo_mixed')
+        b, single = self._spinor_native('wilson_solve_eo_mixed', xn, bn)
+        be, bo = ops.su3_spinor_split_eo(b, L)
+        zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
+        spare = torch.zeros_like(be)
+        bb = _norm2(be, bo, spare, zero) + _norm2(bo, be, spare, zero)                 # |b_e|^2 + |b_o|^2
+        bhat = ops.su3_wilson_hop_eo_n(xn, bo, L, 0, False, antiperiodic_t, a=k, aux=be, b=1.0)
+        like32 = torch.empty(bhat.shape, dtype=torch.complex64, device=bhat.device)
+        ms = _MixedSolve('wilson_solve_eo_mixed', 'cgnr', bhat, _SchurOp(xn, k, L, antiperiodic_t, bhat),
+                         _SchurOpF32(xn, k, L, antiperiodic_t, like32), tol, max_iter, check_every, inner_tol, max_inner,
+                         max_outer, bb=bb)
+        psio = ops.su3_wilson_hop_eo_n(xn, ms.x, L, 1, False, antiperiodic_t, a=k, aux=bo, b=1.0)
+        psi = ops.su3_spinor_merge_eo(ms.x, psio, L)
+        return (psi[:, 0] if single else psi), ms.info()
+
+    def wilson_solve_eo_mixed(self, x: Tensor, b: Tensor, kappa: float, tol: float = 1e-10, max_iter: int = 1000,
+                              check_every: int = 10, antiperiodic_t: bool = True, inner_tol: float = MIXED_INNER_TOL,
+                              max_inner: int = MIXED_MAX_INNER, max_outer: int = MIXED_MAX_OUTER) -> tuple[Tensor, dict]:
+        """`wilson_solve_eo_mixed_n` in the reference layout"""
+        self._wilson_checks('wilson_solve_eo_mixed', kappa, x, b)
+        self._eo_lattice('wilson_solve_eo_mixed')
+        bn, single = self._spinor_reference('wilson_solve_eo_mixed', x, b)
+        psin, info = self.wilson_solve_eo_mixed_n(self.pack(x), bn, kappa, tol, max_iter, check_every, antiperiodic_t,
+                                                  inner_tol, max_inner, max_outer)
+        psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
+        return (psi[:, 0] if single else psi), info
+
+    def wilson_solve_schur_normal_mixed_n(self, xn: Tensor, phi_e: Tensor, kappa: float, tol: float = 1e-10,
+                                          max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                                          inner_tol: float = MIXED_INNER_TOL, max_inner: int = MIXED_MAX_INNER,
+                                          max_outer: int = MIXED_MAX_OUTER) -> tuple[Tensor, Tensor, dict]:
+        """`wilson_solve_schur_normal_n` in mixed precision, by the defect correction of `wilson_solve_eo_mixed_n` on
+        Mhat^H Mhat: the outer loop recomputes r = phi_e - Mhat^H Mhat X_e in fp64 and stops on |r|^2 <= tol^2 |phi_e|^2,
+        the inner cycles are the normal-equation CG on the fp32 kernels.  After the loop Y_e = Mhat X_e and |Y_e|^2 come
+        from the fp64 operator with its fused norm, as there.  Returns (X_e, Y_e, info), info as in
+        `wilson_solve_eo_mixed_n` plus 'action' = |Y_e|^2."""
+        k = self._pf_checks('wilson_solve_schur_normal_mixed', kappa, xn, phi_e)
+        _CG.check_args('wilson_solve_schur_normal_mixed', tol, max_iter, check_every)
+        _MixedSolve.check_args('wilson_solve_schur_normal_mixed', inner_tol, max_inner, max_outer)
+        L = self._eo_lattice('wilson_solve_schur_normal_mixed')
+        b, single = self._spinor_native('wilson_solve_schur_normal_mixed', xn, phi_e, half=True)
+        op = _SchurOp(xn, k, L, antiperiodic_t, b)
+        like32 = torch.empty(b.shape, dtype=torch.complex64, device=b.device)
+        ms = _MixedSolve('wilson_solve_schur_normal_mixed', 'normal', b, op, _SchurOpF32(xn, k, L, antiperiodic_t, like32),
+                         tol, max_iter, check_every, inner_tol, max_inner, max_outer)
+        X, Y = ms.x, torch.empty_like(ms.x)
+        info = {**ms.info(), 'action': op.apply(X, Y, False)}
+        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
+
     def quark_propagator_n(self, xn: Tensor, kappa: float, source=(0, 0, 0, 0), **solve_kwargs) -> tuple[Tensor, dict]:
         """The point-to-all propagator from the site `source` = (t, x, y, z): the twelve unit sources (spin, colour) at
         that site solved as one nrhs = 12 batch of `wilson_solve_n`.  Returns (S, info), S[nb, 12, 12, V] native:
         source component 3 spin + colour, then sink component, then site.  even_odd=True among the keywords: by
-        `wilson_solve_eo_n`."""
+        `wilson_solve_eo_n`; with mixed=True besides (and inner_tol, max_inner, max_outer): by `wilson_solve_eo_mixed_n`."""
         self._wilson_checks('quark_propagator', kappa, xn)
-        solve = self.wilson_solve_eo_n if solve_kwargs.pop('even_odd', False) else self.wilson_solve_n
-        if solve == self.wilson_solve_eo_n:
+        even_odd = bool(solve_kwargs.pop('even_odd', False))
+        mixed = self._pop_mixed('quark_propagator', solve_kwargs, even_odd)
+        solve = self.wilson_solve_eo_n if even_odd else self.wilson_solve_n
+        if even_odd:
             self._eo_lattice('quark_propagator')
+        if mixed is not None:
+            solve_kwargs.update(mixed)
+            solve = self.wilson_solve_eo_mixed_n
         L = self._lattice_shape
         try:
             src = [int(c) for c in source]
@@ -339,6 +532,8 @@ class WilsonFermions:
         """`quark_propagator_n` in the reference layout: S[nb, T, X, Y, Z, 4, 3, 4, 3] (sink spin, sink colour, source
         spin, source colour), for `pion_correlator`."""
         self._wilson_checks('quark_propagator', kappa, x)
+        if self._pop_mixed('quark_propagator', dict(solve_kwargs), bool(solve_kwargs.get('even_odd', False))) is not None:
+            self._eo_lattice('quark_propagator')                                    # raises before the pack
         sn, info = self.quark_propagator_n(self.pack(x), kappa, source, **solve_kwargs)
         S = ops.su3_spinor_unpack(sn, self._lattice_shape).movedim(1, -1).contiguous()
         return S.reshape(*S.shape[:-1], 4, 3), info
@@ -436,14 +631,19 @@ class WilsonFermions:
     def _force_fields_n(self, what: str, xn: Tensor, phin: Tensor, kappa: float, even_odd: bool,
                         **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
         """(X, Y, info), X and Y the full fields whose `l2q_su3_wilson_force` is the force of the pseudofermion action:
-        those of `wilson_solve_normal_n`, or with even_odd, phin the half field phi_e and the action phi_e^H (Mhat^H
+        those of `wilson_solve_normal_n`, or with even_odd (and, with mixed=True among the keywords, by
+        `wilson_solve_schur_normal_mixed_n`), phin the half field phi_e and the action phi_e^H (Mhat^H
         Mhat)^-1 phi_e: X_e, Y_e from `wilson_solve_schur_normal_n`, X_o = kappa H_oe X_e, Y_o = kappa (H^H)_oe Y_e.
         Exact: dS_f = 2 kappa Re[Y_e^H dH_eo X_o + Y_o^H dH_oe X_e], the full-lattice expression."""
+        mixed = self._pop_mixed(what, solve_kwargs, even_odd)
         if not even_odd:
             return self.wilson_solve_normal_n(xn, phin, kappa, **solve_kwargs)
         L = self._eo_lattice(what)
         ap = solve_kwargs.get('antiperiodic_t', True)
-        Xe, Ye, info = self.wilson_solve_schur_normal_n(xn, phin, kappa, **solve_kwargs)
+        if mixed is None:
+            Xe, Ye, info = self.wilson_solve_schur_normal_n(xn, phin, kappa, **solve_kwargs)
+        else:
+            Xe, Ye, info = self.wilson_solve_schur_normal_mixed_n(xn, phin, kappa, **solve_kwargs, **mixed)
         if Xe.dim() == 3:
             Xe, Ye = Xe[:, None].contiguous(), Ye[:, None].contiguous()
         Xo = ops.su3_wilson_hop_eo_n(xn, Xe, L, 1, False, ap, a=kappa)
@@ -521,11 +721,16 @@ class WilsonFermions:
     def pseudofermion_action_n(self, xn: Tensor, phin: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, dict]:
         """S_f = sum_r phi_r^H (M^H M)^-1 phi_r = sum_r |Y_r|^2 per chain, by one `wilson_solve_normal_n` (whose
         keywords these are): (S_f [nb], info).  One more keyword, even_odd (default False): with True phin is the half
-        field phi_e and S_f = sum_r |Y_e,r|^2 by one `wilson_solve_schur_normal_n`."""
+        field phi_e and S_f = sum_r |Y_e,r|^2 by one `wilson_solve_schur_normal_n`; with mixed=True besides (and its
+        inner_tol, max_inner, max_outer) by one `wilson_solve_schur_normal_mixed_n`."""
         self._pf_checks('pseudofermion_action', kappa, xn, phin)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
+        mixed = self._pop_mixed('pseudofermion_action', solve_kwargs, even_odd)
         b = self._pf_field('pseudofermion_action', xn, phin, even_odd, native=True)
         solve = self.wilson_solve_schur_normal_n if even_odd else self.wilson_solve_normal_n
+        if mixed is not None:
+            solve_kwargs.update(mixed)
+            solve = self.wilson_solve_schur_normal_mixed_n
         info = solve(xn, b, kappa, **solve_kwargs)[2]
         return self._sum_fields(info['action']), info
 
@@ -533,6 +738,7 @@ class WilsonFermions:
         """`pseudofermion_action_n` in the reference layout; with even_odd only the even sites of phi are read"""
         self._pf_checks('pseudofermion_action', kappa, x, phi)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
+        self._pop_mixed('pseudofermion_action', dict(solve_kwargs), even_odd)       # raises early; the keys travel on
         pn = self._pf_field('pseudofermion_action', x, phi, even_odd, native=False)
         return self.pseudofermion_action_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
 
@@ -545,16 +751,18 @@ class WilsonFermions:
         Y_o = kappa (H^H)_oe Y_e by one hop each, and the same `l2q_su3_wilson_force` on the merged fields (exact)."""
         k = self._pf_checks('pseudofermion_force', kappa, xn, phin)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
+        self._pop_mixed('pseudofermion_force', dict(solve_kwargs), even_odd)        # raises early; the keys travel on
         b = self._pf_field('pseudofermion_force', xn, phin, even_odd, native=True)
         X, Y, info = self._force_fields_n('pseudofermion_force', xn, b, k, even_odd, **solve_kwargs)
         F = ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True))
-        return F, self._sum_fields(info['action']), info
+        return F, self._sum_fields(info['action']), info                           # (mixed=True: solves as the action's)
 
     def pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
         """`pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]; with even_odd only the even
         sites of phi are read"""
         self._pf_checks('pseudofermion_force', kappa, x, phi)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
+        self._pop_mixed('pseudofermion_force', dict(solve_kwargs), even_odd)
         pn = self._pf_field('pseudofermion_force', x, phi, even_odd, native=False)
         F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
         return self.unpack(F), s, info

@@ -14,7 +14,12 @@
                 hop `l2q_su3_wilson_hop_eo` beside the full apply; one CGNR iteration on M beside one on Mhat (four hops,
                 the update and the xpay on half fields); and the time to solution of `wilson_solve_n` / `wilson_solve_eo_n`
                 and `wilson_solve_normal_n` / `wilson_solve_schur_normal_n` at --eo-kappa, --eo-tol on --nb chains
-                thermalised with --eo-therm heatbath sweeps at beta = 6, Gaussian right-hand sides."""
+                thermalised with --eo-therm heatbath sweeps at beta = 6, Gaussian right-hand sides;
+  --mixed       the mixed-precision even-odd solves (csrc/su3_wilson_f32.hip, profiles/su3_wilson_mixed.md) on the inputs of
+                --eo: per launch the fp32 hop with and without aux + norm beside the fp64 hop of the same session, the fp32
+                update / xpay, demote / promote and the link copy; one CGNR iteration on Mhat in fp32 beside fp64; and the
+                time to solution, inner iterations and outer cycles of `wilson_solve_eo_mixed_n` and
+                `wilson_solve_schur_normal_mixed_n` at each --inner-tol beside their fp64 siblings."""
 import argparse
 import os
 import statistics
@@ -198,6 +203,112 @@ def even_odd(nb, L, nrhs_list, iters, repeats, therm, kappa, tol):
         del psi, pe
 
 
+def mixed(nb, L, nrhs_list, iters, repeats, therm, kappa, tol, inner_tols):
+    V = L[0] * L[1] * L[2] * L[3]
+    Vh = V // 2
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    lat = LatticeSU3(nb, L)
+    xn = lat.pack(lat.heatbath(lat.random().to(dev), 6.0, nsweeps=therm, nover=3)[0])
+    print(f'{L} x {nb} chains, beta 6.0 after {therm} heatbath sweeps (nover 3): plaquette '
+          f'{float(lat.plaq_sums_n(xn)[:, 0].mean()) / (18.0 * V):.5f}; kappa {kappa}, tol {tol}')
+    x32 = ops.su3_links_demote_eo_n(xn, L)
+    S32, L32 = SPINOR // 2, LINKS // 2
+    show('link copy (fp64 in, fp32 parity-ordered out)', windows(lambda: ops.su3_links_demote_eo_n(xn, L, out=x32), iters, repeats),
+         LINKS + L32, nb * V)
+    for nrhs in nrhs_list:
+        hsites = nb * nrhs * Vh
+        print(f'lattice {L} x {nb} chains x {nrhs} right-hand sides, {iters} calls per window, {repeats} windows')
+        c64, c128 = torch.complex64, torch.complex128
+        he, ho, hq, hz, hx = (torch.empty((nb, nrhs, 12, Vh), dtype=c128, device=dev) for _ in range(5))
+        hr, hp = torch.randn_like(he), torch.randn_like(he)
+        he.copy_(hr)
+        hx.zero_()
+        fe, fo, fq, fz, fx = (torch.empty((nb, nrhs, 12, Vh), dtype=c64, device=dev) for _ in range(5))
+        fr, fp = hr.to(c64), hp.to(c64)
+        fe.copy_(fr)
+        fx.zero_()
+        hpart = torch.empty((nb, nrhs, -(-Vh // 256)), dtype=torch.float64, device=dev)
+        hrpart = torch.empty_like(hpart)
+        coef = torch.full((nb, nrhs), 1e-3, dtype=torch.float64, device=dev)
+        # bytes per (system, half-site), the 8 links once per chain (beside it: once per system)
+        t1 = show('fp64 hop (a = 1, no aux), odd sites', windows(lambda: ops.su3_wilson_hop_eo_n(xn, he, L, 1, out=ho), iters, repeats),
+                  2 * SPINOR + 2 * LINKS / nrhs, hsites, 2 * SPINOR + 2 * LINKS)
+        t2 = show('fp64 hop (aux, fused norm), even sites',
+                  windows(lambda: ops.su3_wilson_hop_eo_n(xn, ho, L, 0, a=-kappa * kappa, aux=he, b=1.0, out=hq, norm=hpart),
+                          iters, repeats), 3 * SPINOR + 2 * LINKS / nrhs, hsites, 3 * SPINOR + 2 * LINKS)
+        f1 = show('fp32 hop (a = 1, no aux), odd sites', windows(lambda: ops.su3_wilson_hop_eo_f32_n(x32, fe, L, 1, out=fo), iters, repeats),
+                  2 * S32 + 2 * L32 / nrhs, hsites, 2 * S32 + 2 * L32)
+        f2 = show('fp32 hop (aux, fused norm), even sites',
+                  windows(lambda: ops.su3_wilson_hop_eo_f32_n(x32, fo, L, 0, a=-kappa * kappa, aux=fe, b=1.0, out=fq, norm=hpart),
+                          iters, repeats), 3 * S32 + 2 * L32 / nrhs, hsites, 3 * S32 + 2 * L32)
+        print(f'  Mhat in fp32 {(f1 + f2) * 1e3:.3f} ms against fp64 {(t1 + t2) * 1e3:.3f} ms: ratio {(f1 + f2) / (t1 + t2):.2f}')
+        tu = show('fp64 cg_update, half fields', windows(lambda: ops.su3_spinor_cg_update_(hx, hr, hp, hq, coef, hrpart), iters, repeats),
+                  6 * SPINOR, hsites)
+        fu = show('fp32 cg_update, half fields', windows(lambda: ops.su3_spinor_cg_update_f32_(fx, fr, fp, fq, coef, hrpart), iters, repeats),
+                  6 * S32, hsites)
+        tx = show('fp64 xpay, half fields', windows(lambda: ops.su3_spinor_xpay_(hp, hz, coef), iters, repeats), 3 * SPINOR, hsites)
+        fxp = show('fp32 xpay, half fields', windows(lambda: ops.su3_spinor_xpay_f32_(fp, fz, coef), iters, repeats), 3 * S32, hsites)
+        show('demote (fp64 in, fp32 out)', windows(lambda: ops.su3_spinor_demote(hr, coef, out=fz), iters, repeats), SPINOR + S32, hsites)
+        show('promote_axpy (x64 += s e32)', windows(lambda: ops.su3_spinor_promote_axpy_(hx, fz, coef), iters, repeats),
+             2 * SPINOR + S32, hsites)
+
+        def schur(src, dst, dagger):
+            ops.su3_wilson_hop_eo_n(xn, src, L, 1, dagger, out=ho)
+            ops.su3_wilson_hop_eo_n(xn, ho, L, 0, dagger, a=-kappa * kappa, aux=src, b=1.0, out=dst, norm=hpart)
+            return ops.sum_parts(hpart)
+
+        def schur32(src, dst, dagger):
+            ops.su3_wilson_hop_eo_f32_n(x32, src, L, 1, dagger, out=fo)
+            ops.su3_wilson_hop_eo_f32_n(x32, fo, L, 0, dagger, a=-kappa * kappa, aux=src, b=1.0, out=dst, norm=hpart)
+            return ops.sum_parts(hpart)
+
+        def iteration_eo():
+            qq = schur(hp, hq, False)
+            ops.su3_spinor_cg_update_(hx, hr, hp, hq, (coef / (qq + 1.0)).contiguous(), hrpart)
+            zn = schur(hr, hz, True)
+            ops.su3_spinor_xpay_(hp, hz, (coef / (zn + 1.0)).contiguous())
+
+        def iteration_f32():
+            qq = schur32(fp, fq, False)
+            ops.su3_spinor_cg_update_f32_(fx, fr, fp, fq, (coef / (qq + 1.0)).contiguous(), hrpart)
+            zn = schur32(fr, fz, True)
+            ops.su3_spinor_xpay_f32_(fp, fz, (coef / (zn + 1.0)).contiguous())
+
+        te = show('one CGNR iteration on Mhat, fp64, as launched', windows(iteration_eo, iters, repeats))
+        tf = show('one CGNR iteration on Mhat, fp32, as launched', windows(iteration_f32, iters, repeats))
+        print(f'  launches by themselves: fp64 2 x {(t1 + t2) * 1e3:.3f} + {tu * 1e3:.3f} + {tx * 1e3:.3f} = '
+              f'{(2 * (t1 + t2) + tu + tx) * 1e3:.3f} ms; fp32 2 x {(f1 + f2) * 1e3:.3f} + {fu * 1e3:.3f} + {fxp * 1e3:.3f} = '
+              f'{(2 * (f1 + f2) + fu + fxp) * 1e3:.3f} ms; iteration ratio fp32 / fp64 {tf / te:.2f}')
+        del he, ho, hq, hz, hx, hr, hp, fe, fo, fq, fz, fx, fr, fp
+        psi = torch.randn((nb, nrhs, 12, V), dtype=c128, device=dev)
+        pe = ops.su3_spinor_split_eo(psi, L)[0].contiguous()
+        kw = dict(tol=tol, max_iter=2000)
+
+        def timed(name, fn):
+            fn()                                                    # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            info = res[-1]
+            outer = f', outer cycles {int(info["outer"].min())} .. {int(info["outer"].max())}' if 'outer' in info else ''
+            print(f'{name:52s} {dt * 1e3:9.1f} ms  iterations {int(info["iters"].min())} .. {int(info["iters"].max())}{outer}, '
+                  f'residual <= {float(info["residual"].max()):.3g}, all converged {bool(info["converged"].all())}')
+            return dt
+        t64 = timed('wilson_solve_eo_n (fp64)', lambda: lat.wilson_solve_eo_n(xn, psi, kappa, **kw))
+        for it in inner_tols:
+            tm = timed(f'wilson_solve_eo_mixed_n inner_tol {it:g}', lambda: lat.wilson_solve_eo_mixed_n(xn, psi, kappa, inner_tol=it, **kw))
+            print(f'  time to solution, mixed / fp64: {tm / t64:.2f}')
+        t64 = timed('wilson_solve_schur_normal_n (fp64)', lambda: lat.wilson_solve_schur_normal_n(xn, pe, kappa, **kw))
+        for it in inner_tols:
+            tm = timed(f'wilson_solve_schur_normal_mixed_n inner_tol {it:g}',
+                       lambda: lat.wilson_solve_schur_normal_mixed_n(xn, pe, kappa, inner_tol=it, **kw))
+            print(f'  time to solution, mixed / fp64: {tm / t64:.2f}')
+        del psi, pe
+
+
 def torch_apply(x, psi, kappa, gam):
     """M psi from roll / einsum on reference-layout tensors (antiperiodic in t)"""
     eye = torch.eye(4, dtype=psi.dtype, device=psi.device)
@@ -272,6 +383,8 @@ def main():
     ap.add_argument('--eo-kappa', type=float, default=0.12)
     ap.add_argument('--eo-tol', type=float, default=1e-10)
     ap.add_argument('--eo-therm', type=int, default=10)
+    ap.add_argument('--mixed', action='store_true')
+    ap.add_argument('--inner-tol', type=float, nargs='+', default=[1e-3, 1e-4, 1e-5, 1e-6])
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
@@ -281,6 +394,8 @@ def main():
         torch_compose(args.torch_nb, args.L, args.nrhs, max(2, args.iters // 4), args.repeats)
     if args.eo:
         even_odd(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol)
+    if args.mixed:
+        mixed(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol, args.inner_tol)
     if args.propagator:
         propagator(args.physics_nb, args.L, args.therm, args.kappa)
 

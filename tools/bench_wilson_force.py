@@ -11,7 +11,9 @@ for profiles/su3_wilson_force.md, SU(3) 8^4, complex128:
                 fermion force, gauge kick, link update), then --ntraj trajectories: acceptance, CG iterations per solve,
                 <exp(-dH)> with its standard error; with --even-odd the same split and trajectories again with
                 `WilsonHMCEvenOdd` on the same thermalised links (profiles/su3_wilson_eo.md): its 'solves' stage is the
-                solve on the Schur complement plus the two hops and merges that complete X and Y."""
+                solve on the Schur complement plus the two hops and merges that complete X and Y; with --mixed the
+                even-odd run and then `WilsonHMCMixed` (every solve by fp32 inner CG and fp64 defect correction,
+                profiles/su3_wilson_mixed.md; --inner-tol) on the same links, from the same seed."""
 import argparse
 import os
 import statistics
@@ -23,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'l2hmc-qcd_amd'))
 from l2hmc import _ops as ops  # noqa: E402
-from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC, WilsonHMCEvenOdd  # noqa: E402
+from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC, WilsonHMCEvenOdd, WilsonHMCMixed  # noqa: E402
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3  # noqa: E402
 
 HBM_PEAK = 8.0e12       # B/s, the spec figure that DESIGN.md's fractions are taken against
@@ -83,15 +85,18 @@ def kernels(nb, L, npf_list, iters, repeats):
          3 * LINKS, sites)
 
 
-def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=False):
+def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=False, mixed=False, inner_tol=None):
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
     lat = LatticeSU3(nb, L)
     x = lat.heatbath(lat.random().to(dev), beta, nsweeps=therm, nover=3)[0]
     print(f'{L} x {nb} chains, beta {beta} after {therm} heatbath sweeps (nover 3): plaquette '
           f'{float(lat.plaqs(x).mean()):.5f}; kappa {kappa}, npf {npf}, eps {eps}, nleapfrog {nleapfrog}, '
-          f'even_odd {even_odd}')
-    hmc = (WilsonHMCEvenOdd if even_odd else WilsonHMC)(lat, beta, kappa, eps, nleapfrog, npf=npf)
+          f'even_odd {even_odd}, mixed {mixed}' + (f', inner_tol {inner_tol}' if mixed and inner_tol else ''))
+    if mixed:
+        hmc = WilsonHMCMixed(lat, beta, kappa, eps, nleapfrog, npf=npf, inner_tol=inner_tol)
+    else:
+        hmc = (WilsonHMCEvenOdd if even_odd else WilsonHMC)(lat, beta, kappa, eps, nleapfrog, npf=npf)
     xn = lat.pack(x)
     hmc.trajectory_n(xn)                                         # warm-up
     # one leapfrog stage by stage
@@ -162,15 +167,19 @@ def main():
     ap.add_argument('--nleapfrog', type=int, default=25)
     ap.add_argument('--ntraj', type=int, default=10)
     ap.add_argument('--even-odd', action='store_true')
+    ap.add_argument('--mixed', action='store_true')
+    ap.add_argument('--inner-tol', type=float, default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
     if args.kernels:
         kernels(args.nb, args.L, args.npf, args.iters, args.repeats)
     if args.trajectory:
-        for eo in (False, True) if args.even_odd else (False,):
+        modes = [(True, False), (True, True)] if args.mixed else [(False, False), (True, False)] if args.even_odd \
+            else [(False, False)]
+        for eo, mixed in modes:
             trajectory(args.physics_nb, args.L, args.therm, args.beta, args.kappa, args.eps, args.nleapfrog, args.npf[0],
-                       args.ntraj, eo)
+                       args.ntraj, eo, mixed, args.inner_tol)
 
 
 if __name__ == '__main__':
