@@ -500,6 +500,53 @@ int l2q_su3_spinor_demote(const void* in64, const double* scale, void* out32, lo
 /* x64 += scale[s] e32, product and sum in double; a system with scale[s] = 0 is not written and keeps its bits.
  * L2Q_EINVAL: a null pointer; x64 aliasing e32; a size as above. */
 int l2q_su3_spinor_promote_axpy(void* x64, const void* e32, const double* scale, long nsys, long V, void* stream);
+/* csrc/su3_wilson_clover.hip.  The clover term of the O(a)-improved Wilson operator (Sheikholeslami & Wohlert; Luescher,
+ * Sint, Sommer & Weisz) and the kernels of its even-odd preconditioned solve:
+ *   M_sw = A - kappa H,   A(x) = 1 + kappa c_sw i sum_{mu<nu} sigma_{mu nu} (x) Fhat_{mu nu}(x),
+ * H the hop of l2q_su3_wilson_apply, sigma_{mu nu} = (i/2) [gamma_mu, gamma_nu] in its gamma basis, Fhat_{mu nu} =
+ * (Q_{mu nu} - Q_{mu nu}^H) / 8 with Q_{mu nu} the sum of the four clover leaves of l2q_su3_clover_reduce (L1 = U_mu(x)
+ * U_nu(x+mu) U_mu(x+nu)^H U_nu(x)^H).  Fhat is NOT made traceless: the definition for which published c_sw hold; M_sw is
+ * 2 kappa times D_W + c_sw (i/4) sum_{mu,nu} sigma_{mu nu} Fhat_{mu nu}.  In the chiral basis A(x) = diag(A+, A-), two
+ * Hermitian 6 x 6 blocks (row index 3 spin + colour within a chirality; A+ on spin 0, 1); with E_k = Fhat_{0k} and B =
+ * (Fhat_23, -Fhat_13, Fhat_12):
+ *   A+ = 1 - i kappa c_sw sum_k sigma_k (x) (E_k + B_k),   A- = 1 + i kappa c_sw sum_k sigma_k (x) (E_k - B_k).
+ * A is Hermitian and commutes with gamma5, so M_sw^H = gamma5 M_sw gamma5 and the dagger bit of the hop still gives the
+ * adjoint.  All four extents even (2 is legal), L2Q_ESHAPE otherwise.
+ * Block field: cl[nb][2 parity][2 chirality][36][V/2] doubles, parity-ordered like x32 above: entry h of parity p is the
+ * site of parity p of the pair (2h, 2h + 1).  The 36 reals of a block: its 6 diagonal entries, then (re, im) of the 15
+ * entries above the diagonal, row-major.  The asymmetric even-odd form:
+ *   Mhat = A_ee - kappa^2 H_eo A_oo^-1 H_oe,   bhat_e = b_e + kappa H_eo A_oo^-1 b_o,
+ *   psi_o = A_oo^-1 (b_o + kappa H_oe psi_e);
+ * with psi_o reconstructed, b - M_sw psi is bhat_e - Mhat psi_e on the even sites and 0 on the odd ones.
+ * l2q_su3_clover_term: cl = A of both parities from the native links xn, coef = kappa c_sw (0 gives A = 1).  One thread
+ * per site; once per configuration.  L2Q_EINVAL: a null pointer; cl aliasing xn; a non-positive size; coef not finite. */
+int l2q_su3_clover_term(const void* xn, void* cl, double coef, int nb, int T, int X, int Y, int Z, void* stream);
+/* clinv = the inverse of every block of cl, in the same layout, by an unpivoted L D L^H (no square roots).
+ * minpiv_part[nb][2 parity][ceil((V/2) / 256)]: the smallest pivot d_i of a workgroup's blocks; logdet_part (may be null),
+ * the same shape: its sum of log d_i (log det A of a parity = the sum of its partials), both by the fixed tree of the norm
+ * partials.  A non-positive pivot is no error here: the minimum reports it, and the entries of that block are not
+ * meaningful.  L2Q_EINVAL: a null cl, clinv or minpiv_part; outputs aliasing cl or each other; a non-positive size. */
+int l2q_su3_clover_invert(const void* cl, void* clinv, double* minpiv_part, double* logdet_part, int nb, int T, int X,
+                          int Y, int Z, void* stream);
+/* l2q_su3_wilson_hop_eo with a block field c (A or its inverse; the blocks of `parity`, the parity of out, are read):
+ *   cmode 0   out = b aux + a H src           c null: the hop itself
+ *   cmode 1   out = b (C aux) + a H src
+ *   cmode 2   out = C (b aux + a H src)
+ * C(x) the block pair of c at the output site.  Everything else -- the arguments, flags, parity, aux and norm_part may be
+ * null, out may be aux, the workgroup order with the right-hand side fastest -- as there.  Uses: the first half of Mhat
+ * (cmode 2, c = A^-1, parity 1, no aux, a = 1); the second half (cmode 1, c = A, parity 0, a = -kappa^2, b = 1); the
+ * reconstruction (cmode 2, c = A^-1, parity 1, a = kappa, b = 1); a parity of M_sw itself (cmode 1, c = A, a = -kappa,
+ * b = 1).  Per (system, half-site) 504 flops for the two blocks on top of the hop's, and 576 B of blocks, which the nrhs
+ * systems of a chain share.  L2Q_EINVAL as l2q_su3_wilson_hop_eo, and: cmode outside 0..2; c null with cmode 1 or 2, or
+ * given with cmode 0; out aliasing c.  L2Q_ESHAPE: an odd extent. */
+int l2q_su3_wilson_clover_hop_eo(const void* xn, const void* src, const void* aux, const void* c, void* out,
+                                 double* norm_part, double a, double b, int flags, int parity, int cmode, int nb,
+                                 int nrhs, int T, int X, int Y, int Z, void* stream);
+/* out = C src on the half field [nb][nrhs][12][V/2] of `parity`, C the blocks of that parity of c; out may be src.
+ * norm_part as above (may be null).  L2Q_EINVAL: a null c, src or out; out aliasing c; sizes and parity as above.
+ * L2Q_ESHAPE: an odd extent. */
+int l2q_su3_clover_apply(const void* c, const void* src, void* out, double* norm_part, int parity, int nb, int nrhs,
+                         int T, int X, int Y, int Z, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

@@ -1,5 +1,6 @@
 // su3_clover.hpp -- the clover leaf of one plane, F_{mu nu}(x) = TAH(sum of the four leaves) / 4, shared by the
-// clover sums (su3_flow.hip) and their VJP (su3_clover_bwd.hip).  The leaves are listed in su3_flow.hip.
+// clover sums (su3_flow.hip), their VJP (su3_clover_bwd.hip) and the clover term of the improved Wilson operator
+// (su3_wilson_clover.hip), which takes the leaf sum Q without the TAH.  The leaves are listed in su3_flow.hip.
 #pragma once
 #include "su3_links.hpp"
 
@@ -11,7 +12,7 @@ namespace l2q {
 // operands of a plane.
 #define L2Q_CLOVER_STEP(...) if (go) { __VA_ARGS__ }
 
-// anti-Hermitian traceless 3x3: i d[k] on the diagonal, (re, im)[0..2] = entries (0,1), (0,2), (1,2)
+// anti-Hermitian 3x3 (traceless where TAH made it): i d[k] on the diagonal, (re, im)[0..2] = entries (0,1), (0,2), (1,2)
 struct AH3 {
   double d[3], re[3], im[3];
 };
@@ -23,12 +24,12 @@ struct CloverSites {
   S o, pm, pn, mm, mm_pn, mm_mn, mn, pm_mn;
 };
 
-// F = TAH(sum of the four leaves of plane (mu, nu)) / 4; retr += Re tr L1.  ld(m, dir, site) loads U_dir(site).
+// q = Q_{mu nu}, the sum of the four leaves of plane (mu, nu); retr += Re tr L1.  ld(m, dir, site) loads U_dir(site).
 // Each leaf is a chain of three products, so at most Q, two temporaries and one operand are live.
 template <class Ld, class S>
-__device__ __forceinline__ void clover_plane(AH3& f, double& retr, const Ld& ld, const CloverSites<S>& st, int mu,
-                                             int nu, bool go) {
-  M3 q, a, t, u;
+__device__ __forceinline__ void clover_leaves(M3& q, double& retr, const Ld& ld, const CloverSites<S>& st, int mu,
+                                              int nu, bool go) {
+  M3 a, t, u;
   // L1
   L2Q_CLOVER_STEP(ld(a, mu, st.o); ld(u, nu, st.pm); m3_mul_nn(t, a, u);)
   L2Q_CLOVER_STEP(ld(a, mu, st.pn); m3_mul_na(u, t, a);)
@@ -46,6 +47,22 @@ __device__ __forceinline__ void clover_plane(AH3& f, double& retr, const Ld& ld,
   L2Q_CLOVER_STEP(ld(u, mu, st.mn); m3_mul_an(t, a, u);)      // a = U_nu(x-nu)
   L2Q_CLOVER_STEP(ld(a, nu, st.pm_mn); m3_mul_nn(u, t, a);)
   L2Q_CLOVER_STEP(ld(a, mu, st.o); m3_mac_na(q, u, a);)
+}
+
+// the anti-Hermitian part (Q - Q^H) / 8 with its trace: Fhat_{mu nu} of the Sheikholeslami-Wohlert term
+__device__ __forceinline__ void clover_ah(AH3& f, const M3& q) {
+  f.d[0] = 0.25 * q.im[0]; f.d[1] = 0.25 * q.im[4]; f.d[2] = 0.25 * q.im[8];
+  f.re[0] = 0.125 * (q.re[1] - q.re[3]); f.im[0] = 0.125 * (q.im[1] + q.im[3]);
+  f.re[1] = 0.125 * (q.re[2] - q.re[6]); f.im[1] = 0.125 * (q.im[2] + q.im[6]);
+  f.re[2] = 0.125 * (q.re[5] - q.re[7]); f.im[2] = 0.125 * (q.im[5] + q.im[7]);
+}
+
+// F = TAH(sum of the four leaves of plane (mu, nu)) / 4; retr += Re tr L1
+template <class Ld, class S>
+__device__ __forceinline__ void clover_plane(AH3& f, double& retr, const Ld& ld, const CloverSites<S>& st, int mu,
+                                             int nu, bool go) {
+  M3 q;
+  clover_leaves(q, retr, ld, st, mu, nu, go);
   // F = TAH(Q) / 4 kept as its 9 independent reals (anti-Hermitian, traceless)
   const double tr3 = (q.im[0] + q.im[4] + q.im[8]) * (1.0 / 3.0);
   f.d[0] = 0.25 * (q.im[0] - tr3); f.d[1] = 0.25 * (q.im[4] - tr3); f.d[2] = 0.25 * (q.im[8] - tr3);

@@ -912,6 +912,110 @@ def su3_spinor_promote_axpy_(x64: torch.Tensor, e32: torch.Tensor, scale: torch.
     return x64
 
 
+# the clover term of the improved Wilson operator (csrc/su3_wilson_clover.hip)
+def _clover_field_check(what: str, name: str, t: torch.Tensor, nb: int, Vh: int) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (nb, 2, 2, 36, Vh) \
+            or not t.is_contiguous():
+        got = f'{t.dtype} {list(t.shape)}' if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f'{what}: {name} must be a contiguous float64 block field [{nb}, 2, 2, 36, {Vh}], got {got}')
+
+
+def su3_clover_term_n(xn: torch.Tensor, coef: float, lat: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the block field cl[nb, 2 parity, 2 chirality, 36, V/2] float64 of the clover term A = 1 + coef i sum_{mu<nu}
+    sigma_{mu nu} (x) Fhat_{mu nu}, coef = kappa c_sw, on the native links xn[nb, 4, 9, V] (see l2q.h).  Even extents."""
+    T, X, Y, Z = _even_lattice('su3_clover_term_n', lat)
+    V = T * X * Y * Z
+    if xn.dtype != C128 or xn.dim() != 4 or tuple(xn.shape[1:]) != (4, 9, V) or not xn.is_contiguous():
+        raise ValueError(f'su3_clover_term_n: xn must be contiguous complex128 [nb, 4, 9, {V}], got {xn.dtype} '
+                         f'{list(xn.shape)}')
+    if out is None:
+        out = torch.empty((xn.shape[0], 2, 2, 36, V // 2), dtype=torch.float64, device=xn.device)
+    else:
+        _clover_field_check('su3_clover_term_n', 'out', out, xn.shape[0], V // 2)
+    N.call('l2q_su3_clover_term', xn, out, float(coef), xn.shape[0], T, X, Y, Z)
+    return out
+
+
+def su3_clover_invert_n(cl: torch.Tensor, lat: Sequence[int], out: Optional[torch.Tensor] = None,
+                        logdet: bool = True):
+    """(clinv, minpiv_part, logdet_part): the inverse of every block of cl in the same layout, and per (chain, parity,
+    workgroup) [nb, 2, ceil((V/2) / 256)] the smallest L D L^H pivot and (logdet; else None) the sum of log d_i.  A
+    non-positive pivot is not an error here: the caller looks at minpiv_part."""
+    T, X, Y, Z = _even_lattice('su3_clover_invert_n', lat)
+    Vh = T * X * Y * Z // 2
+    if not isinstance(cl, torch.Tensor) or cl.dim() != 5:
+        raise ValueError(f'su3_clover_invert_n: cl must be a block field [nb, 2, 2, 36, {Vh}]')
+    nb = cl.shape[0]
+    _clover_field_check('su3_clover_invert_n', 'cl', cl, nb, Vh)
+    if out is None:
+        out = torch.empty_like(cl)
+    else:
+        _clover_field_check('su3_clover_invert_n', 'out', out, nb, Vh)
+    minpiv = torch.empty((nb, 2, -(-Vh // 256)), dtype=torch.float64, device=cl.device)
+    ld = torch.empty_like(minpiv) if logdet else None
+    N.call('l2q_su3_clover_invert', cl, out, minpiv, ld, nb, T, X, Y, Z)
+    return out, minpiv, ld
+
+
+def su3_wilson_clover_hop_eo_n(xn: torch.Tensor, src: torch.Tensor, lat: Sequence[int], parity: int, c: Optional[torch.Tensor],
+                               cmode: int, dagger: bool = False, antiperiodic_t: bool = True, a: float = 1.0,
+                               aux: Optional[torch.Tensor] = None, b: float = 0.0, out: Optional[torch.Tensor] = None,
+                               norm: bool = False):
+    """`su3_wilson_hop_eo_n` with a block field c[nb, 2, 2, 36, V/2] (the clover term or its inverse), C its blocks at
+    the output sites: cmode 0 (c None) out = b aux + a H src; 1 out = b (C aux) + a H src; 2 out = C (b aux + a H src)."""
+    what = 'su3_wilson_clover_hop_eo_n'
+    T, X, Y, Z = _even_lattice(what, lat)
+    Vh = T * X * Y * Z // 2
+    if parity not in (0, 1):
+        raise ValueError(f'{what}: parity must be 0 or 1, got {parity!r}')
+    if cmode not in (0, 1, 2) or isinstance(cmode, bool):
+        raise ValueError(f'{what}: cmode must be 0, 1 or 2, got {cmode!r}')
+    if (c is None) != (cmode == 0):
+        raise ValueError(f'{what}: the block field c goes with cmode 1 and 2 and only with them, got cmode {cmode} and '
+                         f'c {"None" if c is None else "given"}')
+    if src.dim() != 4 or src.shape[0] != xn.shape[0] or src.shape[2] != 12 or src.shape[3] != Vh \
+            or xn.shape[-1] != 2 * Vh:
+        raise ValueError(f'{what}: need a half field src [nb, nrhs, 12, V/2] on xn {list(xn.shape)}, got '
+                         f'{list(src.shape)}')
+    _spinor_check(what, 'src', src, src.shape)
+    if c is not None:
+        _clover_field_check(what, 'c', c, src.shape[0], Vh)
+    if aux is not None:
+        _spinor_check(what, 'aux', aux, src.shape)
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _spinor_check(what, 'out', out, src.shape)
+    nb, nrhs = src.shape[:2]
+    part = _norm_part(what, norm, nb, nrhs, lambda: -(-Vh // 256), src.device)
+    N.call('l2q_su3_wilson_clover_hop_eo', xn, src, aux, c, out, part, float(a), float(b),
+           int(bool(dagger)) | (int(bool(antiperiodic_t)) << 1), int(parity), int(cmode), nb, nrhs, T, X, Y, Z)
+    return out if part is None else (out, part)
+
+
+def su3_clover_apply_n(c: torch.Tensor, src: torch.Tensor, lat: Sequence[int], parity: int,
+                       out: Optional[torch.Tensor] = None, norm: bool = False):
+    """out = C src on the half field src[nb, nrhs, 12, V/2] of `parity`, C the blocks of that parity of the block field
+    c; out None = a new field, out may be src.  norm as in `su3_wilson_hop_eo_n`."""
+    what = 'su3_clover_apply_n'
+    T, X, Y, Z = _even_lattice(what, lat)
+    Vh = T * X * Y * Z // 2
+    if parity not in (0, 1):
+        raise ValueError(f'{what}: parity must be 0 or 1, got {parity!r}')
+    if src.dim() != 4 or src.shape[2] != 12 or src.shape[3] != Vh:
+        raise ValueError(f'{what}: need a half field src [nb, nrhs, 12, V/2] on {[T, X, Y, Z]}, got {list(src.shape)}')
+    _spinor_check(what, 'src', src, src.shape)
+    _clover_field_check(what, 'c', c, src.shape[0], Vh)
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _spinor_check(what, 'out', out, src.shape)
+    nb, nrhs = src.shape[:2]
+    part = _norm_part(what, norm, nb, nrhs, lambda: -(-Vh // 256), src.device)
+    N.call('l2q_su3_clover_apply', c, src, out, part, int(parity), nb, nrhs, T, X, Y, Z)
+    return out if part is None else (out, part)
+
+
 def sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
     partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""

@@ -20,7 +20,8 @@ from l2hmc import _autograd as AG
 from l2hmc import _ops as ops
 from l2hmc.configs import Charges
 from l2hmc.lattice.lattice import Lattice
-from l2hmc.lattice.su3.pytorch.wilson import WilsonFermions, _log_positive, effective_mass, pion_correlator  # noqa: F401
+from l2hmc.lattice.su3.pytorch.wilson import (CloverTerm, WilsonFermions, _log_positive, effective_mass,  # noqa: F401
+                                              pion_correlator)
 
 log = logging.getLogger(__name__)
 Tensor = torch.Tensor

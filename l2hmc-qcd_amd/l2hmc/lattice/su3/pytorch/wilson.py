@@ -1,7 +1,8 @@
 """The host side of the Wilson fermions on `LatticeSU3` (kernels: csrc/su3_wilson.hip, csrc/su3_wilson_eo.hip,
-csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip): the mixin ``WilsonFermions`` with the operator, the two solvers on
-one CG loop (``_CG``), their even-odd and mixed-precision forms (``_MixedSolve``: fp64 defect correction around the same
-loop on fp32 fields), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
+csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip, csrc/su3_wilson_clover.hip): the mixin ``WilsonFermions`` with the
+operator, the two solvers on one CG loop (``_CG``), their even-odd and mixed-precision forms (``_MixedSolve``: fp64 defect
+correction around the same loop on fp32 fields), the clover-improved operator and its even-odd solve (``CloverTerm``,
+``_CloverSchurOp``), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
 random-draw rule of the fermion layer."""
 from __future__ import annotations
 
@@ -114,6 +115,35 @@ class _SchurOpF32:
             ops.su3_wilson_hop_eo_f32_n(x32, src, L, 1, dagger, antiperiodic_t, out=odd)
             ops.su3_wilson_hop_eo_f32_n(x32, odd, L, 0, dagger, antiperiodic_t, a=-k * k, aux=src, b=1.0, out=dst,
                                         norm=part if norm else False)
+            return ops.sum_parts(part) if norm else None
+        self.apply = apply
+
+
+class CloverTerm:
+    """The clover term of one configuration, as `clover_term(_n)` builds it: `a` and `ainv`, the block fields [nb, 2
+    parity, 2 chirality, 36, V/2] float64 of A and A^-1 (layout: include/l2q.h); `min_pivot` [nb], the smallest pivot of the
+    L D L^H of any block of the chain (<= 0: A is not positive definite there and `ainv` is not usable); `logdet` [nb, 2],
+    log det A per parity (NaN where a pivot is not positive); and the `kappa` and `c_sw` it was built with."""
+
+    def __init__(self, a: Tensor, ainv: Tensor, min_pivot: Tensor, logdet: Tensor, kappa: float, c_sw: float):
+        self.a, self.ainv, self.min_pivot, self.logdet, self.kappa, self.c_sw = a, ainv, min_pivot, logdet, kappa, c_sw
+
+
+class _CloverSchurOp:
+    """Mhat = A_ee - kappa^2 H_eo A_oo^-1 H_oe on even half fields as the operator of a `_CG`: two
+    `su3_wilson_clover_hop_eo_n` through one scratch odd half field -- A_oo^-1 on the result of the first (cmode 2), A_ee
+    on the aux of the second (cmode 1) -- the fused norm from the second.  A is Hermitian and commutes with gamma5, so
+    the dagger bit on both hops gives Mhat^H.  dst must not be src."""
+
+    def __init__(self, xn: Tensor, k: float, L, antiperiodic_t, like: Tensor, cl: CloverTerm):
+        self.sites = like.shape[3]
+        part = torch.empty((*like.shape[:2], -(-self.sites // 256)), dtype=torch.float64, device=like.device)
+        odd = torch.empty_like(like)
+
+        def apply(src, dst, dagger, norm=True):
+            ops.su3_wilson_clover_hop_eo_n(xn, src, L, 1, cl.ainv, 2, dagger, antiperiodic_t, out=odd)
+            ops.su3_wilson_clover_hop_eo_n(xn, odd, L, 0, cl.a, 1, dagger, antiperiodic_t, a=-k * k, aux=src, b=1.0,
+                                           out=dst, norm=part if norm else False)
             return ops.sum_parts(part) if norm else None
         self.apply = apply
 
@@ -504,11 +534,19 @@ class WilsonFermions:
         """The point-to-all propagator from the site `source` = (t, x, y, z): the twelve unit sources (spin, colour) at
         that site solved as one nrhs = 12 batch of `wilson_solve_n`.  Returns (S, info), S[nb, 12, 12, V] native:
         source component 3 spin + colour, then sink component, then site.  even_odd=True among the keywords: by
-        `wilson_solve_eo_n`; with mixed=True besides (and inner_tol, max_inner, max_outer): by `wilson_solve_eo_mixed_n`."""
+        `wilson_solve_eo_n`; with mixed=True besides (and inner_tol, max_inner, max_outer): by `wilson_solve_eo_mixed_n`.
+        c_sw among the keywords (and clover=, a prebuilt `CloverTerm`): the propagator of the clover-improved operator,
+        by `wilson_clover_solve_n`, which is even-odd preconditioned: not with even_odd=False or mixed=True."""
         self._wilson_checks('quark_propagator', kappa, xn)
+        improved = self._pop_clover('quark_propagator', solve_kwargs)
         even_odd = bool(solve_kwargs.pop('even_odd', False))
         mixed = self._pop_mixed('quark_propagator', solve_kwargs, even_odd)
         solve = self.wilson_solve_eo_n if even_odd else self.wilson_solve_n
+        if improved is not None:
+            self._clover_checks('quark_propagator', kappa, improved['c_sw'])
+
+            def solve(xn, bn, kappa, **kw):
+                return self.wilson_clover_solve_n(xn, bn, kappa, **improved, **kw)
         if even_odd:
             self._eo_lattice('quark_propagator')
         if mixed is not None:
@@ -537,6 +575,175 @@ class WilsonFermions:
         sn, info = self.quark_propagator_n(self.pack(x), kappa, source, **solve_kwargs)
         S = ops.su3_spinor_unpack(sn, self._lattice_shape).movedim(1, -1).contiguous()
         return S.reshape(*S.shape[:-1], 4, 3), info
+
+    # ------------------------------------------------------------ the clover term: the O(a)-improved operator
+    @staticmethod
+    def _pop_clover(what: str, solve_kwargs: dict) -> Optional[dict]:
+        """the clover keywords c_sw and clover popped from solve_kwargs: None without c_sw, else the dict of them.
+        ValueError: clover= without c_sw; c_sw with even_odd=False, mixed=True or a keyword of the mixed solves."""
+        c_sw, clover = solve_kwargs.pop('c_sw', None), solve_kwargs.pop('clover', None)
+        if c_sw is None:
+            if clover is not None:
+                raise ValueError(f'LatticeSU3.{what}: clover= goes with c_sw')
+            return None
+        mixed = [k for k in ('inner_tol', 'max_inner', 'max_outer') if k in solve_kwargs]
+        if not solve_kwargs.get('even_odd', True) or solve_kwargs.get('mixed', False) or mixed:
+            raise ValueError(f'LatticeSU3.{what}: c_sw goes with neither even_odd=False nor mixed=True: the clover solve is '
+                             f'the even-odd preconditioned one, in double precision')
+        solve_kwargs.pop('even_odd', None)
+        solve_kwargs.pop('mixed', None)
+        return {'c_sw': c_sw, 'clover': clover}
+
+    def _clover_checks(self, what: str, kappa, c_sw, *tensors) -> tuple[float, float]:
+        """(kappa, c_sw) as finite floats, after the checks of `_wilson_checks`, on a lattice with even extents"""
+        k = self._wilson_checks(what, kappa, *tensors)
+        try:
+            c = float(c_sw)
+        except (TypeError, ValueError):
+            c = float('nan')
+        if not np.isfinite(c):
+            raise ValueError(f'LatticeSU3.{what}: c_sw must be a finite number, got {c_sw!r}')
+        self._eo_lattice(what)
+        return k, c
+
+    def _clover_for(self, what: str, xn: Tensor, k: float, c: float, clover: Optional[CloverTerm],
+                    inverse: bool = True) -> CloverTerm:
+        """the clover term of xn: built here, or the prebuilt `clover` checked against kappa, c_sw and the batch.
+        inverse: A^-1 is going to be used, so every chain needs min_pivot > 0 (ValueError naming the first that has not)"""
+        if clover is None:
+            clover = self.clover_term_n(xn, k, c)
+        else:
+            shape = (xn.shape[0], 2, 2, 36, self.volume // 2)
+            ok = isinstance(clover, CloverTerm) and clover.kappa == k and clover.c_sw == c \
+                and tuple(clover.a.shape) == shape and tuple(clover.ainv.shape) == shape and clover.a.device == xn.device
+            if not ok:
+                got = (f'kappa {clover.kappa!r}, c_sw {clover.c_sw!r}, blocks {list(clover.a.shape)}'
+                       if isinstance(clover, CloverTerm) else repr(type(clover)))
+                raise ValueError(f'LatticeSU3.{what}: clover= must be the `clover_term` of these links at kappa {k!r}, '
+                                 f'c_sw {c!r} with blocks {list(shape)}, got {got}')
+        if inverse:
+            mp = clover.min_pivot.detach().cpu()
+            bad = torch.nonzero(~(mp > 0)).reshape(-1)
+            if bad.numel():
+                i = int(bad[0])
+                raise ValueError(f'LatticeSU3.{what}: the clover term of chain {i} is not positive definite at kappa '
+                                 f'{k!r}, c_sw {c!r} (smallest L D L^H pivot {float(mp[i])!r}): A_oo^-1 and the Schur '
+                                 f'complement do not exist there')
+        return clover
+
+    def clover_term_n(self, xn: Tensor, kappa: float, c_sw: float) -> CloverTerm:
+        """The clover term A(x) = 1 + kappa c_sw i sum_{mu<nu} sigma_{mu nu} (x) Fhat_{mu nu}(x) of the native links xn and
+        its inverse, as a `CloverTerm`: one `l2q_su3_clover_term` and one `l2q_su3_clover_invert`, once per
+        configuration.  sigma_{mu nu} = (i/2) [gamma_mu, gamma_nu]; Fhat_{mu nu} = (Q_{mu nu} - Q_{mu nu}^H) / 8 of the
+        four-leaf clover sum, NOT made traceless (Sheikholeslami-Wohlert; Luescher et al.: the definition for which
+        published c_sw hold).  c_sw = 0 is legal and gives A = 1.  Even extents.  Never raises on a non-positive pivot:
+        `min_pivot` reports it, and the entry points that need A^-1 raise."""
+        k, c = self._clover_checks('clover_term', kappa, c_sw, xn)
+        L = self._lattice_shape
+        a = ops.su3_clover_term_n(xn, k * c, L)
+        ainv, mp, ld = ops.su3_clover_invert_n(a, L)
+        return CloverTerm(a, ainv, mp.amin((1, 2)), ops.sum_parts(ld), k, c)
+
+    def clover_term(self, x: Tensor, kappa: float, c_sw: float) -> CloverTerm:
+        """`clover_term_n` of links in the reference layout"""
+        self._clover_checks('clover_term', kappa, c_sw, x)
+        return self.clover_term_n(self.pack(x), kappa, c_sw)
+
+    @staticmethod
+    def _clover_dirac_halves(xn: Tensor, pe: Tensor, po: Tensor, k: float, L, dagger, antiperiodic_t,
+                             cl: CloverTerm) -> tuple:
+        """(M_sw psi)_e and (M_sw psi)_o from the halves of psi: A_pp psi_p - kappa H_pq psi_q, one kernel per parity"""
+        return tuple(ops.su3_wilson_clover_hop_eo_n(xn, src, L, p, cl.a, 1, dagger, antiperiodic_t, a=-k, aux=aux, b=1.0)
+                     for p, src, aux in ((0, po, pe), (1, pe, po)))
+
+    def wilson_clover_dirac_n(self, xn: Tensor, psin: Tensor, kappa: float, c_sw: float, dagger: bool = False,
+                              antiperiodic_t: bool = True, clover: Optional[CloverTerm] = None) -> Tensor:
+        """M_sw psi = A psi - kappa H psi (dagger: M_sw^H psi = gamma5 M_sw gamma5 psi) of a native spinor field [nb,
+        nrhs, 12, V] (or [nb, 12, V]): the clover-improved Wilson operator, H as in `wilson_dirac_n`, A as in
+        `clover_term_n` (built here unless `clover` brings it).  Split, one `l2q_su3_wilson_clover_hop_eo` per parity,
+        merge; a new field.  Even extents; no autograd."""
+        k, c = self._clover_checks('wilson_clover_dirac', kappa, c_sw, xn, psin)
+        L = self._lattice_shape
+        p, single = self._spinor_native('wilson_clover_dirac', xn, psin)
+        cl = self._clover_for('wilson_clover_dirac', xn, k, c, clover, inverse=False)
+        pe, po = ops.su3_spinor_split_eo(p, L)
+        out = ops.su3_spinor_merge_eo(*self._clover_dirac_halves(xn, pe, po, k, L, dagger, antiperiodic_t, cl), L)
+        return out[:, 0] if single else out
+
+    def wilson_clover_dirac(self, x: Tensor, psi: Tensor, kappa: float, c_sw: float, dagger: bool = False,
+                            antiperiodic_t: bool = True, clover: Optional[CloverTerm] = None) -> Tensor:
+        """`wilson_clover_dirac_n` in the reference layout"""
+        self._clover_checks('wilson_clover_dirac', kappa, c_sw, x, psi)
+        p, single = self._spinor_reference('wilson_clover_dirac', x, psi)
+        out = ops.su3_spinor_unpack(self.wilson_clover_dirac_n(self.pack(x), p, kappa, c_sw, dagger, antiperiodic_t,
+                                                               clover), self._lattice_shape)
+        return out[:, 0] if single else out
+
+    def wilson_clover_schur_n(self, xn: Tensor, psi_e: Tensor, kappa: float, c_sw: float, dagger: bool = False,
+                              antiperiodic_t: bool = True, clover: Optional[CloverTerm] = None) -> Tensor:
+        """Mhat psi_e = A_ee psi_e - kappa^2 H_eo A_oo^-1 H_oe psi_e (dagger: Mhat^H psi_e) of an even half field [nb,
+        nrhs, 12, V/2] (or [nb, 12, V/2]): the asymmetric Schur complement of M_sw on the even sites.  Two
+        `l2q_su3_wilson_clover_hop_eo`; a new field.  ValueError where a chain's A is not positive definite."""
+        k, c = self._clover_checks('wilson_clover_schur', kappa, c_sw, xn, psi_e)
+        L = self._lattice_shape
+        p, single = self._spinor_native('wilson_clover_schur', xn, psi_e, half=True)
+        cl = self._clover_for('wilson_clover_schur', xn, k, c, clover)
+        out = torch.empty_like(p)
+        _CloverSchurOp(xn, k, L, antiperiodic_t, p, cl).apply(p, out, dagger, norm=False)
+        return out[:, 0] if single else out
+
+    def wilson_clover_schur(self, x: Tensor, psi: Tensor, kappa: float, c_sw: float, dagger: bool = False,
+                            antiperiodic_t: bool = True, clover: Optional[CloverTerm] = None) -> Tensor:
+        """`wilson_clover_schur_n` in the reference layout: psi is a full-shape field of which only the even sites are
+        read; the odd sites of the result are zero."""
+        self._clover_checks('wilson_clover_schur', kappa, c_sw, x, psi)
+        pe, single = self._half_reference('wilson_clover_schur', x, psi)
+        out = self._half_to_reference(self.wilson_clover_schur_n(self.pack(x), pe, kappa, c_sw, dagger, antiperiodic_t,
+                                                                 clover))
+        return out[:, 0] if single else out
+
+    def wilson_clover_solve_n(self, xn: Tensor, bn: Tensor, kappa: float, c_sw: float, tol: float = 1e-10,
+                              max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                              clover: Optional[CloverTerm] = None) -> tuple[Tensor, dict]:
+        """M_sw psi = b for every system (chain, rhs) of the native field bn at once, through the asymmetric even-odd
+        form: bhat_e = b_e + kappa H_eo A_oo^-1 b_o, the CGNR loop of `wilson_solve_eo_n` on Mhat = A_ee - kappa^2 H_eo
+        A_oo^-1 H_oe from zero, psi_o = A_oo^-1 (b_o + kappa H_oe psi_e).  With psi_o reconstructed b - M_sw psi is rhat
+        on the even sites and zero on the odd ones, so the stopping test stays |rhat|^2 <= tol^2 |b|^2 with |b|^2 of the
+        full right-hand side, and tol means what it means everywhere else.  Same freezing, same independence of a
+        system's bits from the batch, same info keys as `wilson_solve_eo_n`; info['residual'] is the full |b - M_sw psi|
+        / |b| recomputed after the reconstruction.  Never raises on non-convergence; b = 0 gives psi = 0.  `clover`: the
+        `clover_term_n` of these links at this kappa and c_sw, so that several solves on one configuration build A and
+        A^-1 once.  ValueError where a chain's A is not positive definite (the message names chain and pivot)."""
+        what = 'wilson_clover_solve'
+        k, c = self._clover_checks(what, kappa, c_sw, xn, bn)
+        _CG.check_args(what, tol, max_iter, check_every)
+        L = self._lattice_shape
+        b, single = self._spinor_native(what, xn, bn)
+        cl = self._clover_for(what, xn, k, c, clover)
+        be, bo = ops.su3_spinor_split_eo(b, L)
+        zero = torch.zeros(b.shape[:2], dtype=torch.float64, device=b.device)
+        spare = torch.zeros_like(be)
+        bb = _norm2(be, bo, spare, zero) + _norm2(bo, be, spare, zero)                 # |b_e|^2 + |b_o|^2
+        bhat = ops.su3_wilson_clover_hop_eo_n(xn, ops.su3_clover_apply_n(cl.ainv, bo, L, 1), L, 0, None, 0, False,
+                                              antiperiodic_t, a=k, aux=be, b=1.0)
+        cg = _CG(what, bhat, single, _CloverSchurOp(xn, k, L, antiperiodic_t, bhat, cl), tol, max_iter, check_every, bb=bb)
+        cg.cgnr()
+        psio = ops.su3_wilson_clover_hop_eo_n(xn, cg.x, L, 1, cl.ainv, 2, False, antiperiodic_t, a=k, aux=bo, b=1.0)
+        psi = ops.su3_spinor_merge_eo(cg.x, psio, L)
+        mpsi = ops.su3_spinor_merge_eo(*self._clover_dirac_halves(xn, cg.x, psio, k, L, False, antiperiodic_t, cl), L)
+        return (psi[:, 0] if single else psi), cg.info(_residual(b.clone(), torch.zeros_like(b), mpsi, mpsi, bb))
+
+    def wilson_clover_solve(self, x: Tensor, b: Tensor, kappa: float, c_sw: float, tol: float = 1e-10,
+                            max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                            clover: Optional[CloverTerm] = None) -> tuple[Tensor, dict]:
+        """`wilson_clover_solve_n` in the reference layout"""
+        self._clover_checks('wilson_clover_solve', kappa, c_sw, x, b)
+        _CG.check_args('wilson_clover_solve', tol, max_iter, check_every)
+        bn, single = self._spinor_reference('wilson_clover_solve', x, b)
+        psin, info = self.wilson_clover_solve_n(self.pack(x), bn, kappa, c_sw, tol, max_iter, check_every,
+                                                antiperiodic_t, clover)
+        psi = ops.su3_spinor_unpack(psin, self._lattice_shape)
+        return (psi[:, 0] if single else psi), info
 
     # ------------------------------------------------------------ dynamical Wilson fermions: pseudofermions
     def _pf_checks(self, what: str, kappa, *tensors) -> float:

@@ -19,7 +19,11 @@
                 --eo: per launch the fp32 hop with and without aux + norm beside the fp64 hop of the same session, the fp32
                 update / xpay, demote / promote and the link copy; one CGNR iteration on Mhat in fp32 beside fp64; and the
                 time to solution, inner iterations and outer cycles of `wilson_solve_eo_mixed_n` and
-                `wilson_solve_schur_normal_mixed_n` at each --inner-tol beside their fp64 siblings."""
+                `wilson_solve_schur_normal_mixed_n` at each --inner-tol beside their fp64 siblings;
+  --clover      the clover term (csrc/su3_wilson_clover.hip, profiles/su3_wilson_clover.md) at --c-sw (1.0) on the inputs
+                of --eo: `clover_term` + `clover_invert`; the two hops of the clover Mhat beside the two of the plain Mhat
+                on the same links, with the algorithmic bytes of both; the site-local apply; and the time to solution of
+                `wilson_clover_solve_n` beside `wilson_solve_eo_n`."""
 import argparse
 import os
 import statistics
@@ -309,6 +313,78 @@ def mixed(nb, L, nrhs_list, iters, repeats, therm, kappa, tol, inner_tols):
         del psi, pe
 
 
+BLOCKS = 2 * 36 * 8     # bytes of the two Hermitian 6 x 6 blocks of a site
+
+
+def clover(nb, L, nrhs_list, iters, repeats, therm, kappa, tol, c_sw):
+    """--clover: the clover term (csrc/su3_wilson_clover.hip, profiles/su3_wilson_clover.md) on the inputs of --eo"""
+    V = L[0] * L[1] * L[2] * L[3]
+    Vh = V // 2
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    lat = LatticeSU3(nb, L)
+    xn = lat.pack(lat.heatbath(lat.random().to(dev), 6.0, nsweeps=therm, nover=3)[0])
+    print(f'{L} x {nb} chains, beta 6.0 after {therm} heatbath sweeps (nover 3): plaquette '
+          f'{float(lat.plaq_sums_n(xn)[:, 0].mean()) / (18.0 * V):.5f}; kappa {kappa}, c_sw {c_sw}, tol {tol}')
+    cl = ops.su3_clover_term_n(xn, kappa * c_sw, L)
+    inv = torch.empty_like(cl)
+    # once per configuration: per site 18 links of each of 6 planes come from cache, 576 B of links and 576 B of blocks are
+    # compulsory; the inverse reads and writes 576 B per site
+    tt = show('clover_term (A, both parities)', windows(lambda: ops.su3_clover_term_n(xn, kappa * c_sw, L, out=cl), iters, repeats),
+              LINKS + BLOCKS, nb * V)
+    tv = show('clover_invert (A^-1, pivots, log det)', windows(lambda: ops.su3_clover_invert_n(cl, L, out=inv), iters, repeats),
+              2 * BLOCKS, nb * V)
+    term = lat.clover_term_n(xn, kappa, c_sw)
+    print(f'  clover_term + clover_invert {(tt + tv) * 1e3:.3f} ms per configuration batch; smallest pivot '
+          f'{float(term.min_pivot.min()):.4f}, log det A_oo per chain {float(term.logdet[:, 1].mean()):.4f}')
+    for nrhs in nrhs_list:
+        hsites = nb * nrhs * Vh
+        he, ho, hq = (torch.empty((nb, nrhs, 12, Vh), dtype=torch.complex128, device=dev) for _ in range(3))
+        he.copy_(torch.randn_like(he))
+        hpart = torch.empty((nb, nrhs, -(-Vh // 256)), dtype=torch.float64, device=dev)
+        print(f'lattice {L} x {nb} chains x {nrhs} right-hand sides, {iters} calls per window, {repeats} windows')
+        b1, b2 = 2 * SPINOR + 2 * LINKS / nrhs, 3 * SPINOR + 2 * LINKS / nrhs
+        p1 = show('plain hop (a = 1, no aux), odd sites', windows(lambda: ops.su3_wilson_hop_eo_n(xn, he, L, 1, out=ho), iters, repeats),
+                  b1, hsites)
+        p2 = show('plain hop (aux, fused norm), even sites',
+                  windows(lambda: ops.su3_wilson_hop_eo_n(xn, ho, L, 0, a=-kappa * kappa, aux=he, b=1.0, out=hq, norm=hpart),
+                          iters, repeats), b2, hsites)
+        z1 = show('clover hop, cmode 0 (the plain hop), odd sites',
+                  windows(lambda: ops.su3_wilson_clover_hop_eo_n(xn, he, L, 1, None, 0, out=ho), iters, repeats), b1, hsites)
+        c1 = show('clover hop, cmode 2 (A_oo^-1 on the result), odd sites',
+                  windows(lambda: ops.su3_wilson_clover_hop_eo_n(xn, he, L, 1, term.ainv, 2, out=ho), iters, repeats),
+                  b1 + BLOCKS / nrhs, hsites)
+        c2 = show('clover hop, cmode 1 (A_ee on aux, fused norm), even sites',
+                  windows(lambda: ops.su3_wilson_clover_hop_eo_n(xn, ho, L, 0, term.a, 1, a=-kappa * kappa, aux=he, b=1.0,
+                                                                 out=hq, norm=hpart), iters, repeats), b2 + BLOCKS / nrhs, hsites)
+        show('clover_apply (A_oo^-1 src), odd sites', windows(lambda: ops.su3_clover_apply_n(term.ainv, he, L, 1, out=ho),
+                                                             iters, repeats), 2 * SPINOR + BLOCKS / nrhs, hsites)
+        plain_b, clover_b = b1 + b2, b1 + b2 + 2 * BLOCKS / nrhs
+        print(f'  clover Mhat {(c1 + c2) * 1e3:.3f} ms against the plain Mhat {(p1 + p2) * 1e3:.3f} ms: time ratio '
+              f'{(c1 + c2) / (p1 + p2):.3f}; algorithmic bytes per (system, even site) {clover_b:.0f} against {plain_b:.0f}: '
+              f'byte ratio {clover_b / plain_b:.3f}; cmode 0 against the plain hop {z1 / p1:.3f}')
+        del he, ho, hq
+        psi = torch.randn((nb, nrhs, 12, V), dtype=torch.complex128, device=dev)
+        kw = dict(tol=tol, max_iter=2000)
+
+        def timed(name, fn):
+            fn()                                                    # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            info = res[-1]
+            print(f'{name:44s} {dt * 1e3:9.1f} ms  iterations {int(info["iters"].min())} .. {int(info["iters"].max())}, '
+                  f'residual <= {float(info["residual"].max()):.3g}, all converged {bool(info["converged"].all())}')
+            return dt
+        tp = timed('wilson_solve_eo_n', lambda: lat.wilson_solve_eo_n(xn, psi, kappa, **kw))
+        tc = timed('wilson_clover_solve_n (prebuilt term)', lambda: lat.wilson_clover_solve_n(xn, psi, kappa, c_sw, clover=term, **kw))
+        tb = timed('wilson_clover_solve_n (builds the term)', lambda: lat.wilson_clover_solve_n(xn, psi, kappa, c_sw, **kw))
+        print(f'  time to solution, clover / plain even-odd: {tc / tp:.2f} (building the term included: {tb / tp:.2f})')
+        del psi
+
+
 def torch_apply(x, psi, kappa, gam):
     """M psi from roll / einsum on reference-layout tensors (antiperiodic in t)"""
     eye = torch.eye(4, dtype=psi.dtype, device=psi.device)
@@ -385,6 +461,8 @@ def main():
     ap.add_argument('--eo-therm', type=int, default=10)
     ap.add_argument('--mixed', action='store_true')
     ap.add_argument('--inner-tol', type=float, nargs='+', default=[1e-3, 1e-4, 1e-5, 1e-6])
+    ap.add_argument('--clover', action='store_true')
+    ap.add_argument('--c-sw', type=float, default=1.0)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
@@ -396,6 +474,8 @@ def main():
         even_odd(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol)
     if args.mixed:
         mixed(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol, args.inner_tol)
+    if args.clover:
+        clover(args.nb, args.L, args.nrhs, args.iters, args.repeats, args.eo_therm, args.eo_kappa, args.eo_tol, args.c_sw)
     if args.propagator:
         propagator(args.physics_nb, args.L, args.therm, args.kappa)
 
