@@ -547,6 +547,37 @@ int l2q_su3_wilson_clover_hop_eo(const void* xn, const void* src, const void* au
  * L2Q_ESHAPE: an odd extent. */
 int l2q_su3_clover_apply(const void* c, const void* src, void* out, double* norm_part, int parity, int nb, int nrhs,
                          int T, int X, int Y, int Z, void* stream);
+/* csrc/su3_clover_force.hip.  The clover part of the force of two flavours of dynamical clover quarks per pseudofermion
+ * field, in the asymmetric even-odd form (Jansen & Liu), conventions of l2q_su3_wilson_force (dU/dt = p U, dS/dt = sum
+ * <p, F>):
+ *   S_f = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r - 2 npf log det A_oo,   det M_sw = det A_oo det Mhat.
+ * With X_e = (Mhat^H Mhat)^-1 phi_e and Y_e = Mhat X_e completed by X_o = kappa A_oo^-1 H_oe X_e and
+ * Y_o = kappa A_oo^-1 (H^H)_oe Y_e (one l2q_su3_wilson_clover_hop_eo each: cmode 2, c = A^-1, parity 1, the second with
+ * the dagger bit),
+ *   dS_pf  = -2 Re[Y^H dM_sw X] = 2 kappa Re[Y^H dH X] - 2 Re sum_x Y(x)^H dA(x) X(x),
+ *   dS_det = -2 npf sum_{x odd} tr[A^-1(x) dA(x)],   dA(x) = kappa c_sw i sum_{mu<nu} sigma_{mu nu} (x) dFhat_{mu nu}(x).
+ * The hop part is l2q_su3_wilson_force on the merged (X, Y).  This entry is the rest: with a b^H the colour outer product
+ * summed over spin and
+ *   Lambda_{mu nu}(x) = i sum_r (sigma_{mu nu} X_r)(x) Y_r(x)^H + [x odd] det_weight i tr_spin[sigma_{mu nu} A^-1(x)],
+ * it is -2 kc sum_x sum_{mu<nu} Re tr[dFhat_{mu nu}(x) Lambda_{mu nu}(x)], kc = kappa c_sw.  Only the anti-Hermitian part of
+ * Lambda contributes (with its trace: Fhat keeps its own), and Re tr(Lambda dFhat) = 1/4 Re tr(Lambda_AH dQ).
+ *   f_out = (f_in ? f_in : 0) + coef F_sw,   F_sw = -TAH(U_mu(x) B_mu(x)),   dS = sum Re tr(B_mu(x) dU_mu(x)),
+ * f_in, coef and the in-place use (f_in == f_out) as in l2q_su3_wilson_force; F_sw is stored exactly anti-Hermitian.
+ * X, Y: full native fields [nb][npf][12][V], or both null with npf = 0: the determinant term alone.  clinv: the block
+ * field of A^-1 (l2q_su3_clover_invert; its parity-1 half is read, entry s >> 1 for the odd site s), or null: the
+ * pseudofermion term alone.  det_weight multiplies the determinant term: npf of the action above.
+ * Two kernels, both gathers, no atomics: one thread per (chain, site) writes G = -(kc / 2) Lambda_AH as 6 planes x 9 reals
+ * into ws[nb][6][9][V] (planes (01) (23) (02) (13) (03) (12); npf * 384 B of spinors and 2 x 288 B of blocks on odd sites
+ * in, 432 B out), the sum over r in its order; one thread per link inserts G into the four clover leaves (the gather of
+ * l2q_su3_clover_bwd) and projects.  A chain's force is the same bits alone and in a batch, and from run to run.  All
+ * four extents even (2 is legal: every geometric occurrence is its own term, as in the forward), L2Q_ESHAPE otherwise.
+ * ws_bytes >= nb * 54 * V * sizeof(double).
+ * L2Q_EINVAL, before any HIP call: a null xn, f_out or ws; X or Y null with npf > 0 or given with npf = 0, npf < 0; both
+ * halves absent (npf = 0 and clinv null); f_out aliasing xn, X, Y, clinv or ws; ws aliasing xn, X, Y, clinv or f_in; a
+ * non-positive size; nb * npf * 12 * V of 2^31 or more; kc, coef or det_weight not finite; the workspace too small. */
+int l2q_su3_clover_force(const void* xn, const void* X, const void* Y, const void* clinv, const void* f_in, void* f_out,
+                         double kc, double coef, double det_weight, int nb, int npf, int T, int X_, int Y_, int Z,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- L2HMC momentum update */
 /* Generalised v-update with real network heads s, t, q [nb][n] applied entry-wise:

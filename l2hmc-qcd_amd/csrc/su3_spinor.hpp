@@ -101,6 +101,32 @@ __device__ __forceinline__ void wilson_reconstruct(double (&ar)[12], double (&ai
   }
 }
 
+// fout = (fin ? fin : 0) + cf TAH(w) at site s of one link's nine planes, the epilogue of the fermion forces
+// (su3_wilson_force.hip, su3_clover_force.hip).  TAH(w) is stored exactly anti-Hermitian: the two planes of a transposed
+// pair get one number and its negative, the diagonal no real part.  fin may be fout: an entry is read before it is
+// written, by its own thread.
+__device__ __forceinline__ void store_tah_axpy(const double2* fin, double2* fout, int V, int s, double cf,
+                                               const M3& w) {
+  const double tr3 = (w.im[0] + w.im[4] + w.im[8]) / 3.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int e = 4 * i;
+    const double2 in = fin ? fin[e * V + s] : make_double2(0.0, 0.0);
+    fout[e * V + s] = make_double2(in.x, fma(cf, w.im[e] - tr3, in.y));
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i + 1; j < 3; ++j) {
+      const int e = 3 * i + j, et = 3 * j + i;
+      const double ar = 0.5 * (w.re[e] - w.re[et]), ai = 0.5 * (w.im[e] + w.im[et]);
+      const double2 in = fin ? fin[e * V + s] : make_double2(0.0, 0.0);
+      const double2 it = fin ? fin[et * V + s] : make_double2(0.0, 0.0);
+      fout[e * V + s] = make_double2(fma(cf, ar, in.x), fma(cf, ai, in.y));
+      fout[et * V + s] = make_double2(fma(cf, -ar, it.x), fma(cf, ai, it.y));
+    }
+}
+
 // the system and the site block of workgroup w: chain, site block, right-hand side (the fastest)
 struct WilsonBlock {
   long c, sys;

@@ -75,24 +75,7 @@ __device__ __forceinline__ void wilson_force_link(const double2* __restrict__ um
   M3 u, w;
   load_link(u, um, V, s);
   m3_mul_nn(w, u, c);
-  const double tr3 = (w.im[0] + w.im[4] + w.im[8]) / 3.0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int e = 4 * i;
-    const double2 in = fin ? fin[e * V + s] : make_double2(0.0, 0.0);
-    fout[e * V + s] = make_double2(in.x, fma(cf, w.im[e] - tr3, in.y));
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = i + 1; j < 3; ++j) {
-      const int e = 3 * i + j, et = 3 * j + i;
-      const double ar = 0.5 * (w.re[e] - w.re[et]), ai = 0.5 * (w.im[e] + w.im[et]);
-      const double2 in = fin ? fin[e * V + s] : make_double2(0.0, 0.0);
-      const double2 it = fin ? fin[et * V + s] : make_double2(0.0, 0.0);
-      fout[e * V + s] = make_double2(fma(cf, ar, in.x), fma(cf, ai, in.y));
-      fout[et * V + s] = make_double2(fma(cf, -ar, it.x), fma(cf, ai, it.y));
-    }
+  store_tah_axpy(fin, fout, V, s, cf, w);
 }
 
 // cf = -2 kappa coef; apbc: the seam of direction 0 carries -1; fin may be null or fout

@@ -1016,6 +1016,43 @@ def su3_clover_apply_n(c: torch.Tensor, src: torch.Tensor, lat: Sequence[int], p
     return out if part is None else (out, part)
 
 
+def su3_clover_force_n(xn: torch.Tensor, X: Optional[torch.Tensor], Y: Optional[torch.Tensor],
+                       clinv: Optional[torch.Tensor], kc: float, lat: Sequence[int], det_weight: float = 0.0,
+                       coef: float = 1.0, f_in: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (f_in or 0) + coef F_sw: the clover part of the force of dynamical clover quarks (`l2q_su3_clover_force`, see
+    l2q.h), kc = kappa c_sw.  X, Y [nb, npf, 12, V]: the completed solutions, or both None (the determinant term alone);
+    clinv: the block field of A^-1, or None (the pseudofermion term alone); det_weight: npf of the action.  coef, f_in
+    and out as in `su3_wilson_force_n`: f_in = out = vn is the kick in place."""
+    what = 'su3_clover_force_n'
+    T, X_, Y_, Z = _even_lattice(what, lat)
+    V = T * X_ * Y_ * Z
+    if (X is None) != (Y is None):
+        raise ValueError(f'{what}: X and Y come together or not at all')
+    if X is None and clinv is None:
+        raise ValueError(f'{what}: need the fields X, Y, the blocks clinv, or both')
+    for name, t in (('xn', xn), ('f_in', f_in), ('out', out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != C128 or t.dim() != 4
+                              or tuple(t.shape) != (xn.shape[0], 4, 9, V) or not t.is_contiguous()):
+            raise ValueError(f'{what}: {name} must be contiguous complex128 [nb, 4, 9, V] on {list(lat)}, got '
+                             f'{getattr(t, "dtype", type(t))} {list(getattr(t, "shape", []))}')
+    nb, npf = xn.shape[0], 0
+    if X is not None:
+        if X.dim() != 4 or X.shape[0] != nb or X.shape[1] < 1 or X.shape[2] != 12 or X.shape[3] != V:
+            raise ValueError(f'{what}: need X [nb, npf, 12, V] on xn {list(xn.shape)}, got {list(X.shape)}')
+        _spinor_check(what, 'X', X, X.shape)
+        _spinor_check(what, 'Y', Y, X.shape)
+        npf = X.shape[1]
+    if clinv is not None:
+        _clover_field_check(what, 'clinv', clinv, nb, V // 2)
+    if out is None:
+        out = torch.empty_like(xn)
+    ws = _ws(nb, 54 * V * 64, xn.device)       # 54 V doubles per chain; _ws counts 32 bytes per 256 items
+    N.call('l2q_su3_clover_force', xn, X, Y, clinv, f_in, out, float(kc), float(coef), float(det_weight), nb, npf,
+           T, X_, Y_, Z, ws, ws.numel())
+    return out
+
+
 def sum_parts(part: torch.Tensor) -> torch.Tensor:
     """[..., parts] -> [...] by a pairwise tree of element-wise additions: the bits of an entry depend on its own
     partials only, not on the batch around it (which a library reduction does not promise).  Always a new tensor."""

@@ -1,7 +1,8 @@
 """HMC with two flavours of dynamical Wilson quarks (Duane et al. 1987; Gottlieb et al. 1987): the gauge action plus
 the pseudofermion action S_f = sum_r phi_r^H (M^H M)^-1 phi_r, which puts det(M^H M)^npf into the ensemble.  Built from
 the lattice's kernels: the gauge force kick, `l2q_su3_wilson_force` behind a CG on M^H M, the expm link update, the
-kinetic-energy reduction and the accept step.  Plain leapfrog, every solve from zero (a chronological guess would break
+kinetic-energy reduction and the accept step.  `WilsonCloverHMC`: the same with clover-improved sea quarks
+(`l2q_su3_clover_force`, the log det A_oo term).  Plain leapfrog, every solve from zero (a chronological guess would break
 reversibility at a finite solver tolerance).  Not wired into `Dynamics`, the trainer or the CLI; see INTEGRATION.md,
 "Dynamical Wilson fermions", for what is deliberately left out."""
 from __future__ import annotations
@@ -77,6 +78,12 @@ class WilsonHMC:
         unconv = sum(int((~i['converged']).sum()) for i in infos)
         return xn, vn, {'cg_iters': iters, 'unconverged': unconv}
 
+    def _refresh_n(self, xn: Tensor, generator: Optional[torch.Generator]) -> tuple[Tensor, Tensor]:
+        """(phi, S_f(phi) on xn) of the pseudofermion heatbath"""
+        lat = self.lattice
+        refresh = lat.pseudofermion_refresh_eo_n if self.even_odd else lat.pseudofermion_refresh_n
+        return refresh(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
+
     def hamiltonian_n(self, xn: Tensor, vn: Tensor, phin: Tensor, info: Optional[dict] = None) -> Tensor:
         """H [nb] = kinetic + S_g + S_f, the solve at tol_h; `info`, if given, receives the solve's info"""
         sf, sinfo = self.lattice.pseudofermion_action_n(xn, phin, self.kappa, even_odd=self.even_odd,
@@ -94,8 +101,7 @@ class WilsonHMC:
         nb = xn.shape[0]
         xn = xn.detach().contiguous()
         vn = ops.su3_assemble_tah_n(draw((8, nb, 4, lat.volume), generator, xn.device))
-        refresh = lat.pseudofermion_refresh_eo_n if self.even_odd else lat.pseudofermion_refresh_n
-        phin, s0 = refresh(xn, self.kappa, self.npf, generator, self.antiperiodic_t)
+        phin, s0 = self._refresh_n(xn, generator)
         h0 = ops.su3_kinetic_n(vn) + lat.action_n(xn, self.beta) + s0             # S_f(phi) = |eta|^2: no solve
         x1, v1, info = self.leapfrog_n(xn, vn, phin)
         hinfo: dict = {}
@@ -158,3 +164,55 @@ class WilsonHMCMixed(WilsonHMCEvenOdd):
 
     def _solve_kw(self, tol: float) -> dict:
         return dict(super()._solve_kw(tol), mixed=True, **self.mixed_kw)
+
+
+class WilsonCloverHMC(WilsonHMCEvenOdd):
+    """`WilsonHMCEvenOdd` with O(a)-improved (Sheikholeslami-Wohlert) sea quarks at the clover coefficient `c_sw`, in the
+    asymmetric even-odd form (Jansen & Liu 1997; same draw order, same metrics):
+        S_f = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r - 2 npf log det A_oo,   Mhat = A_ee - kappa^2 H_eo A_oo^-1 H_oe,
+    which puts det(M_sw^H M_sw)^npf into the ensemble.  One `clover_term_n` per kick and per Hamiltonian, shared by the
+    solve, the completion hops and `l2q_su3_clover_force`; both fermion kicks go in place into the momentum.  The
+    determinant term is part of `hamiltonian_n` and of H0.  A clover term that is not positive definite raises (the
+    ValueError of `LatticeSU3.wilson_clover_solve_n`, naming chain and pivot).  Double precision only."""
+
+    def __init__(self, lattice: LatticeSU3, beta: float, kappa: float, c_sw: float, eps: float, nleapfrog: int,
+                 **kwargs) -> None:
+        super().__init__(lattice, beta, kappa, eps, nleapfrog, **kwargs)
+        if isinstance(c_sw, bool) or not isinstance(c_sw, (int, float, np.floating, np.integer)) or not np.isfinite(c_sw):
+            raise ValueError(f'WilsonCloverHMC: c_sw must be a finite number, got {c_sw!r}')
+        self.c_sw = float(c_sw)
+
+    def _clover(self, xn: Tensor):
+        """the clover term of xn, positive definite or ValueError"""
+        lat = self.lattice
+        return lat._clover_for('WilsonCloverHMC', xn, self.kappa, self.c_sw, lat.clover_term_n(xn, self.kappa, self.c_sw))
+
+    def _kick_(self, xn: Tensor, vn: Tensor, phin: Tensor, step: float, infos: list) -> None:
+        """vn -= step * (F_g + F_f), in place: the gauge kick, then the hop and the clover part of the fermion kick"""
+        lat, L = self.lattice, self.lattice._lattice_shape
+        if lat.c1 == 0:
+            ops.su3_force_kick_n(xn, self.beta, -step, vn, L)
+        else:
+            ops.axpy_(vn, lat.grad_action_n(xn, self.beta), -step)
+        cl = self._clover(xn)
+        X, Y, info = lat._clover_force_fields_n(xn, phin, self.kappa, self.c_sw, cl, **self._solve_kw(self.tol_md))
+        ops.su3_wilson_force_n(xn, X, Y, self.kappa, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
+        ops.su3_clover_force_n(xn, X, Y, cl.ainv, self.kappa * self.c_sw, L, det_weight=self.npf, coef=-step, f_in=vn,
+                               out=vn)
+        infos.append(info)
+
+    def hamiltonian_n(self, xn: Tensor, vn: Tensor, phin: Tensor, info: Optional[dict] = None) -> Tensor:
+        """H [nb] = kinetic + S_g + S_f with its determinant term, the solve at tol_h"""
+        sf, sinfo = self.lattice.clover_pseudofermion_action_n(xn, phin, self.kappa, self.c_sw, self._clover(xn),
+                                                               **self._solve_kw(self.tol_h))
+        if info is not None:
+            info.update(sinfo)
+        return ops.su3_kinetic_n(vn) + self.lattice.action_n(xn, self.beta) + sf
+
+    def _refresh_n(self, xn: Tensor, generator: Optional[torch.Generator]) -> tuple[Tensor, Tensor]:
+        """(phi_e, S_f(phi_e) on xn): the heatbath's |eta_e|^2 plus the determinant term -- one clover term, no solve"""
+        lat = self.lattice
+        cl = self._clover(xn)
+        phin, s0 = lat.clover_pseudofermion_refresh_n(xn, self.kappa, self.c_sw, self.npf, generator, self.antiperiodic_t,
+                                                      cl)
+        return phin, s0 + lat._clover_logdet_part(cl, self.npf)

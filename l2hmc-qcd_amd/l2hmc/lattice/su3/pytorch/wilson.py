@@ -1,5 +1,5 @@
 """The host side of the Wilson fermions on `LatticeSU3` (kernels: csrc/su3_wilson.hip, csrc/su3_wilson_eo.hip,
-csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip, csrc/su3_wilson_clover.hip): the mixin ``WilsonFermions`` with the
+csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip, csrc/su3_wilson_clover.hip, csrc/su3_clover_force.hip): the mixin ``WilsonFermions`` with the
 operator, the two solvers on one CG loop (``_CG``), their even-odd and mixed-precision forms (``_MixedSolve``: fp64 defect
 correction around the same loop on fp32 fields), the clover-improved operator and its even-odd solve (``CloverTerm``,
 ``_CloverSchurOp``), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
@@ -883,7 +883,9 @@ class WilsonFermions:
         12, V/2, 2), phi_e = Mhat^H eta_e.  Returns (phi_e [nb, npf, 12, V/2], S0 [nb]), S0 = |eta_e|^2."""
         return self._pf_refresh_n('pseudofermion_refresh_eo', xn, kappa, npf, generator, antiperiodic_t, True)
 
-    def _pf_refresh_n(self, what: str, xn: Tensor, kappa, npf, generator, antiperiodic_t, even_odd: bool):
+    def _pf_refresh_n(self, what: str, xn: Tensor, kappa, npf, generator, antiperiodic_t, even_odd: bool,
+                      cl: Optional[CloverTerm] = None):
+        """cl (with even_odd): the clover term, and phi_e = Mhat^H eta_e on the Schur complement of M_sw"""
         k = self._pf_checks(what, kappa, xn)
         if isinstance(npf, bool) or not isinstance(npf, (int, np.integer)) or int(npf) < 1:
             raise ValueError(f'LatticeSU3.{what}: npf must be an integer >= 1, got {npf!r}')
@@ -893,7 +895,8 @@ class WilsonFermions:
         eta = torch.view_as_complex(draw(shape, generator, xn.device) * float(np.sqrt(0.5))).contiguous()
         if even_odd:
             phi = torch.empty_like(eta)
-            _SchurOp(xn, k, L, antiperiodic_t, eta).apply(eta, phi, True, norm=False)
+            op = _SchurOp(xn, k, L, antiperiodic_t, eta) if cl is None else _CloverSchurOp(xn, k, L, antiperiodic_t, eta, cl)
+            op.apply(eta, phi, True, norm=False)
         else:
             phi = ops.su3_wilson_apply_n(xn, eta, k, self._lattice_shape, True, antiperiodic_t)
         zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
@@ -972,4 +975,125 @@ class WilsonFermions:
         self._pop_mixed('pseudofermion_force', dict(solve_kwargs), even_odd)
         pn = self._pf_field('pseudofermion_force', x, phi, even_odd, native=False)
         F, s, info = self.pseudofermion_force_n(self.pack(x), pn, kappa, even_odd=even_odd, **solve_kwargs)
+        return self.unpack(F), s, info
+
+    # ------------------------------------------------------------ dynamical clover quarks: pseudofermions
+    def _clover_pf_checks(self, what: str, kappa, c_sw, *tensors) -> tuple[float, float]:
+        """(kappa, c_sw) after the checks of `_pf_checks` and `_clover_checks`"""
+        self._pf_checks(what, kappa, *tensors)
+        return self._clover_checks(what, kappa, c_sw, *tensors)
+
+    def wilson_clover_solve_schur_normal_n(self, xn: Tensor, phi_e: Tensor, kappa: float, c_sw: float, tol: float = 1e-10,
+                                           max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                                           clover: Optional[CloverTerm] = None) -> tuple[Tensor, Tensor, dict]:
+        """Mhat^H Mhat X_e = phi_e for every system of the even half field phi_e at once, and Y_e = Mhat X_e, on the
+        asymmetric Schur complement Mhat = A_ee - kappa^2 H_eo A_oo^-1 H_oe of the clover-improved operator:
+        `wilson_solve_schur_normal_n` with `_CloverSchurOp`, the same loop.  Returns (X_e, Y_e, info), info as there with
+        info['action'] = |Y_e|^2.  `clover` as in `wilson_clover_solve_n`.  ValueError where a chain's A is not positive
+        definite.  Double precision only."""
+        what = 'wilson_clover_solve_schur_normal'
+        k, c = self._clover_pf_checks(what, kappa, c_sw, xn, phi_e)
+        _CG.check_args(what, tol, max_iter, check_every)
+        L = self._lattice_shape
+        b, single = self._spinor_native(what, xn, phi_e, half=True)
+        cl = self._clover_for(what, xn, k, c, clover)
+        op = _CloverSchurOp(xn, k, L, antiperiodic_t, b, cl)
+        return self._solve_normal(_CG(what, b, single, op, tol, max_iter, check_every))
+
+    def wilson_clover_solve_schur_normal(self, x: Tensor, phi: Tensor, kappa: float, c_sw: float, tol: float = 1e-10,
+                                         max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                                         clover: Optional[CloverTerm] = None) -> tuple[Tensor, Tensor, dict]:
+        """`wilson_clover_solve_schur_normal_n` in the reference layout: of the full-shape phi only the even sites are
+        read; the odd sites of X_e and Y_e are zero"""
+        self._clover_pf_checks('wilson_clover_solve_schur_normal', kappa, c_sw, x, phi)
+        pe, single = self._half_reference('wilson_clover_solve_schur_normal', x, phi)
+        X, Y, info = self.wilson_clover_solve_schur_normal_n(self.pack(x), pe, kappa, c_sw, tol, max_iter, check_every,
+                                                             antiperiodic_t, clover)
+        X, Y = (self._half_to_reference(f) for f in (X, Y))
+        return (X[:, 0], Y[:, 0], info) if single else (X, Y, info)
+
+    def clover_pseudofermion_refresh_n(self, xn: Tensor, kappa: float, c_sw: float, npf: int = 1,
+                                       generator: Optional[torch.Generator] = None, antiperiodic_t: bool = True,
+                                       clover: Optional[CloverTerm] = None) -> tuple[Tensor, Tensor]:
+        """The heatbath of the pseudofermion part of the clover action (see `clover_pseudofermion_action_n`): eta_e drawn
+        by the rule of `pseudofermion_refresh_eo_n`, phi_e = Mhat^H eta_e on the Schur complement of M_sw.  Returns (phi_e
+        [nb, npf, 12, V/2], S0 [nb]), S0 = |eta_e|^2: the pseudofermion part of S_f on these links without a solve (the
+        determinant part is not in it).  The clover term is built, and checked, before anything is drawn."""
+        what = 'clover_pseudofermion_refresh'
+        k, c = self._clover_pf_checks(what, kappa, c_sw, xn)
+        cl = self._clover_for(what, xn, k, c, clover)
+        return self._pf_refresh_n(what, xn, k, npf, generator, antiperiodic_t, True, cl)
+
+    def clover_pseudofermion_refresh(self, x: Tensor, kappa: float, c_sw: float, npf: int = 1,
+                                     generator: Optional[torch.Generator] = None, antiperiodic_t: bool = True,
+                                     clover: Optional[CloverTerm] = None) -> tuple[Tensor, Tensor]:
+        """`clover_pseudofermion_refresh_n` in the reference layout: the full shape phi[nb, npf, T, X, Y, Z, 4, 3], phi_e
+        on the even sites and zero on the odd ones"""
+        self._clover_pf_checks('clover_pseudofermion_refresh', kappa, c_sw, x)
+        phi, s0 = self.clover_pseudofermion_refresh_n(self.pack(x), kappa, c_sw, npf, generator, antiperiodic_t, clover)
+        return self._half_to_reference(phi), s0
+
+    @staticmethod
+    def _clover_logdet_part(cl: CloverTerm, npf: int) -> Tensor:
+        """-2 npf log det A_oo [nb]"""
+        return -2.0 * npf * cl.logdet[:, 1]
+
+    def clover_pseudofermion_action_n(self, xn: Tensor, phi_e: Tensor, kappa: float, c_sw: float,
+                                      clover: Optional[CloverTerm] = None, **solve_kwargs) -> tuple[Tensor, dict]:
+        """The action of two flavours of clover-improved quarks per pseudofermion field, in the asymmetric even-odd form:
+            S_f = sum_r phi_e,r^H (Mhat^H Mhat)^-1 phi_e,r - 2 npf log det A_oo,
+        which puts det(M_sw^H M_sw)^npf = (det A_oo det Mhat)^(2 npf) into the ensemble.  One
+        `wilson_clover_solve_schur_normal_n` (whose keywords the others are).  Returns (S_f [nb], info): the solve's info
+        with info['action'] [nb, npf] the pseudofermion part per field and info['logdet'] [nb] the determinant part."""
+        what = 'clover_pseudofermion_action'
+        k, c = self._clover_pf_checks(what, kappa, c_sw, xn, phi_e)
+        b = self._spinor_native(what, xn, phi_e, half=True)[0]
+        cl = self._clover_for(what, xn, k, c, clover)
+        info = self.wilson_clover_solve_schur_normal_n(xn, b, k, c, clover=cl, **solve_kwargs)[2]
+        info['logdet'] = self._clover_logdet_part(cl, b.shape[1])
+        return self._sum_fields(info['action']) + info['logdet'], info
+
+    def clover_pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, c_sw: float,
+                                    clover: Optional[CloverTerm] = None, **solve_kwargs) -> tuple[Tensor, dict]:
+        """`clover_pseudofermion_action_n` in the reference layout; only the even sites of phi are read"""
+        self._clover_pf_checks('clover_pseudofermion_action', kappa, c_sw, x, phi)
+        pe = self._half_reference('clover_pseudofermion_action', x, phi)[0]
+        return self.clover_pseudofermion_action_n(self.pack(x), pe, kappa, c_sw, clover, **solve_kwargs)
+
+    def _clover_force_fields_n(self, xn: Tensor, b: Tensor, k: float, c: float, cl: CloverTerm,
+                               **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """(X, Y, info): X_e, Y_e of `wilson_clover_solve_schur_normal_n` on the half field b [nb, npf, 12, V/2], completed
+        by X_o = kappa A_oo^-1 H_oe X_e and Y_o = kappa A_oo^-1 (H^H)_oe Y_e (one hop each) and merged: the full fields
+        whose `l2q_su3_wilson_force` plus `l2q_su3_clover_force` is the force of the clover action (see l2q.h)"""
+        L = self._lattice_shape
+        ap = solve_kwargs.get('antiperiodic_t', True)
+        Xe, Ye, info = self.wilson_clover_solve_schur_normal_n(xn, b, k, c, clover=cl, **solve_kwargs)
+        Xo = ops.su3_wilson_clover_hop_eo_n(xn, Xe, L, 1, cl.ainv, 2, False, ap, a=k)
+        Yo = ops.su3_wilson_clover_hop_eo_n(xn, Ye, L, 1, cl.ainv, 2, True, ap, a=k)
+        return ops.su3_spinor_merge_eo(Xe, Xo, L), ops.su3_spinor_merge_eo(Ye, Yo, L), info
+
+    def clover_pseudofermion_force_n(self, xn: Tensor, phi_e: Tensor, kappa: float, c_sw: float,
+                                     clover: Optional[CloverTerm] = None, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """The force of the S_f of `clover_pseudofermion_action_n` on the links, in the convention of `grad_action_n`
+        (dS_f/dt = sum <p, F> under dU/dt = p U; the kick is p <- p - eps F): one solve, the two completion hops,
+        `l2q_su3_wilson_force` for the hop part and `l2q_su3_clover_force` for the clover part of the pseudofermion term
+        and the determinant term, into the same field.  Returns (F [nb, 4, 9, V], S_f [nb], info), info as the action's."""
+        what = 'clover_pseudofermion_force'
+        k, c = self._clover_pf_checks(what, kappa, c_sw, xn, phi_e)
+        b = self._spinor_native(what, xn, phi_e, half=True)[0]
+        cl = self._clover_for(what, xn, k, c, clover)
+        L = self._lattice_shape
+        X, Y, info = self._clover_force_fields_n(xn, b, k, c, cl, **solve_kwargs)
+        F = ops.su3_wilson_force_n(xn, X, Y, k, L, solve_kwargs.get('antiperiodic_t', True))
+        ops.su3_clover_force_n(xn, X, Y, cl.ainv, k * c, L, det_weight=b.shape[1], f_in=F, out=F)
+        info['logdet'] = self._clover_logdet_part(cl, b.shape[1])
+        return F, self._sum_fields(info['action']) + info['logdet'], info
+
+    def clover_pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, c_sw: float,
+                                   clover: Optional[CloverTerm] = None, **solve_kwargs) -> tuple[Tensor, Tensor, dict]:
+        """`clover_pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]; only the even sites of phi
+        are read"""
+        self._clover_pf_checks('clover_pseudofermion_force', kappa, c_sw, x, phi)
+        pe = self._half_reference('clover_pseudofermion_force', x, phi)[0]
+        F, s, info = self.clover_pseudofermion_force_n(self.pack(x), pe, kappa, c_sw, clover, **solve_kwargs)
         return self.unpack(F), s, info

@@ -97,6 +97,7 @@ SIGNATURES = {
     'l2q_su3_clover_invert': (I, [P, P, P, P, I, I, I, I, I, P]),
     'l2q_su3_wilson_clover_hop_eo': (I, [P, P, P, P, P, P, D, D, I, I, I, I, I, I, I, I, I, P]),
     'l2q_su3_clover_apply': (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
+    'l2q_su3_clover_force': (I, [P, P, P, P, P, P, D, D, D, I, I, I, I, I, I, P, Z, P]),
     'l2q_v_update': (I, [P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_v_update_to': (I, [P, P, P, P, P, P, D, I, I, I, I, L, P, P, Z, P]),
     'l2q_accept': (I, [P, P, P, P, P, P, I, I, P]),

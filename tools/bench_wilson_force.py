@@ -13,7 +13,16 @@ for profiles/su3_wilson_force.md, SU(3) 8^4, complex128:
                 `WilsonHMCEvenOdd` on the same thermalised links (profiles/su3_wilson_eo.md): its 'solves' stage is the
                 solve on the Schur complement plus the two hops and merges that complete X and Y; with --mixed the
                 even-odd run and then `WilsonHMCMixed` (every solve by fp32 inner CG and fp64 defect correction,
-                profiles/su3_wilson_mixed.md; --inner-tol) on the same links, from the same seed."""
+                profiles/su3_wilson_mixed.md; --inner-tol) on the same links, from the same seed.
+With --c-sw (profiles/su3_clover_force.md; --kappa 0.12 there):
+  --kernels     `l2q_su3_clover_force` on --nb chains thermalised with --clover-therm heatbath sweeps at beta = 6: the
+                entry (both kernels) with both terms at each --npf, as force and as kick in place, the determinant term
+                alone, and -- alternating window by window on the same links -- `l2q_su3_clover_bwd`, whose second pass
+                is the same gather; with the algorithmic bytes of the two kernels and the time the G kernel's bytes take
+                at the HBM figure.  Per-kernel times come from `rocprofv3 --kernel-trace --stats` on --profile-loop;
+  --profile-loop  nothing but --iters alternating calls of the two entries (npf = --npf[0]), for the profiler;
+  --trajectory  `WilsonHMCEvenOdd`, then `WilsonCloverHMC` at --c-sw on the same thermalised links, from the same seed;
+                the stage split has two more stages: the clover term with its inverse, and the clover force."""
 import argparse
 import os
 import statistics
@@ -25,7 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'l2hmc-qcd_amd'))
 from l2hmc import _ops as ops  # noqa: E402
-from l2hmc.dynamics.pytorch.fermion_hmc import WilsonHMC, WilsonHMCEvenOdd, WilsonHMCMixed  # noqa: E402
+from l2hmc.dynamics.pytorch.fermion_hmc import WilsonCloverHMC, WilsonHMC, WilsonHMCEvenOdd, WilsonHMCMixed  # noqa: E402
 from l2hmc.lattice.su3.pytorch.lattice import LatticeSU3  # noqa: E402
 
 HBM_PEAK = 8.0e12       # B/s, the spec figure that DESIGN.md's fractions are taken against
@@ -85,7 +94,72 @@ def kernels(nb, L, npf_list, iters, repeats):
          3 * LINKS, sites)
 
 
-def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=False, mixed=False, inner_tol=None):
+def clover_setup(nb, L, therm, kappa, c_sw):
+    """(lattice, thermalised native links, their clover term, a momentum) of the --c-sw kernel measurements"""
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    lat = LatticeSU3(nb, L)
+    xn = lat.pack(lat.heatbath(lat.random().to(dev), 6.0, nsweeps=therm, nover=3)[0])
+    term = lat.clover_term_n(xn, kappa, c_sw)
+    vn = ops.su3_assemble_tah_n(torch.randn((8, nb, 4, lat.volume), dtype=torch.float64, device=dev))
+    print(f'{L} x {nb} chains, beta 6.0 after {therm} heatbath sweeps (nover 3): plaquette '
+          f'{float(lat.plaq_sums_n(xn)[:, 0].mean()) / (18.0 * lat.volume):.5f}; kappa {kappa}, c_sw {c_sw}, smallest pivot '
+          f'{float(term.min_pivot.min()):.3f}')
+    return lat, xn, term, vn
+
+
+def clover_kernels(nb, L, npf_list, iters, repeats, therm, kappa, c_sw):
+    lat, xn, term, vn = clover_setup(nb, L, therm, kappa, c_sw)
+    V, sites, kc = lat.volume, nb * lat.volume, kappa * c_sw
+    f = torch.empty_like(xn)
+    G, BLOCKS = 54 * 8, 2 * 36 * 8 / 2              # bytes of G per site; of the two blocks of A^-1, odd sites only
+    link_bytes = LINKS + G + LINKS                   # the link kernel: links and G read once, the force written
+    w3 = torch.tensor([[0.3, -0.2, 0.0]], dtype=torch.float64, device=xn.device).repeat(nb, 1)
+    gx = torch.zeros_like(xn)
+    for npf in npf_list:
+        X = torch.randn((nb, npf, 12, V), dtype=torch.complex128, device=xn.device)
+        Y = torch.randn_like(X)
+        g_bytes = npf * 2 * SPINOR + BLOCKS + G
+        print(f'npf {npf}: G kernel {g_bytes:.0f} B/site = {g_bytes * sites / HBM_PEAK * 1e3:.3f} ms at 8 TB/s; link kernel '
+              f'{link_bytes} B/site (+ {LINKS} of f_in) = {link_bytes * sites / HBM_PEAK * 1e3:.3f} ms')
+        show(f'clover_force npf {npf} (both kernels)',
+             windows(lambda: ops.su3_clover_force_n(xn, X, Y, term.ainv, kc, L, det_weight=npf, out=f), iters, repeats),
+             g_bytes + link_bytes, sites)
+        show(f'clover_force npf {npf}, kick in place',
+             windows(lambda: ops.su3_clover_force_n(xn, X, Y, term.ainv, kc, L, det_weight=npf, coef=-1e-6, f_in=vn, out=vn),
+                     iters, repeats), g_bytes + link_bytes + LINKS, sites)
+        show(f'wilson_force npf {npf}, kick in place (the hop part)',
+             windows(lambda: ops.su3_wilson_force_n(xn, X, Y, kappa, L, coef=-1e-6, f_in=vn, out=vn), iters, repeats),
+             3 * LINKS + npf * 2 * SPINOR, sites)
+        del X, Y
+    show('clover_force, determinant term alone', windows(lambda: ops.su3_clover_force_n(xn, None, None, term.ainv, kc, L,
+                                                                                        det_weight=1.0, out=f), iters, repeats),
+         BLOCKS + G + link_bytes, sites)
+    # the two entries window by window on the same links: the second kernel of either is the same gather
+    X = torch.randn((nb, npf_list[0], 12, V), dtype=torch.complex128, device=xn.device)
+    Y = torch.randn_like(X)
+    fa, fb = [], []
+    for _ in range(repeats):
+        fa += windows(lambda: ops.su3_clover_force_n(xn, X, Y, term.ainv, kc, L, det_weight=1.0, out=f), iters, 1, warm=1)
+        fb += windows(lambda: ops.su3_clover_bwd_(gx, xn, w3, L), iters, 1, warm=1)
+    show(f'alternating: clover_force npf {npf_list[0]} (both kernels)', fa, npf_list[0] * 2 * SPINOR + BLOCKS + G + link_bytes, sites)
+    show('alternating: clover_bwd (both kernels)', fb, 2 * LINKS + G + G + LINKS, sites)
+
+
+def profile_loop(nb, L, npf, iters, therm, kappa, c_sw):
+    lat, xn, term, vn = clover_setup(nb, L, therm, kappa, c_sw)
+    X = torch.randn((nb, npf, 12, lat.volume), dtype=torch.complex128, device=xn.device)
+    Y = torch.randn_like(X)
+    w3 = torch.tensor([[0.3, -0.2, 0.0]], dtype=torch.float64, device=xn.device).repeat(nb, 1)
+    f, gx = torch.empty_like(xn), torch.zeros_like(xn)
+    for _ in range(iters):
+        ops.su3_clover_force_n(xn, X, Y, term.ainv, kappa * c_sw, L, det_weight=npf, out=f)
+        ops.su3_clover_bwd_(gx, xn, w3, L)
+    torch.cuda.synchronize()
+
+
+def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=False, mixed=False, inner_tol=None,
+               c_sw=None):
     dev = torch.device('cuda:0')
     torch.manual_seed(1)
     lat = LatticeSU3(nb, L)
@@ -93,7 +167,10 @@ def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=F
     print(f'{L} x {nb} chains, beta {beta} after {therm} heatbath sweeps (nover 3): plaquette '
           f'{float(lat.plaqs(x).mean()):.5f}; kappa {kappa}, npf {npf}, eps {eps}, nleapfrog {nleapfrog}, '
           f'even_odd {even_odd}, mixed {mixed}' + (f', inner_tol {inner_tol}' if mixed and inner_tol else ''))
-    if mixed:
+    if c_sw is not None:
+        print(f'c_sw {c_sw}')
+        hmc = WilsonCloverHMC(lat, beta, kappa, c_sw, eps, nleapfrog, npf=npf)
+    elif mixed:
         hmc = WilsonHMCMixed(lat, beta, kappa, eps, nleapfrog, npf=npf, inner_tol=inner_tol)
     else:
         hmc = (WilsonHMCEvenOdd if even_odd else WilsonHMC)(lat, beta, kappa, eps, nleapfrog, npf=npf)
@@ -101,6 +178,8 @@ def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=F
     hmc.trajectory_n(xn)                                         # warm-up
     # one leapfrog stage by stage
     spent = {'solves': 0.0, 'fermion force': 0.0, 'gauge kick': 0.0, 'link update': 0.0}
+    if c_sw is not None:
+        spent.update({'clover term': 0.0, 'clover force': 0.0})
     iters = []
 
     def timed(key, fn):
@@ -113,13 +192,22 @@ def trajectory(nb, L, therm, beta, kappa, eps, nleapfrog, npf, ntraj, even_odd=F
 
     def kick(xn, vn, step):
         timed('gauge kick', lambda: ops.su3_force_kick_n(xn, beta, -step, vn, L))
+        if c_sw is not None:
+            cl = timed('clover term', lambda: hmc._clover(xn))
+            X, Y, info = timed('solves', lambda: lat._clover_force_fields_n(xn, phin, kappa, c_sw, cl,
+                                                                            **hmc._solve_kw(hmc.tol_md)))
+            timed('fermion force', lambda: ops.su3_wilson_force_n(xn, X, Y, kappa, L, True, coef=-step, f_in=vn, out=vn))
+            timed('clover force', lambda: ops.su3_clover_force_n(xn, X, Y, cl.ainv, kappa * c_sw, L, det_weight=npf,
+                                                                 coef=-step, f_in=vn, out=vn))
+            iters.append(info['iters'])
+            return
         X, Y, info = timed('solves', lambda: lat._force_fields_n('pseudofermion_force', xn, phin, kappa, even_odd,
                                                                  **hmc._solve_kw(hmc.tol_md)))
         timed('fermion force', lambda: ops.su3_wilson_force_n(xn, X, Y, kappa, L, True, coef=-step, f_in=vn, out=vn))
         iters.append(info['iters'])
 
     vn = ops.su3_assemble_tah_n(torch.randn((8, nb, 4, lat.volume), dtype=torch.float64, device=dev))
-    phin, _ = (lat.pseudofermion_refresh_eo_n if even_odd else lat.pseudofermion_refresh_n)(xn, kappa, npf)
+    phin, _ = hmc._refresh_n(xn, None)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     kick(xn, vn, 0.5 * eps)
@@ -169,17 +257,30 @@ def main():
     ap.add_argument('--even-odd', action='store_true')
     ap.add_argument('--mixed', action='store_true')
     ap.add_argument('--inner-tol', type=float, default=None)
+    ap.add_argument('--c-sw', type=float, default=None)
+    ap.add_argument('--clover-therm', type=int, default=10)
+    ap.add_argument('--profile-loop', action='store_true')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU'
     torch.set_default_dtype(torch.float64)
-    if args.kernels:
+    if args.profile_loop:
+        profile_loop(args.nb, args.L, args.npf[0], args.iters, args.clover_therm, args.kappa, args.c_sw)
+        return
+    if args.kernels and args.c_sw is not None:
+        clover_kernels(args.nb, args.L, args.npf, args.iters, args.repeats, args.clover_therm, args.kappa, args.c_sw)
+    elif args.kernels:
         kernels(args.nb, args.L, args.npf, args.iters, args.repeats)
     if args.trajectory:
         modes = [(True, False), (True, True)] if args.mixed else [(False, False), (True, False)] if args.even_odd \
             else [(False, False)]
+        if args.c_sw is not None:
+            modes = [(True, False)]
         for eo, mixed in modes:
             trajectory(args.physics_nb, args.L, args.therm, args.beta, args.kappa, args.eps, args.nleapfrog, args.npf[0],
                        args.ntraj, eo, mixed, args.inner_tol)
+        if args.c_sw is not None:
+            trajectory(args.physics_nb, args.L, args.therm, args.beta, args.kappa, args.eps, args.nleapfrog, args.npf[0],
+                       args.ntraj, True, False, None, args.c_sw)
 
 
 if __name__ == '__main__':
