@@ -428,6 +428,26 @@ int l2q_su3_spinor_cg_update(void* x, void* r, const void* p, const void* q, con
                              long nsys, long V, void* stream);
 /* p = z + beta[s] p, beta a device array [nsys] of doubles.  L2Q_EINVAL as above (p must not alias z). */
 int l2q_su3_spinor_xpay(void* p, const void* z, const double* beta, long nsys, long V, void* stream);
+/* csrc/su3_spinor_mshift.hip: the BLAS-1 kernels of multi-shift CG (Jegerlehner, hep-lat/9612014).  Shifted fields are
+ * f[nsys][ns][12][V] complex128, contiguous: a (system, shift) pair is a system of every other spinor entry, so the same
+ * memory read as [nsys * ns][12][V] feeds the operator, the hops and the force.  r, p, z and out are [nsys][12][V]; V is
+ * the site count of the fields, a half lattice included.  Coefficients are device arrays of doubles.
+ * l2q_su3_spinor_mshift_update, the fused step of an iteration, per system s, with the new residual r:
+ *   p <- r + beta[s] p;  for every shift k with live[s][k] != 0:  x_k += a[s][k] p_k, then p_k <- zeta[s][k] r + b[s][k] p_k
+ * (the old p_k in the first).  a, b, zeta: [nsys][ns]; beta: [nsys]; live: [nsys][ns] int32.  A shift that is not live is
+ * neither read nor written: its x_k and p_k keep their bits.  r is read once: 3 + 4 (live shifts) field streams per site.
+ * L2Q_EINVAL, before any HIP call: a null pointer; r, p, x or ps overlapping one another (as byte ranges, so r aliasing
+ * any x_k or p_k is caught); ns < 1; a non-positive size or nsys * ns * 12 * V of 2^31 or more. */
+int l2q_su3_spinor_mshift_update(void* x, void* ps, void* p, const void* r, const double* a, const double* b,
+                                 const double* zeta, const double* beta, const int* live, long nsys, long ns, long V,
+                                 void* stream);
+/* The residual step: r -= alpha[s] z, and rr_part[nsys][ceil(V / 256)] = partial sums of |r|^2 of the new r, in the fixed
+ * order of l2q_su3_spinor_cg_update.  L2Q_EINVAL: a null pointer; r aliasing z; a bad size as there. */
+int l2q_su3_spinor_axmy_norm(void* r, const void* z, const double* alpha, double* rr_part, long nsys, long V,
+                             void* stream);
+/* out[s] = sum_k w[s][k] x[s][k] over the ns fields of a system, summed in the order of k; w: [nsys][ns].  L2Q_EINVAL: a
+ * null pointer; out overlapping x; ns < 1; a bad size as for l2q_su3_spinor_mshift_update. */
+int l2q_su3_spinor_lincomb(const void* x, const double* w, void* out, long nsys, long ns, long V, void* stream);
 /* csrc/su3_wilson_force.hip.  The force of npf two-flavour pseudofermion fields, S_f = sum_r phi_r^H (M^H M)^-1 phi_r,
  * from the solutions X_r = (M^H M)^-1 phi_r and Y_r = M X_r, both [nb][npf][12][V]: the TAH field F_f with dS_f/dt =
  * sum_links <p, F_f>, <a, b> = Re tr(a^H b), under dU/dt = p U (the convention of l2q_su3_force).  With s the seam sign

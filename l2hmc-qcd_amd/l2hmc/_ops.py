@@ -695,6 +695,68 @@ def su3_spinor_xpay_(p: torch.Tensor, z: torch.Tensor, beta: torch.Tensor) -> to
     return p
 
 
+def _shift_coef(what: str, name: str, t: torch.Tensor, shape, dtype=torch.float64) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{what}: {name} must be contiguous {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}')
+
+
+def su3_spinor_mshift_update_(x: torch.Tensor, ps: torch.Tensor, p: torch.Tensor, r: torch.Tensor, a: torch.Tensor,
+                              b: torch.Tensor, zeta: torch.Tensor, beta: torch.Tensor, live: torch.Tensor) -> None:
+    """The fused step of a multi-shift CG iteration, in place (see l2q.h): p = r + beta p on [nb, nrhs, 12, V], and for
+    every live shift k  x_k += a_k p_k, p_k = zeta_k r + b_k p_k  on the shifted fields x, ps [nb, nrhs, ns, 12, V].
+    a, b, zeta [nb, nrhs, ns] and beta [nb, nrhs] float64, live [nb, nrhs, ns] int32, all on the device."""
+    what = 'su3_spinor_mshift_update_'
+    if x.dim() != 5 or x.shape[2] < 1:
+        raise ValueError(f'{what}: need shifted fields [nb, nrhs, ns, 12, V] with ns >= 1, got {list(x.shape)}')
+    nb, nrhs, ns, _, V = x.shape
+    _spinor_check(what, 'x', x, (nb, nrhs, ns, 12, V))
+    _spinor_check(what, 'ps', ps, x.shape)
+    _spinor_check(what, 'p', p, (nb, nrhs, 12, V))
+    _spinor_check(what, 'r', r, (nb, nrhs, 12, V))
+    for name, t in (('a', a), ('b', b), ('zeta', zeta)):
+        _shift_coef(what, name, t, (nb, nrhs, ns))
+    _shift_coef(what, 'beta', beta, (nb, nrhs))
+    _shift_coef(what, 'live', live, (nb, nrhs, ns), torch.int32)
+    N.call('l2q_su3_spinor_mshift_update', x, ps, p, r, a, b, zeta, beta, live, nb * nrhs, ns, V)
+
+
+def su3_spinor_axmy_norm_(r: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor,
+                          part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """r -= alpha_s z in place on native spinor fields [nb, nrhs, 12, V], alpha [nb, nrhs] float64 on the device;
+    returns the partial sums [nb, nrhs, parts] of |r|^2 of the new r"""
+    what = 'su3_spinor_axmy_norm_'
+    if r.dim() != 4:
+        raise ValueError(f'{what}: need fields [nb, nrhs, 12, V], got {list(r.shape)}')
+    _spinor_check(what, 'r', r, r.shape)
+    _spinor_check(what, 'z', z, r.shape)
+    nb, nrhs, _, V = r.shape
+    _shift_coef(what, 'alpha', alpha, (nb, nrhs))
+    parts = -(-V // 256)
+    if part is None:
+        part = torch.empty((nb, nrhs, parts), dtype=torch.float64, device=r.device)
+    else:
+        _shift_coef(what, 'part', part, (nb, nrhs, parts))
+    N.call('l2q_su3_spinor_axmy_norm', r, z, alpha, part, nb * nrhs, V)
+    return part
+
+
+def su3_spinor_lincomb(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = sum_k w_k x_k [nb, nrhs, 12, V] over the ns fields of a system of x [nb, nrhs, ns, 12, V], w [nb, nrhs, ns]
+    float64 on the device; summed in the order of k.  out None = a new field."""
+    what = 'su3_spinor_lincomb'
+    if x.dim() != 5 or x.shape[2] < 1:
+        raise ValueError(f'{what}: need shifted fields [nb, nrhs, ns, 12, V] with ns >= 1, got {list(x.shape)}')
+    nb, nrhs, ns, _, V = x.shape
+    _spinor_check(what, 'x', x, (nb, nrhs, ns, 12, V))
+    _shift_coef(what, 'w', w, (nb, nrhs, ns))
+    if out is None:
+        out = torch.empty((nb, nrhs, 12, V), dtype=C128, device=x.device)
+    else:
+        _spinor_check(what, 'out', out, (nb, nrhs, 12, V))
+    N.call('l2q_su3_spinor_lincomb', x, w, out, nb * nrhs, ns, V)
+    return out
+
+
 def su3_wilson_force_n(xn: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, kappa: float, lat: Sequence[int],
                        antiperiodic_t: bool = True, coef: float = 1.0, f_in: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -116,7 +116,11 @@ class WilsonHMC:
                    'cg_iters_h': {'mean': float(hinfo['iters'].to(torch.float64).mean()),
                                   'max': int(hinfo['iters'].max())},
                    'unconverged': info['unconverged'] + int((~hinfo['converged']).sum())}
+        self._more_metrics(metrics, info, hinfo)
         return xo, metrics
+
+    def _more_metrics(self, metrics: dict, info: dict, hinfo: dict) -> None:
+        """what a subclass adds to the metrics of a trajectory from the infos of its leapfrog and its Hamiltonian"""
 
     def trajectory(self, x: Tensor, generator: Optional[torch.Generator] = None) -> tuple[Tensor, dict]:
         """`trajectory_n` in the reference layout x[nb, 4, T, X, Y, Z, 3, 3]: momentum refresh (the `assemble_tah`
@@ -216,3 +220,88 @@ class WilsonCloverHMC(WilsonHMCEvenOdd):
         phin, s0 = lat.clover_pseudofermion_refresh_n(xn, self.kappa, self.c_sw, self.npf, generator, self.antiperiodic_t,
                                                       cl)
         return phin, s0 + lat._clover_logdet_part(cl, self.npf)
+
+
+class WilsonRHMC(WilsonHMCEvenOdd):
+    """HMC with ONE flavour of Wilson quarks at `kappa` by the rational action S_1 = sum_r phi_e,r^H R(Mhat^H Mhat) phi_e,r
+    (`LatticeSU3.rhmc_pseudofermion_action_n`; `rat` = `rational.zolotarev_inv_sqrt(n, ra, rb)`, whose interval must hold
+    the spectrum of Mhat^H Mhat along the trajectory: `LatticeSU3.schur_spectrum_n`), every solve a multi-shift CG.  With
+    `kappa_light` it also carries the two-flavour even-odd pseudofermion of `WilsonHMCEvenOdd` at that hopping parameter:
+    N_f = 2 + 1.  The ensemble weight of the one flavour is det R^-1, |det M| up to the relative error rat.delta of R; no
+    reweighting is done.  Draw order of a trajectory: the momentum normals, the light pseudofermion noise (if any), then
+    the strange one, then the accept uniforms.  The fermion kicks go in place into the momentum in the same order, light
+    then strange.  `phin` is the pair (phi_light or None, phi_strange), each [nb, npf, 12, V/2].  Metrics: those of the
+    parent -- 'cg_iters_md' and 'cg_iters_h' count the light solves where there are any, else the multi-shift ones --
+    plus 'cg_iters_ms_md' and 'cg_iters_ms_h' for the multi-shift solves.  Double precision, plain Wilson only."""
+
+    def __init__(self, lattice: LatticeSU3, beta: float, kappa: float, eps: float, nleapfrog: int, *, rat,
+                 kappa_light: Optional[float] = None, **kwargs) -> None:
+        super().__init__(lattice, beta, kappa, eps, nleapfrog, **kwargs)
+        lattice._rat_checks('WilsonRHMC', rat)
+        if kappa_light is not None and (isinstance(kappa_light, bool) or not np.isfinite(kappa_light)):
+            raise ValueError(f'WilsonRHMC: kappa_light must be a finite number or None, got {kappa_light!r}')
+        self.rat = rat
+        self.kappa_light = None if kappa_light is None else float(kappa_light)
+
+    def _kick_(self, xn: Tensor, vn: Tensor, phin, step: float, infos: list) -> None:
+        """vn -= step * (F_g + F_light + F_strange), in place, in that order; infos receives the light solve's info (if
+        any), then the multi-shift solve's"""
+        lat, L = self.lattice, self.lattice._lattice_shape
+        if lat.c1 == 0:
+            ops.su3_force_kick_n(xn, self.beta, -step, vn, L)
+        else:
+            ops.axpy_(vn, lat.grad_action_n(xn, self.beta), -step)
+        phi_l, phi_s = phin
+        if phi_l is not None:
+            X, Y, info = lat._force_fields_n('pseudofermion_force', xn, phi_l, self.kappa_light, True,
+                                             **self._solve_kw(self.tol_md))
+            ops.su3_wilson_force_n(xn, X, Y, self.kappa_light, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
+            infos.append(info)
+        X, Y, ms = lat._rhmc_force_fields_n(xn, phi_s, self.kappa, self.rat, **self._solve_kw(self.tol_md))
+        ops.su3_wilson_force_n(xn, X, Y, self.kappa, L, self.antiperiodic_t, coef=-step, f_in=vn, out=vn)
+        infos.append(ms)
+
+    def leapfrog_n(self, xn: Tensor, vn: Tensor, phin) -> tuple[Tensor, Tensor, dict]:
+        """`WilsonHMC.leapfrog_n`; info['unconverged'] counts the systems of every solve, light and multi-shift;
+        info['cg_iters_ms'] [kicks, nb, npf] are the multi-shift solves' iterations and info['cg_iters'] the light
+        solves' where there is a light field, else the same multi-shift ones"""
+        x1, v1, info = super().leapfrog_n(xn, vn, phin)
+        if phin[0] is not None:                      # the kicks appended light, multi-shift, light, ...
+            info['cg_iters'], info['cg_iters_ms'] = info['cg_iters'][0::2], info['cg_iters'][1::2]
+        else:
+            info['cg_iters_ms'] = info['cg_iters']
+        return x1, v1, info
+
+    def _refresh_n(self, xn: Tensor, generator: Optional[torch.Generator]):
+        """((phi_light or None, phi_strange), S_f on xn): the light heatbath first, then the strange one"""
+        lat = self.lattice
+        phi_l, s0 = None, 0.0
+        if self.kappa_light is not None:
+            phi_l, s0 = lat.pseudofermion_refresh_eo_n(xn, self.kappa_light, self.npf, generator, self.antiperiodic_t)
+        phi_s, s1 = lat.rhmc_pseudofermion_refresh_n(xn, self.kappa, self.rat, self.npf, generator, self.antiperiodic_t,
+                                                     tol=self.tol_h, max_iter=self.max_iter)
+        return (phi_l, phi_s), s0 + s1
+
+    def hamiltonian_n(self, xn: Tensor, vn: Tensor, phin, info: Optional[dict] = None) -> Tensor:
+        """H [nb] = kinetic + S_g + S_light + S_1, the solves at tol_h; `info`, if given, receives the light solve's info
+        (without a light field: the multi-shift solve's) and under 'multishift' the multi-shift solve's"""
+        lat = self.lattice
+        phi_l, phi_s = phin
+        sf, ms = lat.rhmc_pseudofermion_action_n(xn, phi_s, self.kappa, self.rat, **self._solve_kw(self.tol_h))
+        sinfo = ms
+        if phi_l is not None:
+            sl, sinfo = lat.pseudofermion_action_n(xn, phi_l, self.kappa_light, even_odd=True,
+                                                   **self._solve_kw(self.tol_h))
+            sf = sl + sf
+        if info is not None:
+            info.update(sinfo)
+            info['multishift'] = ms
+        return ops.su3_kinetic_n(vn) + lat.action_n(xn, self.beta) + sf
+
+    def _more_metrics(self, metrics: dict, info: dict, hinfo: dict) -> None:
+        ms = hinfo['multishift']
+        for key, it in (('cg_iters_ms_md', info['cg_iters_ms']), ('cg_iters_ms_h', ms['iters'])):
+            it = it.to(torch.float64)
+            metrics[key] = {'mean': float(it.mean()), 'max': int(it.max())}
+        if self.kappa_light is not None:             # the parent counted the light solve of the Hamiltonian only
+            metrics['unconverged'] += int((~ms['converged']).sum())

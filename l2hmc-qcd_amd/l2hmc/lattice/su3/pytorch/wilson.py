@@ -2,7 +2,8 @@
 csrc/su3_wilson_f32.hip, csrc/su3_wilson_force.hip, csrc/su3_wilson_clover.hip, csrc/su3_clover_force.hip): the mixin ``WilsonFermions`` with the
 operator, the two solvers on one CG loop (``_CG``), their even-odd and mixed-precision forms (``_MixedSolve``: fp64 defect
 correction around the same loop on fp32 fields), the clover-improved operator and its even-odd solve (``CloverTerm``,
-``_CloverSchurOp``), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
+``_CloverSchurOp``), the multi-shift CG (``_CG.multishift``, kernels: csrc/su3_spinor_mshift.hip) with the one-flavour
+rational pseudofermion on it (``rational.py``), the propagator and the pseudofermions; ``pion_correlator`` / ``effective_mass``; and ``draw``, the
 random-draw rule of the fermion layer."""
 from __future__ import annotations
 
@@ -210,6 +211,57 @@ class _CG:
         action = apply(X, Y, False)
         apply(Y, z, True, norm=False)
         return Y, action
+
+    def multishift(self, shifts: Tensor, freeze: bool = True) -> Tensor:
+        """(A + sigma_k) x_k = b for A = op^H op and every shift sigma_k >= 0 of `shifts` [ns] at once, by multi-shift
+        CG (Jegerlehner, hep-lat/9612014) from x_k = 0: the base system is the unshifted one, carried through p, r,
+        alpha and beta (it has no x of its own); every shifted residual is zeta_k r.  Per iteration the two applies of
+        `normal`, the residual step `l2q_su3_spinor_axmy_norm`, the zeta, a, b recurrences as [nb, nrhs, ns] tensor ops
+        on the device, and the fused `l2q_su3_spinor_mshift_update`.  A system leaves at a check with |r|^2 <= tol^2 bb;
+        at a check (freeze) a single shift with zeta_k^2 |r|^2 <= tol^2 bb has its `live` cleared and is frozen from then
+        on.  Returns X [nb, nrhs, ns, 12, sites]; leaves `shift_iters` [nb, nrhs, ns], the check at which a shift froze
+        (or its system left; max_iter if never)."""
+        b, r, q, z, apply = self.b, self.r, self.q, self.z, self.apply
+        nb, nrhs, ns = b.shape[0], b.shape[1], shifts.numel()
+        sig = shifts.to(torch.float64).reshape(1, 1, ns)
+        X = torch.zeros((nb, nrhs, ns, *b.shape[2:]), dtype=b.dtype, device=b.device)
+        P = b[:, :, None].repeat(1, 1, ns, 1, 1)                     # a copy also at ns = 1
+        self.p = p = b.clone()
+        one = torch.ones((nb, nrhs, ns), dtype=torch.float64, device=b.device)
+        zeta, zeta_old = one, one
+        alpha_old, beta_old = torch.ones_like(self.zero), self.zero
+        slive = torch.ones((nb, nrhs, ns), dtype=torch.bool, device=b.device)
+        self.shift_iters = torch.full((nb, nrhs, ns), self.max_iter, dtype=torch.int64, device=b.device)
+        state = {'rr': self.bb0, 'it': 0}
+
+        def rnorm():                       # called once per check, before the systems that converged leave
+            nonlocal slive
+            bound = (self.tol2 * self.bb)[..., None]
+            done = slive & self.active[..., None] & ((zeta * zeta * state['rr'][..., None] <= bound) if freeze
+                                                     else (state['rr'] <= self.tol2 * self.bb)[..., None])
+            self.shift_iters = torch.where(done, state['it'], self.shift_iters)
+            slive = slive & ~done
+            return state['rr']
+        for active in self.iterations(rnorm):
+            rr = state['rr']
+            qq = apply(p, q, False)
+            apply(q, z, True, norm=False)
+            alpha = ratio(active, rr, qq)
+            rn = ops.sum_parts(ops.su3_spinor_axmy_norm_(r, z, alpha, self.rpart))
+            beta = ratio(active, rn, rr)
+            al, bt, alo, bto = alpha[..., None], beta[..., None], alpha_old[..., None], beta_old[..., None]
+            den = al * bto * (zeta_old - zeta) + zeta_old * alo * (1.0 + sig * al)
+            lv = slive & (al > 0) & (den != 0)
+            zn = torch.where(lv, zeta * zeta_old * alo / torch.where(lv, den, one), zeta)
+            rat = torch.where(lv, zn / torch.where(lv, zeta, one), torch.zeros_like(one))
+            ops.su3_spinor_mshift_update_(X, P, p, r, (al * rat).contiguous(), (bt * rat * rat).contiguous(),
+                                          zn.contiguous(), beta, lv.to(torch.int32).contiguous())
+            zeta_old, zeta = torch.where(lv, zeta, zeta_old), zn
+            moved = alpha > 0
+            alpha_old, beta_old = torch.where(moved, alpha, alpha_old), torch.where(moved, beta, beta_old)
+            state['rr'], state['it'] = rn, state['it'] + 1
+        self.shift_iters = torch.where(self.bb[..., None] <= self.tol2 * self.bb[..., None], 0, self.shift_iters)
+        return X
 
     def iterations(self, rnorm):
         """`active` [nb, nrhs] once per iteration, for `ratio`.  At a check a system with rnorm() <= tol^2 |b|^2 leaves
@@ -834,6 +886,238 @@ class WilsonFermions:
         b, single = self._spinor_native('wilson_solve_schur_normal', xn, phi_e, half=True)
         op = _SchurOp(xn, k, L, antiperiodic_t, b)
         return self._solve_normal(_CG('wilson_solve_schur_normal', b, single, op, tol, max_iter, check_every))
+
+    # ------------------------------------------------------------ multi-shift CG on the Schur complement
+    @staticmethod
+    def _shift_list(what: str, shifts) -> list:
+        try:
+            s = [float(v) for v in shifts]
+        except (TypeError, ValueError):
+            s = []
+        if not s or not all(np.isfinite(v) and v >= 0.0 for v in s):
+            raise ValueError(f'LatticeSU3.{what}: shifts must be a non-empty sequence of finite numbers >= 0, got '
+                             f'{shifts!r}')
+        return s
+
+    def wilson_solve_multishift_n(self, xn: Tensor, phi_e: Tensor, kappa: float, shifts, tol: float = 1e-10,
+                                  max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                                  clover: Optional[CloverTerm] = None, freeze: bool = True) -> tuple[Tensor, dict]:
+        """(Mhat^H Mhat + sigma_k) X_k = phi_e for every system of the even half field phi_e [nb, nrhs, 12, V/2] (or [nb,
+        12, V/2]) and every shift sigma_k >= 0 at once, by multi-shift CG (`_CG.multishift`; Jegerlehner) on the even-odd
+        Schur complement of M = 1 - kappa H; with clover= a `CloverTerm` of these links (its kappa must be this one) on
+        that of the clover-improved operator.  One Krylov space for all shifts: per iteration the two operator applies of
+        `wilson_solve_schur_normal_n`, one `l2q_su3_spinor_axmy_norm` and one fused `l2q_su3_spinor_mshift_update`, which
+        reads the residual once for all shifts.  The stopping test is that of the unshifted system, |r|^2 <= tol^2
+        |phi_e|^2, every check_every iterations; the shifted residuals are zeta_k r with |zeta_k| <= 1.  With freeze (the
+        default) a single shift that meets the test alone stops being updated at that check.  A system's bits do not
+        depend on the batch.  Returns (X [nb, nrhs, ns, 12, V/2], info): 'iters', 'converged' [nb, nrhs]; 'shift_iters'
+        and 'residual' [nb, nrhs, ns], the latter |phi_e - (Mhat^H Mhat + sigma_k) X_k| / |phi_e| recomputed by one
+        operator pass over all nrhs * ns systems.  Never raises on non-convergence; phi_e = 0 gives X = 0.  fp64 only."""
+        what = 'wilson_solve_multishift'
+        k = self._pf_checks(what, kappa, xn, phi_e)
+        _CG.check_args(what, tol, max_iter, check_every)
+        sig = self._shift_list(what, shifts)
+        L = self._eo_lattice(what)
+        b, single = self._spinor_native(what, xn, phi_e, half=True)
+        if clover is not None:
+            clover = self._clover_for(what, xn, k, getattr(clover, 'c_sw', None), clover)
+
+        def make_op(like):
+            if clover is None:
+                return _SchurOp(xn, k, L, antiperiodic_t, like)
+            return _CloverSchurOp(xn, k, L, antiperiodic_t, like, clover)
+        cg = _CG(what, b, single, make_op(b), tol, max_iter, check_every)
+        sg = torch.tensor(sig, dtype=torch.float64, device=b.device)
+        X = cg.multishift(sg, freeze=bool(freeze))
+        nb, nrhs, ns = X.shape[:3]
+        Xw = X.view(nb, nrhs * ns, 12, X.shape[-1])
+        R = b[:, :, None].repeat(1, 1, ns, 1, 1).view_as(Xw)           # a copy also at ns = 1: b is the caller's
+        Q, Z = torch.empty_like(Xw), torch.empty_like(Xw)
+        wide = make_op(Xw)
+        wide.apply(Xw, Q, False, norm=False)
+        wide.apply(Q, Z, True, norm=False)
+        ops.su3_spinor_axmy_norm_(R, Z, torch.ones((nb, nrhs * ns), dtype=torch.float64, device=b.device))
+        rr = ops.sum_parts(ops.su3_spinor_axmy_norm_(R, Xw, sg.repeat(nb, nrhs).contiguous())).view(nb, nrhs, ns)
+        bb = cg.bb[..., None]
+        res = torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb)))
+        info = {'iters': cg.iters, 'converged': ~cg.active, 'shift_iters': cg.shift_iters, 'residual': res}
+        if single:
+            X, info = X[:, 0], {key: v[:, 0] for key, v in info.items()}
+        return X, info
+
+    def wilson_solve_multishift(self, x: Tensor, phi: Tensor, kappa: float, shifts, tol: float = 1e-10,
+                                max_iter: int = 1000, check_every: int = 10, antiperiodic_t: bool = True,
+                                clover: Optional[CloverTerm] = None, freeze: bool = True) -> tuple[Tensor, dict]:
+        """`wilson_solve_multishift_n` in the reference layout: of the full-shape phi [nb, nrhs, T, X, Y, Z, 4, 3] (or
+        without nrhs) only the even sites are read; X is [nb, nrhs, ns, T, X, Y, Z, 4, 3], zero on the odd sites."""
+        what = 'wilson_solve_multishift'
+        self._pf_checks(what, kappa, x, phi)
+        _CG.check_args(what, tol, max_iter, check_every)
+        self._shift_list(what, shifts)
+        self._eo_lattice(what)
+        pe, single = self._half_reference(what, x, phi)
+        X, info = self.wilson_solve_multishift_n(self.pack(x), pe, kappa, shifts, tol, max_iter, check_every,
+                                                 antiperiodic_t, clover, freeze)
+        nb, nrhs, ns = X.shape[:3]
+        out = self._half_to_reference(X.reshape(nb, nrhs * ns, 12, -1))
+        out = out.reshape(nb, nrhs, ns, *out.shape[2:])
+        if single:
+            out, info = out[:, 0], {key: v[:, 0] for key, v in info.items()}
+        return out, info
+
+    # ------------------------------------------------------------ one flavour: the rational (RHMC) pseudofermion
+    def _rat_checks(self, what: str, rat) -> None:
+        from .rational import Rational
+        if not isinstance(rat, Rational):
+            raise ValueError(f'LatticeSU3.{what}: rat must be a `rational.Rational` (zolotarev_inv_sqrt), got '
+                             f'{type(rat)!r}')
+
+    def rhmc_pseudofermion_refresh_n(self, xn: Tensor, kappa: float, rat, npf: int = 1,
+                                     generator: Optional[torch.Generator] = None, antiperiodic_t: bool = True,
+                                     **solve_kwargs) -> tuple[Tensor, Tensor]:
+        """The heatbath of the one-flavour action S_1 = phi_e^H R(Mhat^H Mhat) phi_e (`rhmc_pseudofermion_action_n`):
+        eta_e drawn by the rule of `pseudofermion_refresh_eo_n` (same shape, same generator handling), and phi_e = C
+        eta_e with C C^H = R^-1 (rational.py), Qhat = gamma5 Mhat: one multi-shift solve Z_k = (Mhat^H Mhat + nu_k^2)^-1
+        eta, two `l2q_su3_spinor_lincomb` W = sum_k c_k Z_k and Vv = sum_k c_k nu_k Z_k, and phi_e = A^(-1/2) (eta + i
+        gamma5 Mhat W + Vv); gamma5 = diag(-1, -1, 1, 1) is a sign on components 0..5.  Returns (phi_e [nb, npf, 12,
+        V/2], S0 [nb]): S0 = |eta_e|^2 is S_1(phi_e) on these links exactly (to the solver's tolerance), without a
+        further solve.  solve_kwargs: tol, max_iter, check_every of the solve."""
+        what = 'rhmc_pseudofermion_refresh'
+        k = self._pf_checks(what, kappa, xn)
+        self._rat_checks(what, rat)
+        if isinstance(npf, bool) or not isinstance(npf, (int, np.integer)) or int(npf) < 1:
+            raise ValueError(f'LatticeSU3.{what}: npf must be an integer >= 1, got {npf!r}')
+        L = self._eo_lattice(what)
+        shape = (xn.shape[0], int(npf), 12, self.volume // 2, 2)
+        eta = torch.view_as_complex(draw(shape, generator, xn.device) * float(np.sqrt(0.5))).contiguous()
+        Zk, _ = self.wilson_solve_multishift_n(xn, eta, k, rat.nu ** 2, antiperiodic_t=antiperiodic_t, **solve_kwargs)
+        coef = torch.tensor(np.stack([rat.c, rat.c * rat.nu]), dtype=torch.float64, device=xn.device)
+        w = [c.repeat(shape[0], shape[1], 1).contiguous() for c in coef]
+        W, Vv = ops.su3_spinor_lincomb(Zk, w[0]), ops.su3_spinor_lincomb(Zk, w[1])
+        MW = torch.empty_like(W)
+        _SchurOp(xn, k, L, antiperiodic_t, W).apply(W, MW, False, norm=False)
+        g5 = torch.ones(12, dtype=torch.float64, device=xn.device)
+        g5[:6] = -1.0
+        phi = ((eta + 1j * g5[None, None, :, None] * MW + Vv) / float(np.sqrt(rat.A))).contiguous()
+        zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
+        return phi, self._sum_fields(_norm2(eta, phi, torch.zeros_like(eta), zero))      # |eta|^2
+
+    def rhmc_pseudofermion_refresh(self, x: Tensor, kappa: float, rat, npf: int = 1,
+                                   generator: Optional[torch.Generator] = None, antiperiodic_t: bool = True,
+                                   **solve_kwargs) -> tuple[Tensor, Tensor]:
+        """`rhmc_pseudofermion_refresh_n` in the reference layout: the full shape phi[nb, npf, T, X, Y, Z, 4, 3], phi_e
+        on the even sites and zero on the odd ones"""
+        self._pf_checks('rhmc_pseudofermion_refresh', kappa, x)
+        self._rat_checks('rhmc_pseudofermion_refresh', rat)
+        self._eo_lattice('rhmc_pseudofermion_refresh')
+        phi, s0 = self.rhmc_pseudofermion_refresh_n(self.pack(x), kappa, rat, npf, generator, antiperiodic_t,
+                                                    **solve_kwargs)
+        return self._half_to_reference(phi), s0
+
+    def _rhmc_solve_n(self, what: str, xn: Tensor, phi_e: Tensor, kappa, rat, solve_kwargs):
+        """(b [nb, npf, 12, V/2], X [nb, npf, n, 12, V/2], info) of the solve with the poles a_2k as shifts"""
+        k = self._pf_checks(what, kappa, xn, phi_e)
+        self._rat_checks(what, rat)
+        self._eo_lattice(what)
+        b = self._spinor_native(what, xn, phi_e, half=True)[0]
+        X, info = self.wilson_solve_multishift_n(xn, b, k, rat.poles, **solve_kwargs)
+        return k, b, X, info
+
+    def rhmc_pseudofermion_action_n(self, xn: Tensor, phi_e: Tensor, kappa: float, rat,
+                                    **solve_kwargs) -> tuple[Tensor, dict]:
+        """The action of ONE flavour of Wilson quarks per pseudofermion field on the even-odd Schur complement,
+            S_1 = sum_r phi_e,r^H R(Mhat^H Mhat) phi_e,r,   R(y) ~ y^(-1/2) on [rat.ra, rat.rb] (rational.py),
+        which puts det R^-1 ~ |det Mhat| = |det M| into the ensemble, up to the relative error rat.delta of R; the
+        spectrum of Mhat^H Mhat must lie inside [ra, rb] (`schur_spectrum_n`).  No reweighting by the error of R is
+        done.  One `wilson_solve_multishift_n` with the poles a_2k as shifts (whose keywords the others are), and S = A
+        (|phi|^2 + sum_k rho_k <phi, X_k>) with <phi, X_k> = |Mhat X_k|^2 + a_2k |X_k|^2 from fixed-order partial sums of
+        norms (no cancellation: every term is positive), summed in the order of k, then of the fields.  Returns (S_1 [nb], info); info['action'] [nb, npf] is S per field."""
+        k, b, X, info = self._rhmc_solve_n('rhmc_pseudofermion_action', xn, phi_e, kappa, rat, solve_kwargs)
+        nb, npf, n = X.shape[:3]
+        zero = torch.zeros((nb, npf), dtype=torch.float64, device=b.device)
+        s = _norm2(b.clone(), b, torch.zeros_like(b), zero)
+        # <phi, X_k> = <(Mhat^H Mhat + a_2k) X_k, X_k> = |Mhat X_k|^2 + a_2k |X_k|^2: two norms per (field, shift), the first
+        # fused into one operator pass over the npf * n systems, the second from the residual kernel at alpha = 0
+        Xw = X.view(nb, npf * n, 12, -1)
+        Q = torch.empty_like(Xw)
+        qq = _SchurOp(xn, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True), Xw).apply(Xw, Q, False)
+        xx = ops.sum_parts(ops.su3_spinor_axmy_norm_(Xw, Q, torch.zeros_like(qq)))
+        dots = (qq + torch.tensor(np.tile(rat.poles, npf), dtype=torch.float64, device=b.device) * xx).view(nb, npf, n)
+        for j in range(n):
+            s = s + float(rat.rho[j]) * dots[:, :, j]
+        info['action'] = float(rat.A) * s
+        return self._sum_fields(info['action']), info
+
+    def rhmc_pseudofermion_action(self, x: Tensor, phi: Tensor, kappa: float, rat, **solve_kwargs) -> tuple[Tensor, dict]:
+        """`rhmc_pseudofermion_action_n` in the reference layout; only the even sites of phi are read"""
+        self._pf_checks('rhmc_pseudofermion_action', kappa, x, phi)
+        self._eo_lattice('rhmc_pseudofermion_action')
+        pe = self._half_reference('rhmc_pseudofermion_action', x, phi)[0]
+        return self.rhmc_pseudofermion_action_n(self.pack(x), pe, kappa, rat, **solve_kwargs)
+
+    def rhmc_pseudofermion_force_n(self, xn: Tensor, phi_e: Tensor, kappa: float, rat,
+                                   **solve_kwargs) -> tuple[Tensor, dict]:
+        """The force of S_1 on the links, in the convention of `grad_action_n`: with X_k = (Mhat^H Mhat + a_2k)^-1 phi_e
+        of the same solve as the action's, dS_1 = -A sum_k rho_k X_k^H d(Mhat^H Mhat) X_k, which is the two-flavour
+        force of the fields X'_k = sqrt(A rho_k) X_k, Y'_k = Mhat X'_k taken as npf * n systems: the odd halves as in
+        `_force_fields_n`, one `l2q_su3_wilson_force`, no new force kernel.  Returns (F [nb, 4, 9, V], info)."""
+        k = self._pf_checks('rhmc_pseudofermion_force', kappa, xn, phi_e)
+        X, Y, info = self._rhmc_force_fields_n(xn, phi_e, kappa, rat, **solve_kwargs)
+        return ops.su3_wilson_force_n(xn, X, Y, k, self._lattice_shape, solve_kwargs.get('antiperiodic_t', True)), info
+
+    def _rhmc_force_fields_n(self, xn: Tensor, phi_e: Tensor, kappa: float, rat, **solve_kwargs):
+        """(X, Y, info): the full fields [nb, npf * n, 12, V] whose `l2q_su3_wilson_force` is the force of S_1"""
+        what = 'rhmc_pseudofermion_force'
+        k, b, X, info = self._rhmc_solve_n(what, xn, phi_e, kappa, rat, solve_kwargs)
+        L = self._lattice_shape
+        ap = solve_kwargs.get('antiperiodic_t', True)
+        nb, npf, n = X.shape[:3]
+        w = torch.tensor(np.sqrt(rat.A * rat.rho), dtype=torch.float64, device=b.device)
+        Xe = (X * w[None, None, :, None, None]).view(nb, npf * n, 12, -1)
+        Ye = torch.empty_like(Xe)
+        _SchurOp(xn, k, L, ap, Xe).apply(Xe, Ye, False, norm=False)
+        Xo = ops.su3_wilson_hop_eo_n(xn, Xe, L, 1, False, ap, a=k)
+        Yo = ops.su3_wilson_hop_eo_n(xn, Ye, L, 1, True, ap, a=k)
+        return ops.su3_spinor_merge_eo(Xe, Xo, L), ops.su3_spinor_merge_eo(Ye, Yo, L), info
+
+    def rhmc_pseudofermion_force(self, x: Tensor, phi: Tensor, kappa: float, rat, **solve_kwargs) -> tuple[Tensor, dict]:
+        """`rhmc_pseudofermion_force_n` in the reference layout: F[nb, 4, T, X, Y, Z, 3, 3]"""
+        self._pf_checks('rhmc_pseudofermion_force', kappa, x, phi)
+        self._eo_lattice('rhmc_pseudofermion_force')
+        pe = self._half_reference('rhmc_pseudofermion_force', x, phi)[0]
+        F, info = self.rhmc_pseudofermion_force_n(self.pack(x), pe, kappa, rat, **solve_kwargs)
+        return self.unpack(F), info
+
+    def schur_spectrum_n(self, xn: Tensor, kappa: float, iters: int = 30, generator: Optional[torch.Generator] = None,
+                         antiperiodic_t: bool = True, **solve_kwargs) -> tuple[Tensor, Tensor]:
+        """(lambda_min, lambda_max) estimates [nb] of Mhat^H Mhat on these links, for the choice of [ra, rb] of the
+        rational approximation: lambda_max by `iters` steps of power iteration (a lower estimate of the largest
+        eigenvalue), lambda_min by `iters` steps of inverse iteration on `wilson_solve_schur_normal_n` (an upper
+        estimate of the smallest), both as Rayleigh quotients of one random start vector.  Leave a margin: the rigorous
+        bound is lambda_max <= (1 + 64 kappa^2)^2, from ||H|| <= 8."""
+        what = 'schur_spectrum'
+        k = self._pf_checks(what, kappa, xn)
+        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
+            raise ValueError(f'LatticeSU3.{what}: iters must be an integer >= 1, got {iters!r}')
+        L = self._eo_lattice(what)
+        shape = (xn.shape[0], 1, 12, self.volume // 2, 2)
+        v0 = torch.view_as_complex(draw(shape, generator, xn.device)).contiguous()
+        op = _SchurOp(xn, k, L, antiperiodic_t, v0)
+        zero = torch.zeros(shape[:2], dtype=torch.float64, device=xn.device)
+
+        def normalised(f):
+            return (f / torch.sqrt(_norm2(f.clone(), f, torch.zeros_like(f), zero))[..., None, None]).contiguous()
+        v, q, z = normalised(v0), torch.empty_like(v0), torch.empty_like(v0)
+        for _ in range(int(iters)):
+            lmax = op.apply(v, q, False)                                    # <v, A v> = |Mhat v|^2 at |v| = 1
+            op.apply(q, z, True, norm=False)
+            v = normalised(z)
+        u = normalised(v0)
+        for _ in range(int(iters)):
+            X, _, info = self.wilson_solve_schur_normal_n(xn, u, k, antiperiodic_t=antiperiodic_t, **solve_kwargs)
+            u = normalised(X)
+        lmin = op.apply(u, q, False)
+        return lmin[:, 0], lmax[:, 0]
 
     def _force_fields_n(self, what: str, xn: Tensor, phin: Tensor, kappa: float, even_odd: bool,
                         **solve_kwargs) -> tuple[Tensor, Tensor, dict]:

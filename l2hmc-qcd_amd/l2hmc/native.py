@@ -85,6 +85,9 @@ SIGNATURES = {
     'l2q_su3_wilson_apply': (I, [P, P, P, P, D, I, I, I, I, I, I, I, P]),
     'l2q_su3_spinor_cg_update': (I, [P, P, P, P, P, P, L, L, P]),
     'l2q_su3_spinor_xpay': (I, [P, P, P, L, L, P]),
+    'l2q_su3_spinor_mshift_update': (I, [P, P, P, P, P, P, P, P, P, L, L, L, P]),
+    'l2q_su3_spinor_axmy_norm': (I, [P, P, P, P, L, L, P]),
+    'l2q_su3_spinor_lincomb': (I, [P, P, P, L, L, L, P]),
     'l2q_su3_wilson_force': (I, [P, P, P, P, P, D, D, I, I, I, I, I, I, I, P]),
     'l2q_su3_wilson_hop_eo': (I, [P, P, P, P, P, D, D, I, I, I, I, I, I, I, I, P]),
     'l2q_su3_links_demote_eo': (I, [P, P, I, I, I, I, I, P]),
